@@ -34,6 +34,13 @@ kernel kind, input size, HIP-event duration) - `frac` is bytes actually moved th
 dominant kernel / its measured duration / 8 TB/s and is <= 1 by construction; SURVEY section 8d's
 one-round-per-pass byte model is reported separately as `sec8d_credited_frac`.  The CPU baseline and
 every correctness check use oracle/ as the checker only; the measured path is libsumcheck_hip.so.
+
+--dump-outputs DIR writes what the LAST timed step returned to its caller as DIR/<name>.npy (rank 0): prover, gkr and
+triangle -> c_1, round_evals [n][3], challenges [n]; mle -> evaluate_le, evaluate_be, fix_variables_k<k>; gnew -> f_a, f_b.
+Every value is a 64-bit field word (Montgomery form, as the library hands it out), stored exactly as float64 in two 32-bit
+limbs: shape = the output's shape + (2,), [..., 0] the low and [..., 1] the high half.  An output of more than 2^18 words is
+stored as a fixed, seeded sample of 2^18 of them, its word indices in <name>_index.npy.  The inputs are fixed seeds, so two
+builds run with the same arguments can be compared file for file.
 """
 import argparse
 import json
@@ -48,6 +55,9 @@ os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # the pool's driver on
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
+DUMP_SAMPLE_WORDS = 1 << 18   # --dump-outputs: larger outputs are stored as a seeded sample of this many words
+DUMP_MAX_BYTES = 64 << 20     # ... and everything one run writes stays below this
+LAST_OUTPUTS = {}             # --dump-outputs: {name: uint64 array} of the last timed step, filled by the workload on rank 0
 ABANDONED = []   # contexts whose stream may be stuck in a collective that never completes: never destroyed; the process
                  # leaves through os._exit once rank 0's line is out
 FIELD = {"p": None, "name": "GoldilocksMont", "label": "Goldilocks p=2^64-2^32+1"}   # set by main() from --field
@@ -74,6 +84,34 @@ def check_identities(F, c1, evals, ch, final_eval):
     if claim != final_eval:
         return "g_n(r_n) != g(r)"
     return None
+
+
+def keep_outputs(args, **outputs):
+    """--dump-outputs: remember what the last timed step returned (host copies, taken outside the timed region)"""
+    import numpy as np
+    if args.dump_outputs:
+        for name, v in outputs.items():
+            LAST_OUTPUTS[name] = np.array(v.to_evaluations() if hasattr(v, "to_evaluations") else v, dtype=np.uint64)
+
+
+def dump_outputs(path):
+    """write LAST_OUTPUTS to path/<name>.npy: u64 words as exact float64 limb pairs, large outputs as a fixed seeded sample"""
+    import numpy as np
+    if not LAST_OUTPUTS:
+        raise SystemExit("--dump-outputs: this workload kept no outputs of its timed steps")
+    files = {}
+    for name, words in sorted(LAST_OUTPUTS.items()):
+        if words.size > DUMP_SAMPLE_WORDS:
+            idx = np.sort(np.random.default_rng(0x5EED).choice(words.size, DUMP_SAMPLE_WORDS, replace=False))
+            words = words.reshape(-1)[idx]
+            files[name + "_index"] = idx.astype(np.float64)
+        files[name] = np.stack([words & np.uint64(0xFFFFFFFF), words >> np.uint64(32)], axis=-1).astype(np.float64)
+    total = sum(a.nbytes for a in files.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes of outputs, more than the %d allowed" % (total, DUMP_MAX_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in files.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def kernel_name(rec):
@@ -570,7 +608,8 @@ def time_plane(args, pkg, torch, dist, rank, world, local_rank, plane, n):
         raise SystemExit("PARITY FAILURE at n=%d (%s): %s" % (n, label, problem))
     return {"ok": True, "plane": plane, "label": label, "ctx": ctx, "tables": (a, b, g), "elapsed": elapsed, "step_ms": step_ms,
             "n_launch": n_launch, "kernel_ms": kernel_ms, "log": log, "steps_with_events": steps_with_events,
-            "timed_every": timed_every, "comm_nranks": comm_nranks, "transcript": (c1, evals.tobytes()), "ramp": ramp, "first_proof": first_proof}
+            "timed_every": timed_every, "comm_nranks": comm_nranks, "transcript": (c1, evals.tobytes()), "ramp": ramp, "first_proof": first_proof,
+            "outputs": (c1, evals, ch)}
 
 
 def run_prover(args, pkg, torch, dist, rank, world, local_rank):
@@ -613,6 +652,8 @@ def run_prover(args, pkg, torch, dist, rank, world, local_rank):
                          "to run over the host (gloo) transport on purpose" % "; ".join("%s: %s" % kv for kv in failed.items()))
     best = runs[0]
     ctx = best["ctx"]
+    if rank == 0:       # the headline plane's last timed proof (rank 0 works on every plane)
+        keep_outputs(args, c_1=best["outputs"][0], round_evals=best["outputs"][1], challenges=best["outputs"][2])
     a, b, g = best.pop("tables") or (None, None, None)     # (None on the ranks that only waited for an "inproc" plane)
     elapsed, step_ms, log = best["elapsed"], best["step_ms"], best["log"]
     n_launch, kernel_ms, steps_with_events, timed_every = best["n_launch"], best["kernel_ms"], best["steps_with_events"], best["timed_every"]
@@ -942,6 +983,7 @@ def run_mle(args, pkg, torch, dist, rank, world, local_rank):
     ctx.set_option("time_kernels", 0)
     n_launch, kernel_ms = ctx.kernel_time(reset=True)
     log = ctx.launch_log(reset=True)
+    keep_outputs(args, evaluate_le=outs[0], evaluate_be=outs[1], **{"fix_variables_k%d" % k: folded for k, folded in zip(ks, outs[2:])})
     if os.environ.get("SC_BENCH_DEBUG"):
         sys.stderr.write("step_ms: %s\n" % " ".join("%.3f" % x for x in step_ms))
 
@@ -1162,6 +1204,7 @@ def run_gkr(args, pkg, torch, dist, rank, world, local_rank):
 
     elapsed, step_ms, n_launch, kernel_ms, log, last = timed_steps(args, torch, ctx, lambda: gp.prove_w(ctx, w, seed))
     c1, evals, ch = last
+    keep_outputs(args, c_1=c1, round_evals=evals, challenges=ch)
 
     # ---- parity gates (outside the timed region) -----------------------------------------------
     wi = pkg.DenseMultilinearExtension.from_evaluations_vec(ctx, k, np.array(evaluation[0], dtype=np.uint64))
@@ -1259,6 +1302,7 @@ def run_gnew(args, pkg, torch, dist, rank, world, local_rank):
         return g
 
     elapsed, step_ms, n_launch, kernel_ms, log, g = timed_steps(args, torch, ctx, step)
+    keep_outputs(args, f_a=g.f_a, f_b=g.f_b)
 
     # ---- parity (outside the timed region) -----------------------------------------------------
     side = 1 << n
@@ -1328,6 +1372,7 @@ def run_triangle(args, pkg, torch, dist, rank, world, local_rank):
     g = table(m, k)
     elapsed, step_ms, n_launch, kernel_ms, log, last = timed_steps(args, torch, ctx, lambda: tc_mod.prove(ctx, g, seed))
     c1, evals, ch = last
+    keep_outputs(args, c_1=c1, round_evals=evals, challenges=ch)
 
     a = m.astype(np.int64)
     tri = int(np.trace(a @ a @ a)) // 6
@@ -1418,7 +1463,11 @@ def main():
     ap.add_argument("--field", default=os.environ.get("SC_BENCH_FIELD", "goldilocks"),
                     help="goldilocks (BASELINE's 64-bit prime field, the headline) | generic (p = 2^64-59 through the kernels of "
                          "every other modulus: the reference's Fp64<MontBackend<T,1>>) | an odd prime below 2^64")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (see the module docstring)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.field == "goldilocks":
         FIELD["p"] = 2**64 - 2**32 + 1
     else:
@@ -1456,6 +1505,8 @@ def main():
     run = {"prover": run_prover, "mle": run_mle, "gkr": run_gkr, "gnew": run_gnew, "triangle": run_triangle}[args.workload]
     result = run(args, pkg, torch, dist, rank, world, local_rank)
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs)
         print(json.dumps(result), flush=True)
     abandoned = bool(ABANDONED)
     if dist is not None:          # ... on ANY rank: then nobody waits in a final barrier for a rank that has to leave

@@ -1,6 +1,6 @@
 """One rank of the multi-process transport tests (launched by torch.distributed.run; every rank on GPU 0 - or, with
 SC_WORKER_DISTINCT_DEVICES=1 on a box that has them, rank r on GPU r: tests/test_gpu_multi_device.py).
-SC_PEER_WORKER_MODE = parity | faults | widened | rccl_death | headline.  Not collected by pytest.
+SC_PEER_WORKER_MODE = parity | faults | widened | rccl_death | headline | w_sharded.  Not collected by pytest.
 SC_WORKER_TRANSPORT = peer (default: the in-kernel exchange over HIP IPC) | rccl (Transport::kRccl: ncclAllReduce behind every
 sharded pass, ncclAllGather at the tail - on a one-GPU box through tests/rccl_double, selected by SC_RCCL_LIBRARY, because
 RCCL itself refuses two ranks on one device).
@@ -194,6 +194,21 @@ def widened(pkg, dist, pyref, Oracle, rank, world):
     dist.barrier()
     ctx.close()
     print("WIDENED-OK rank %d" % rank, flush=True)
+
+
+def w_sharded(pkg, dist, pyref, Oracle, rank, world):
+    """tests/test_gpu_gkr.py test_w_prover_sharded with one PROCESS per rank: the dense W prover on this rank's rows of add_i /
+    mul_i beside the replicated sparse prover, every round bit-exact vs the oracle"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_gpu_gkr import check_w_shard_rounds, w_shard_rounds, w_sharded_cases
+    ctx = pkg.Context(pkg.Field(pyref.GOLDILOCKS), device=DEVICE)
+    attach(pkg, ctx, rank, world)
+    for case in w_sharded_cases(pkg, Oracle(pyref.GOLDILOCKS)):
+        dist.barrier()
+        check_w_shard_rounds(w_shard_rounds(pkg, ctx, case, rank, world), case)
+    dist.barrier()
+    ctx.close()
+    print("W-SHARDED-OK rank %d" % rank, flush=True)
 
 
 def faults(pkg, dist, pyref, Oracle, rank, world):
@@ -415,7 +430,8 @@ def main():
     dist.init_process_group(backend="gloo", rank=rank, world_size=world)
     pkg = ge.load_package()
     mode = os.environ.get("SC_PEER_WORKER_MODE", "parity")
-    {"parity": parity, "faults": faults, "widened": widened, "rccl_death": rccl_death, "headline": headline}[mode](pkg, dist, pyref, Oracle, rank, world)
+    {"parity": parity, "faults": faults, "widened": widened, "rccl_death": rccl_death, "headline": headline,
+     "w_sharded": w_sharded}[mode](pkg, dist, pyref, Oracle, rank, world)
     dist.barrier()
     dist.destroy_process_group()
 

@@ -124,27 +124,47 @@ def test_structs_that_cross_the_abi_have_the_same_fields_everywhere():
         assert values <= set(table) | {1}, (prefix, values - set(table))
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/sum-check-protocol"), reason="the reference tree is only present in the build container")
-def test_round_engine_patch_applies_to_the_reference(tmp_path):
-    """rust/patches/sum-check-protocol-round-engine.patch is the ONLY edit the reference needs: it must apply
-    cleanly to sum-check-protocol/src/lib.rs and leave every other line untouched"""
-    import shutil
+def _patch_preimage(patch_text):
+    """the lines of sum-check-protocol/src/lib.rs the patch's hunks quote (context and removed lines), each at the line number its
+    hunk header gives, blank filler between: enough of the file for `patch` to apply every hunk with neither offset nor fuzz"""
+    lines = []
+    for m in re.finditer(r"^@@ -(\d+),(\d+) \+\d+,\d+ @@[^\n]*\n((?:[ +\-][^\n]*\n|\n)*)", patch_text, flags=re.M):
+        start, count = int(m.group(1)), int(m.group(2))
+        body = [l[1:] if l else "" for l in m.group(3).split("\n")[:-1] if not l.startswith("+")]
+        assert len(body) == count, (start, count, len(body))     # the hunk header agrees with its body
+        assert len(lines) < start, start                          # hunks in order, none overlapping
+        lines += [""] * (start - 1 - len(lines)) + body
+    return lines
+
+
+def _apply_patch(tmp_path, old_lines):
+    import difflib
     dst = tmp_path / "sum-check-protocol" / "src"
     dst.mkdir(parents=True)
-    shutil.copy("/root/reference/sum-check-protocol/src/lib.rs", dst / "lib.rs")
+    (dst / "lib.rs").write_text("\n".join(old_lines) + "\n")
     patch = os.path.join(ROOT, "rust", "patches", "sum-check-protocol-round-engine.patch")
-    out = subprocess.run(["patch", "-p1", "-i", patch], cwd=tmp_path, capture_output=True, text=True)
-    assert out.returncode == 0, out.stdout + out.stderr
+    out = subprocess.run(["patch", "-p1", "-F0", "-i", patch], cwd=tmp_path, capture_output=True, text=True)
+    assert out.returncode == 0 and "offset" not in out.stdout and "fuzz" not in out.stdout, out.stdout + out.stderr
     new = (dst / "lib.rs").read_text().splitlines()
-    old = open("/root/reference/sum-check-protocol/src/lib.rs").read().splitlines()
-    import difflib
-    removed = [l for l in difflib.unified_diff(old, new, lineterm="", n=0) if l.startswith("-") and not l.startswith("---")]
+    removed = [l for l in difflib.unified_diff(old_lines, new, lineterm="", n=0) if l.startswith("-") and not l.startswith("---")]
     # the only lines that go away: the struct's closing brace moves, and Prover::new's one-line c_1
     assert len(removed) <= 4, removed
     text = "\n".join(new)
     for needle in ("pub trait RoundEngine<F: Field>", "fn hypercube_sum(&self) -> F", "fn native_engine(&self) -> Option<Box<dyn RoundEngine<F>>>",
                    "engine: Option<Box<dyn RoundEngine<F>>>"):
         assert needle in text
+
+
+def test_round_engine_patch_applies_to_the_reference(tmp_path):
+    """rust/patches/sum-check-protocol-round-engine.patch is the ONLY edit the reference needs: it must apply
+    cleanly to sum-check-protocol/src/lib.rs and leave every other line untouched.  Checked against the reference's lines as
+    the patch quotes them, at the places its hunks name; and against the reference tree itself where SC_REFERENCE_DIR names one"""
+    patch = os.path.join(ROOT, "rust", "patches", "sum-check-protocol-round-engine.patch")
+    _apply_patch(tmp_path / "quoted", _patch_preimage(open(patch).read()))
+    src = os.environ.get("SC_REFERENCE_DIR")
+    lib_rs = os.path.join(src, "sum-check-protocol", "src", "lib.rs") if src else None
+    if lib_rs and os.path.isfile(lib_rs):
+        _apply_patch(tmp_path / "tree", open(lib_rs).read().splitlines())
 
 
 def test_rccl_library_selection_and_the_test_double():

@@ -1,7 +1,7 @@
 """Launches with several processes on ONE GPU: the driver's `torch.distributed.run` line for N > 1 ranks and the peer
 transport between processes (HIP IPC), i.e. everything of a multi-GPU run but xGMI.
 
-This file sorts first on purpose.  Eight ranks that wait for each other inside their kernels need the GPU to run all
+This file sorts first on purpose.  Four ranks that wait for each other inside their kernels need the GPU to run all
 of them side by side; a pytest process that already holds a few dozen contexts (streams = hardware queues) of earlier
 tests oversubscribes the queues, the scheduler then time-slices whole processes, and an exchange that takes 4 s took
 100 s and more (measured: the same tests at the end of the suite).  Here the parent has not created a context yet."""
@@ -105,20 +105,20 @@ def test_bench_plain_invocation_starts_its_own_ranks():
 
 
 @pytest.mark.gpu
-def test_bench_eight_ranks_n28_on_one_device():
-    """BASELINE config 4 at its stated shape - n = 28 over 8 ranks of 2^25-entry shards - through the driver's launch
-    line and the default data plane (in-kernel exchange through HIP-IPC-mapped inboxes), the eight processes sharing
-    GPU 0 (what a one-GPU box can run: everything but xGMI).  The run gates on the verifier identities of the n = 28
+def test_bench_four_ranks_n28_on_one_device():
+    """BASELINE config 4's size - n = 28, here over 4 ranks of 2^26-entry shards (the one-device tests keep to at most four rank
+    processes on the GPU) - through the driver's launch line and the default data plane (in-kernel exchange through
+    HIP-IPC-mapped inboxes), the four processes sharing GPU 0 (what a one-GPU box can run: everything but xGMI).  The run gates on the verifier identities of the n = 28
     transcript.  One attempt, with the library's default bound on the in-kernel waits."""
     port = 29750 + (os.getpid() % 90)
-    d = _one_line(_bench(["--gpus", "8", "--steps", "6", "--warmup", "2", "--cpu-num-vars", "0"], {"SC_BENCH_TRANSPORT": "peer"},
-                         nproc=8, port=port, timeout=900))
-    assert d["n_gpus"] == 8 and d["scaling"] == "strong" and d["value"] > 0
+    d = _one_line(_bench(["--gpus", "4", "--steps", "6", "--warmup", "2", "--cpu-num-vars", "0"], {"SC_BENCH_TRANSPORT": "peer"},
+                         nproc=4, port=port, timeout=900))
+    assert d["n_gpus"] == 4 and d["scaling"] == "strong" and d["value"] > 0
     c = d["config"]
     assert c["num_vars"] == 28 and c["transport"] == "peer" and "verifier identities at n=28 ok" in c["parity_gate"]
-    assert c["transports"]["peer"]["comm_nranks"] == 8
+    assert c["transports"]["peer"]["comm_nranks"] == 4
     sched = c["schedule"]
-    assert sched[0] == ["gram_pass", 0, 4, 25] and sched[-1][0] == "grid_pass"  # 2^25-entry shards: the matrix-core first pass, five-round passes to the end
+    assert sched[0] == ["gram_pass", 0, 4, 26] and sched[-1][0] == "grid_pass"  # 2^26-entry shards: the matrix-core first pass, five-round passes to the end
     assert sum(s[2] for s in sched if s[0] != "gram_finish") == 28      # (gram_finish: the second launch of the first pass)
 
 
@@ -149,9 +149,9 @@ def _workers(nproc, mode, port, timeout=600, transport="peer", extra_env=None):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("nproc", [2, 8])
+@pytest.mark.parametrize("nproc", [2, 4])
 def test_peer_transport_processes_one_device(nproc):
-    """2 / 8 PROCESSES on GPU 0 exchanging HIP IPC handles (the mapping a multi-GPU node uses, minus xGMI): sharded
+    """2 / 4 PROCESSES on GPU 0 exchanging HIP IPC handles (the mapping a multi-GPU node uses, minus xGMI): sharded
     proofs, sharded evaluate and the degenerate paths, bit-exact against the oracle on every rank.  One attempt, with
     the library's default bound on the in-kernel waits."""
     out = _workers(nproc, "parity", 29950 + (os.getpid() % 40) + nproc)
@@ -187,10 +187,10 @@ def test_config5_pieces_over_peer_processes(nproc):
 # matrix-core pass, gather_table at the tail, ncclCommCount - which no one-GPU box could reach before; what does not run is RCCL.
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("nproc", [2, 4, 8])
+@pytest.mark.parametrize("nproc", [2, 4])
 def test_rccl_plane_processes_one_device(nproc):
     """sharded proofs (n = 1 .. 22, both sharded schedules, the gather at the tail), sharded evaluate and the degenerate paths over
-    Transport::kRccl with 2 / 4 / 8 ranks: bit-exact against the oracle on every rank, comm_nranks == world"""
+    Transport::kRccl with 2 / 4 ranks: bit-exact against the oracle on every rank, comm_nranks == world"""
     out = _workers(nproc, "parity", 30250 + (os.getpid() % 40) + nproc, transport="rccl")
     assert out.returncode == 0, (_quiet(out.stdout, 1500), _quiet(out.stderr))
     assert out.stdout.count("RCCL-OK") == nproc, out.stdout[-3000:]
@@ -206,7 +206,7 @@ def test_config5_pieces_over_rccl_processes(nproc):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("nproc", [2, 8])
+@pytest.mark.parametrize("nproc", [2, 4])
 def test_rccl_plane_a_rank_that_dies(nproc):
     """the last rank leaves between two proofs: every survivor's next proof fails with SC_ERR_RCCL inside the bound, none hangs"""
     out = _workers(nproc, "rccl_death", 30450 + (os.getpid() % 40) + nproc, timeout=300, transport="rccl",
@@ -215,7 +215,7 @@ def test_rccl_plane_a_rank_that_dies(nproc):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("transport,nproc", [("peer", 2), ("peer", 8), ("rccl", 4)])
+@pytest.mark.parametrize("transport,nproc", [("peer", 2), ("peer", 4), ("rccl", 4)])
 def test_headline_worker_on_one_device(transport, nproc):
     """the worker mode tests/test_gpu_multi_device.py runs at n = 20 and n = 28 on a real node (rank 0's oracle transcript handed to
     every rank, every rank's c_1 and round triples compared, launches == plan, cold and warm proof) - here at n = 16 and n = 22 with
@@ -238,19 +238,19 @@ def test_rccl_plane_a_collective_that_never_completes(nproc):
 
 
 @pytest.mark.gpu
-def test_bench_eight_ranks_all_three_planes():
-    """`bench.py --gpus 8` through the driver's launch line with the RCCL double in place: ONE line with all three data planes
-    timed - peer, rccl (comm_nranks 8 from the transport itself), inproc - and the same transcript on each"""
+def test_bench_four_ranks_all_three_planes():
+    """`bench.py --gpus 4` through the driver's launch line with the RCCL double in place: ONE line with all three data planes
+    timed - peer, rccl (comm_nranks 4 from the transport itself), inproc - and the same transcript on each"""
     port = 29760 + (os.getpid() % 90)
-    d = _one_line(_bench(["--gpus", "8", "--num-vars", "24", "--steps", "4", "--warmup", "1", "--cpu-num-vars", "24"],
-                         {"SC_RCCL_LIBRARY": RCCL_DOUBLE}, nproc=8, port=port, timeout=900))
-    # the five keys of a measured line (SURVEY 8d), at N = 8
+    d = _one_line(_bench(["--gpus", "4", "--num-vars", "24", "--steps", "4", "--warmup", "1", "--cpu-num-vars", "24"],
+                         {"SC_RCCL_LIBRARY": RCCL_DOUBLE}, nproc=4, port=port, timeout=900))
+    # the five keys of a measured line (SURVEY 8d), at N = 4
     assert d["value"] > 0 and d["config"]["workload"] and d["roofline"]["frac"] > 0 and d["roofline"]["per_gpu"] is True
     assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["cores"] == 1 and d["cpu_baseline"]["value"] > 0
-    assert "8-rank transcript is bit-exact vs the CPU oracle at n=24" in d["config"]["parity_gate"]
+    assert "4-rank transcript is bit-exact vs the CPU oracle at n=24" in d["config"]["parity_gate"]
     tr = d["config"]["transports"]
     assert set(tr) == {"peer", "rccl", "inproc"}
     for plane in ("peer", "rccl", "inproc"):
-        assert tr[plane]["ms_per_step"] and tr[plane]["ms_per_step"] > 0 and tr[plane]["comm_nranks"] == 8, (plane, tr[plane])
+        assert tr[plane]["ms_per_step"] and tr[plane]["ms_per_step"] > 0 and tr[plane]["comm_nranks"] == 4, (plane, tr[plane])
     assert "same transcript" in d["config"]["parity_gate"]
     assert "double" in str(tr["rccl"].get("library", "")), tr["rccl"]      # the line says what stood in for librccl

@@ -243,21 +243,10 @@ def test_wiring_collisions_and_errors():
     assert ei.value.code == 5
 
 
-@pytest.mark.parametrize("world", [2, 4])
-@pytest.mark.parametrize("transport", ["host", "peer"])
-def test_w_prover_sharded(world, transport):
-    """the dense W prover on a sharded context (BASELINE config 5 names gkr on 8 GPUs): every rank holds its rows of c
-    of add_i / mul_i (top index bits = rank) and the whole W tables; P and L are summed across ranks, add(r_b,.) /
-    mul(r_b,.) gathered; round polynomials bit-exact vs the oracle on every rank.  The sparse prover is replicated."""
-    import threading
-    from test_gpu_sharded import Loopback
-    if transport == "peer" and world > 2:
-        pytest.skip("threads of one process: see test_virtual_ranks_peer_transport")
-    pkg = load_package()
+def w_sharded_cases(pkg, o):
+    """the W layers of test_w_prover_sharded (fixed seed): (k_next, circuit, evaluation, r_i, oadd, omul, ow, ch, oracle transcript)"""
     p = GOLD
-    o = oracle(p)
     F0 = pkg.Field(p)
-    gp = pkg.gkr_protocol
     rng = random.Random(77)
     for ks in ([3, 3], [5, 4], [6, 7], [4, 9]):
         layers = random_circuit(rng, ks)
@@ -271,12 +260,62 @@ def test_w_prover_sharded(world, transport):
         ch = [F0.from_int(rng.randrange(p)) for _ in range(2 * k_next)]
         ref = o.w_prove(oadd, omul, ow, ow, ch)
         assert ref["status"] == 0
+        yield k_next, circuit, evaluation, r_i, oadd, omul, ow, ch, ref
+
+
+def w_shard_rounds(pkg, ctx, case, rank, world):
+    """the dense W prover on this rank's rows of add_i / mul_i beside the replicated sparse prover:
+    [(c_1, c_1), (round j dense, round j sparse) ...]"""
+    gp = pkg.gkr_protocol
+    k_next, circuit, evaluation, r_i, oadd, omul, ow, ch, _ = case
+    n_loc = oadd.size // world
+    DM = pkg.DenseMultilinearExtension
+    add_t = DM.from_evaluations_vec(ctx, 2 * k_next - (world.bit_length() - 1), oadd[rank * n_loc:(rank + 1) * n_loc])
+    mul_t = DM.from_evaluations_vec(ctx, 2 * k_next - (world.bit_length() - 1), omul[rank * n_loc:(rank + 1) * n_loc])
+    w_t = DM.from_evaluations_vec(ctx, k_next, ow)
+    eng = gp.W(add_t, mul_t, w_t, w_t).native_prover()
+    seng = gp.SparseLayerProver(ctx, circuit, evaluation, 0, r_i)
+    got = [(eng.c1(), seng.c1())]
+    for j in range(2 * k_next):
+        rp = ch[j - 1] if j else ctx.field.one
+        got.append((eng.round_evals(rp, j), seng.round_evals(rp, j)))
+    return got
+
+
+def check_w_shard_rounds(got, case):
+    k_next, ref = case[0], case[-1]
+    assert got[0] == (ref["c_1"], ref["c_1"]), k_next
+    for j in range(2 * k_next):
+        e = [int(x) for x in ref["evals"][j]]
+        assert got[1 + j] == (e, e), (k_next, j)
+
+
+@pytest.mark.parametrize("world", [2, 4])
+@pytest.mark.parametrize("transport", ["host", "peer"])
+def test_w_prover_sharded(world, transport):
+    """the dense W prover on a sharded context (BASELINE config 5 names gkr on 8 GPUs): every rank holds its rows of c
+    of add_i / mul_i (top index bits = rank) and the whole W tables; P and L are summed across ranks, add(r_b,.) /
+    mul(r_b,.) gathered; round polynomials bit-exact vs the oracle on every rank.  The sparse prover is replicated.
+    The ranks are threads of this process, except peer at four ranks: there they are processes (tests/peer_worker.py
+    w_sharded), as test_virtual_ranks_peer_transport explains."""
+    import threading
+    from test_gpu_sharded import Loopback
+    if transport == "peer" and world > 2:
+        import os
+        from test_gpu_00_multiprocess import _quiet, _workers
+        out = _workers(world, "w_sharded", 30750 + (os.getpid() % 40) + world)
+        assert out.returncode == 0, (_quiet(out.stdout, 1500), _quiet(out.stderr))
+        assert out.stdout.count("W-SHARDED-OK") == world, out.stdout[-3000:]
+        return
+    pkg = load_package()
+    o = oracle(GOLD)
+    for case in w_sharded_cases(pkg, o):
         lb = Loopback(world)
         ctxs, errors, results = [None] * world, [], [None] * world
 
         def body(rank):
             try:
-                ctx = pkg.Context(pkg.Field(p))
+                ctx = pkg.Context(pkg.Field(GOLD))
                 if transport == "peer":
                     ctx.set_option("peer_spin_ms", 20000)
                     ctx.comm_peer_export(rank, world)
@@ -287,21 +326,9 @@ def test_w_prover_sharded(world, transport):
                 else:
                     ar, ag = lb.collectives(rank)
                     ctx.comm_init_host(rank, world, ar, ag)
-                n_loc = oadd.size // world
-                DM = pkg.DenseMultilinearExtension
-                add_t = DM.from_evaluations_vec(ctx, 2 * k_next - (world.bit_length() - 1), oadd[rank * n_loc:(rank + 1) * n_loc])
-                mul_t = DM.from_evaluations_vec(ctx, 2 * k_next - (world.bit_length() - 1), omul[rank * n_loc:(rank + 1) * n_loc])
-                w_t = DM.from_evaluations_vec(ctx, k_next, ow)
-                eng = gp.W(add_t, mul_t, w_t, w_t).native_prover()
-                seng = gp.SparseLayerProver(ctx, circuit, evaluation, 0, r_i)
-                got = [(eng.c1(), seng.c1())]
-                for j in range(2 * k_next):
-                    rp = ch[j - 1] if j else F0.one
-                    got.append((eng.round_evals(rp, j), seng.round_evals(rp, j)))
-                results[rank] = got
+                results[rank] = w_shard_rounds(pkg, ctx, case, rank, world)
                 if transport == "peer":
                     lb.barrier.wait()
-                del eng, seng, add_t, mul_t, w_t
                 ctx.close()
             except Exception as e:  # pragma: no cover
                 import traceback
@@ -316,10 +343,7 @@ def test_w_prover_sharded(world, transport):
             t.join(timeout=300)
         assert not errors, errors
         for got in results:
-            assert got[0] == (ref["c_1"], ref["c_1"]), ks
-            for j in range(2 * k_next):
-                e = [int(x) for x in ref["evals"][j]]
-                assert got[1 + j] == (e, e), (ks, j)
+            check_w_shard_rounds(got, case)
 
 
 @pytest.mark.parametrize("p", [GOLD, 389], ids=pid)

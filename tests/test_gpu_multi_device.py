@@ -6,8 +6,9 @@ shards / N processes of device 0, RCCL at world 1 or replaced by tests/rccl_doub
   * the REAL librccl      SC_RCCL_LIBRARY unset: ncclCommInitRank over N devices, ncclAllReduce / ncclAllGather over xGMI
   * the peer plane        HIP IPC (dmabuf) between processes that own different devices: in-kernel exchange over xGMI
 
-and they SKIP, with the reason below, wherever torch.cuda.device_count() < 2 - on this pool, always.  On a node that has the
-GPUs they are what runs before the driver's SCALE bench does, so that bench is not the first execution of any of this:
+On a box with ONE GPU they run as the rehearsal described below (every "device" = GPU 0, the librccl stand-in); with no GPU
+they skip like every -m gpu test.  On a node that has the GPUs they are what runs before the driver's SCALE bench does, so that
+bench is not the first execution of any of this:
 
   (a) process per GPU: sharded proofs n = 1 .. 22 (every sharded schedule), then n = 20 and n = 28 (BASELINE's shape) against
       the oracle's transcript, over RCCL and over the peer plane, comm_nranks == N as the transport itself reports it;
@@ -43,19 +44,21 @@ def _ndev():
         return 0
 
 
-# REHEARSAL (SC_MULTI_DEVICE_REHEARSAL=1, what this pool can do): the same test bodies with every "device" = GPU 0 and the librccl
-# stand-in of tests/rccl_double - it proves nothing about distinct devices, RCCL or xGMI (the one-device suite already covers that
-# ground); it executes THIS FILE's code, so that a typo here is not what the first run on a real node finds.  Run once per round:
-#   SC_MULTI_DEVICE_REHEARSAL=1 python -m pytest tests/test_gpu_multi_device.py -m gpu
-REHEARSAL = os.environ.get("SC_MULTI_DEVICE_REHEARSAL") == "1"
+# REHEARSAL (on a one-GPU box, or forced with SC_MULTI_DEVICE_REHEARSAL=1): the same test bodies with every "device" = GPU 0 and
+# the librccl stand-in of tests/rccl_double - it proves nothing about distinct devices, RCCL or xGMI (the one-device suite already
+# covers that ground); it executes THIS FILE's code, so that a typo here is not what the first run on a real node finds.
+VISIBLE = _ndev()
+REHEARSAL = os.environ.get("SC_MULTI_DEVICE_REHEARSAL") == "1" or VISIBLE == 1
 RCCL_DOUBLE = os.path.join(ROOT, "tests", "rccl_double", "librccl_double.so")
-NDEV = 8 if REHEARSAL else _ndev()
+NDEV = 8 if REHEARSAL else VISIBLE
 NMAX = 1 << (min(NDEV, 8).bit_length() - 1) if NDEV >= 1 else 1          # the largest power of two of devices, up to 8
 needs_two = pytest.mark.skipif(
     NDEV < 2, reason="needs >= 2 GPUs in one box (this one shows %d): distinct devices, the real librccl with N > 1 ranks and "
                      "xGMI cannot run here; the one-device forms of these tests are test_gpu_00_multiprocess.py, test_gpu_multi.py, "
                      "test_gpu_headline.py" % NDEV)
-WORLDS = sorted({2, NMAX} - {1})
+NPROC = min(NMAX, 4)          # rank processes of one launch: at most four, like the one-device tests
+WORLDS = sorted({2, NPROC} - {1})             # world sizes of the process-per-GPU launches
+HANDLE_SIZES = sorted({2, NMAX} - {1})        # devices behind one handle (one process)
 
 
 def _env(transport):
@@ -96,12 +99,12 @@ def test_sharded_proofs_one_process_per_gpu(transport, nproc):
 @needs_two
 @pytest.mark.parametrize("transport", ["rccl", "peer"])
 def test_n20_and_n28_over_all_devices_vs_oracle(transport):
-    """BASELINE configs[3]: the n = 28 hypercube over the box's GPUs (8 where it has them), one RCCL all-reduce per sharded
+    """BASELINE configs[3]: the n = 28 hypercube over up to 4 of the box's GPUs (one process each), one RCCL all-reduce per sharded
     pass - and the same over the in-kernel exchange - c_1 and all 28 round triples equal to the CPU oracle's on every rank"""
-    out = _workers(NMAX, "headline", transport, 31150 + (os.getpid() % 40) + (20 if transport == "peer" else 0), timeout=1800,
+    out = _workers(NPROC, "headline", transport, 31150 + (os.getpid() % 40) + (20 if transport == "peer" else 0), timeout=1800,
                    extra={"SC_WORKER_NUM_VARS": "20,28"})
     assert out.returncode == 0, _tail(out)
-    assert out.stdout.count("HEADLINE-OK") == NMAX, _tail(out)
+    assert out.stdout.count("HEADLINE-OK") == NPROC, _tail(out)
 
 
 @needs_two
@@ -109,17 +112,17 @@ def test_n20_and_n28_over_all_devices_vs_oracle(transport):
 def test_config5_pieces_one_process_per_gpu(transport):
     """BASELINE configs[4]'s pieces between devices: sharded G::new (the f_a vector all-reduce over xGMI), the sharded W prover
     with sharded wiring, the sharded triangle prover"""
-    out = _workers(min(NMAX, 4), "widened", transport, 31250 + (os.getpid() % 40) + (20 if transport == "peer" else 0))
+    out = _workers(NPROC, "widened", transport, 31250 + (os.getpid() % 40) + (20 if transport == "peer" else 0))
     assert out.returncode == 0, _tail(out)
-    assert out.stdout.count("WIDENED-OK") == min(NMAX, 4), _tail(out)
+    assert out.stdout.count("WIDENED-OK") == NPROC, _tail(out)
 
 
 @needs_two
 def test_peer_plane_fault_injection_between_devices():
     """late ranks, a rank out of step, interleaved provers, gathers longer than the arena - across devices"""
-    out = _workers(min(NMAX, 4), "faults", "peer", 31350 + (os.getpid() % 40))
+    out = _workers(NPROC, "faults", "peer", 31350 + (os.getpid() % 40))
     assert out.returncode == 0, _tail(out)
-    assert out.stdout.count("FAULTS-OK") == min(NMAX, 4), _tail(out)
+    assert out.stdout.count("FAULTS-OK") == NPROC, _tail(out)
 
 
 # ---- (c) a rank that dies under the real librccl -------------------------------------------------------------------------------
@@ -154,7 +157,7 @@ def test_handle_over_distinct_devices_vs_oracle(n):
     ch_ref = challenges(o, n)
     c1_ref, ev_ref = o.prover_run_mt(oa, ob, ch_ref)
     del oa, ob
-    for n_dev in WORLDS:
+    for n_dev in HANDLE_SIZES:
         ctx = _handle(pkg, GOLD, n_dev)
         a = pkg.DenseMultilinearExtension.generate(ctx, pyref.SEED_A, n)
         b = pkg.DenseMultilinearExtension.generate(ctx, pyref.SEED_B, n)
@@ -203,7 +206,7 @@ def test_handle_g_new_block_exchange_across_devices():
         fa, fb = o.g_new(n, A, B, pt)
         ch = challenges(o, n)
         ref = o.prove(fa, fb, ch)
-        for n_dev in WORLDS:
+        for n_dev in HANDLE_SIZES:
             ctx = _handle(pkg, GOLD, n_dev)
             G = pkg.matrix_multiplication.G.new(ctx, n, A, B, [int(x) for x in pt])
             assert np.array_equal(G.f_a.to_evaluations(), fa) and np.array_equal(G.f_b.to_evaluations(), fb), (n, n_dev)
@@ -230,8 +233,8 @@ def test_bench_line_on_real_devices():
     env = _env("peer")
     env.pop("SC_WORKER_DISTINCT_DEVICES")
     env.pop("SC_WORKER_TRANSPORT")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(NMAX), "--master-addr", "127.0.0.1",
-           "--master-port", str(31550 + (os.getpid() % 40)), os.path.join(ROOT, "bench.py"), "--gpus", str(NMAX), "--steps", "5", "--warmup", "2",
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(NPROC), "--master-addr", "127.0.0.1",
+           "--master-port", str(31550 + (os.getpid() % 40)), os.path.join(ROOT, "bench.py"), "--gpus", str(NPROC), "--steps", "5", "--warmup", "2",
            "--num-vars", "24", "--cpu-num-vars", "24"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=1200, cwd=ROOT, env=env)
     assert out.returncode == 0, _tail(out)
@@ -239,9 +242,9 @@ def test_bench_line_on_real_devices():
     assert len(lines) == 1, out.stdout[-2000:]
     d = json.loads(lines[0])
     tr = d["config"]["transports"]
-    assert d["n_gpus"] == NMAX and set(tr) == {"peer", "rccl", "inproc"}
+    assert d["n_gpus"] == NPROC and set(tr) == {"peer", "rccl", "inproc"}
     for plane in ("peer", "rccl", "inproc"):
-        assert tr[plane]["ms_per_step"] and tr[plane]["comm_nranks"] == NMAX, (plane, tr[plane])
+        assert tr[plane]["ms_per_step"] and tr[plane]["comm_nranks"] == NPROC, (plane, tr[plane])
     assert REHEARSAL or "double" not in str(tr["rccl"].get("library", ""))
     assert d["roofline"]["frac"] > 0 and d["cpu_baseline"]["value"] > 0 and d["cpu_baseline"]["cores"] == 1
-    assert "%d-rank transcript is bit-exact vs the CPU oracle at n=24" % NMAX in d["config"]["parity_gate"]
+    assert "%d-rank transcript is bit-exact vs the CPU oracle at n=24" % NPROC in d["config"]["parity_gate"]

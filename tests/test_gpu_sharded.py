@@ -234,7 +234,7 @@ def test_virtual_ranks_peer_transport(p, world):
     Two ranks only when the ranks are threads of ONE process: a workgroup that waits for a peer needs the
     peer's kernel to run beside it, and one process's streams share a handful of hardware queues (with four
     contexts a waiting kernel can sit in front of the kernel it waits for: measured, bounded by peer_spin_ms).
-    One process per rank - the deployment - has no such coupling; tests/test_gpu_00_multiprocess.py runs 2 and 8 processes."""
+    One process per rank - the deployment - has no such coupling; tests/test_gpu_00_multiprocess.py runs 2 and 4 processes."""
     pkg = load_package()
     o = oracle(p)
     g = world.bit_length() - 1
