@@ -216,6 +216,7 @@ int sc_ctx_kernel_time(sc_ctx* ctx, double out[2], int reset);
 #define SC_KIND_GRAM_PASS 11   /* gram_pass_kernel: the four-round first pass of a large proof on the int8 matrix cores (ks = 4) */
 #define SC_KIND_WFOLD_PASS 13  /* wfold_pass_kernel: a fold of kf = 4 / 5 variables of large tables that serves ks = 5 / 3..5 rounds (behind the matrix-core first pass; the pass behind that) */
 /* 12 was gram_finish_kernel (rounds 4: a second launch behind the gram pass; folded into gram_pass_kernel in round 5) */
+#define SC_KIND_CIRCUIT 14     /* circuit_layer_kernel: one layer of sc_circuit_evaluate; log_in = k[i] (gates), kf = k[i+1]; bytes = the streamed 20 B per gate */
 typedef struct sc_launch_record {
   int32_t kind;           /* SC_KIND_* */
   int32_t kf, ks;         /* variables folded / rounds served (meaning per kind above) */
@@ -460,6 +461,41 @@ int sc_gkr_prover_destroy(sc_gkr_prover* pr);
  * split by its top index bits like every table there.  The reference returns a SparsePolynomial: drop zero terms. */
 int sc_table_restrict_to_line(sc_ctx* ctx, const sc_table* t, const uint64_t* b, const uint64_t* c, size_t k,
                               uint64_t* out_coeffs);
+
+/* ---- gkr_protocol::circuit::Circuit on the device, and the whole GKR prover over it ----------------------------------
+ * A circuit lives on ONE context of one device and one rank: sharded contexts (world > 1) and multi-device handles get
+ * SC_ERR_UNSUPPORTED from every call below, before the circuit is looked at.  Limits are the sparse prover's:
+ * k[i] <= 30, 1 <= k[i+1] <= 26. */
+typedef struct sc_circuit sc_circuit;
+/* circuit.rs:72-124: `depth` layers, layers[0] = outputs.  Layer i has 2^k[i] gates reading layer i+1;
+ * k[depth] = number of input variables.  Gate arrays as for sc_gkr_wiring (type 0 = add, 1 = mul).
+ * Checked once here (SC_ERR_ARG naming the layer and the gate), then copied to the device; the host arrays may be freed
+ * on return.  The circuit must outlive every prover made from it (sc_gkr_prover_create_circuit). */
+int sc_circuit_create(sc_ctx* ctx, size_t depth, const size_t* k /* depth + 1 */, const int32_t* const* gate_type,
+                      const uint32_t* const* in0, const uint32_t* const* in1, sc_circuit** out);
+int sc_circuit_destroy(sc_ctx* ctx, sc_circuit* c);
+/* Circuit::evaluate (circuit.rs:99-124): values[i] (i < depth) = layer i's 2^k[i] values, new tables the caller frees;
+ * `input` has 2^k[depth] entries.  One circuit_layer_kernel launch per layer, from the input up, on the context's stream
+ * (no host sync between them). */
+int sc_circuit_evaluate(sc_ctx* ctx, const sc_circuit* c, const sc_table* input, sc_table** values);
+/* sc_gkr_prover_create_sparse for layer i (lib.rs:373-436), from the device-resident gate list: no host check, no copy,
+ * no sync.  w_next = layer i+1's values (2^k[i+1] entries), r_i has k[i] entries.  i >= depth: SC_ERR_ARG. */
+int sc_gkr_prover_create_circuit(sc_ctx* ctx, const sc_circuit* c, size_t i, const uint64_t* r_i,
+                                 const sc_table* w_next, sc_gkr_prover** out);
+/* The prover's side of the whole protocol (lib.rs:324-474, as the reference's protocol tests at :550-702 drive it) in
+ * one call: evaluate, read the outputs back, then per layer the circuit-backed sparse prover's 2k rounds, q =
+ * restrict_poly on the device table W_{i+1}, and r_{i+1} = b* + r (c* - b*) (`line`, :278-289).  Every output may be NULL:
+ *   outputs  2^k[0] words: the Begin message
+ *   c1       depth words: each layer's StartSumCheck claim
+ *   evals    3 * sum_i 2 k[i+1] words: every round's H(0), H(1), H(2), layer by layer
+ *   q        sum_i (k[i+1] + 1) words: each layer's restrict_poly coefficients, dense, lowest degree first
+ *   draws    k[0] + sum_i (2 k[i+1] + 1) words: every challenge, in the order drawn
+ * Draw order (the reference Verifier's): k[0] draws for r_0; then per layer 2k - 1 sumcheck draws, final_random_point,
+ * and the line draw.  draw(user, t, evals) gets the running draw index t; evals is the round's three sums for a draw that
+ * follows a round message, NULL for r_0's draws, final_random_point and the line draw.  draw == NULL: the synthetic
+ * challenger of sc_prove over t (to_mont(splitmix64(seed_r + t + 1) mod p)). */
+int sc_gkr_prove_circuit(sc_ctx* ctx, const sc_circuit* c, const sc_table* input, sc_draw_fn draw, void* user,
+                         uint64_t seed_r, uint64_t* outputs, uint64_t* c1, uint64_t* evals, uint64_t* q, uint64_t* draws);
 
 /* ---- triangle_counting::G -------------------------------------
  *   g(X,Y,Z) = f(X,Y) f(Y,Z) f(X,Z)   (triangle-counting/src/lib.rs:10-27)

@@ -87,6 +87,10 @@ pub struct sc_gkr_prover {
 pub struct sc_tri_prover {
     _private: [u8; 0],
 }
+#[repr(C)]
+pub struct sc_circuit {
+    _private: [u8; 0],
+}
 
 pub type sc_allreduce_fn = Option<unsafe extern "C" fn(user: *mut c_void, buf: *mut u64, count: usize) -> c_int>;
 pub type sc_allgather_fn =
@@ -330,6 +334,39 @@ extern "C" {
         c: *const u64,
         k: usize,
         out_coeffs: *mut u64,
+    ) -> c_int;
+    // ---- gkr_protocol::circuit::Circuit on the device, and the whole GKR prover over it -------------------
+    pub fn sc_circuit_create(
+        ctx: *mut sc_ctx,
+        depth: usize,
+        k: *const usize,
+        gate_type: *const *const i32,
+        in0: *const *const u32,
+        in1: *const *const u32,
+        out: *mut *mut sc_circuit,
+    ) -> c_int;
+    pub fn sc_circuit_destroy(ctx: *mut sc_ctx, c: *mut sc_circuit) -> c_int;
+    pub fn sc_circuit_evaluate(ctx: *mut sc_ctx, c: *const sc_circuit, input: *const sc_table, values: *mut *mut sc_table) -> c_int;
+    pub fn sc_gkr_prover_create_circuit(
+        ctx: *mut sc_ctx,
+        c: *const sc_circuit,
+        i: usize,
+        r_i: *const u64,
+        w_next: *const sc_table,
+        out: *mut *mut sc_gkr_prover,
+    ) -> c_int;
+    pub fn sc_gkr_prove_circuit(
+        ctx: *mut sc_ctx,
+        c: *const sc_circuit,
+        input: *const sc_table,
+        draw: sc_draw_fn,
+        user: *mut c_void,
+        seed_r: u64,
+        outputs: *mut u64,
+        c1: *mut u64,
+        evals: *mut u64,
+        q: *mut u64,
+        draws: *mut u64,
     ) -> c_int;
 
     // ---- triangle_counting::G ----------------------------------------------------------------

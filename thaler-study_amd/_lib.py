@@ -49,7 +49,7 @@ class ScLaunchRecord(ctypes.Structure):
                 ("bytes_read", u64), ("bytes_written", u64), ("ms", ctypes.c_double)]
 
 
-KIND_NAMES = {0: "pass", 2: "evaluate", 3: "fold", 4: "fix_low", 5: "fold_be", 6: "coldot", 7: "gkr", 8: "matsq", 10: "grid_pass", 11: "gram_pass", 13: "wfold_pass"}
+KIND_NAMES = {0: "pass", 2: "evaluate", 3: "fold", 4: "fix_low", 5: "fold_be", 6: "coldot", 7: "gkr", 8: "matsq", 10: "grid_pass", 11: "gram_pass", 13: "wfold_pass", 14: "circuit"}
 
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, voidp, u64p, size_t)
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, voidp, u64p, u64p, size_t)
@@ -122,6 +122,13 @@ SIGNATURES = {
     "sc_gkr_prover_round": (ctypes.c_int, [voidp, u64, size_t, u64p]),
     "sc_gkr_prover_destroy": (ctypes.c_int, [voidp]),
     "sc_table_restrict_to_line": (ctypes.c_int, [voidp, voidp, u64p, u64p, size_t, u64p]),
+    "sc_circuit_create": (ctypes.c_int, [voidp, size_t, ctypes.POINTER(size_t), ctypes.POINTER(ctypes.POINTER(ctypes.c_int32)),
+                                          ctypes.POINTER(ctypes.POINTER(ctypes.c_uint32)), ctypes.POINTER(ctypes.POINTER(ctypes.c_uint32)),
+                                          ctypes.POINTER(voidp)]),
+    "sc_circuit_destroy": (ctypes.c_int, [voidp, voidp]),
+    "sc_circuit_evaluate": (ctypes.c_int, [voidp, voidp, voidp, ctypes.POINTER(voidp)]),
+    "sc_gkr_prover_create_circuit": (ctypes.c_int, [voidp, voidp, size_t, u64p, voidp, ctypes.POINTER(voidp)]),
+    "sc_gkr_prove_circuit": (ctypes.c_int, [voidp, voidp, voidp, DRAW_FN, voidp, u64, u64p, u64p, u64p, u64p, u64p]),
     "sc_tri_to_evaluations": (ctypes.c_int, [voidp, voidp, voidp, voidp, size_t, ctypes.POINTER(voidp)]),
     "sc_tri_round_sums": (ctypes.c_int, [voidp, voidp, voidp, voidp, size_t, u64p]),
     "sc_tri_fix_variables": (ctypes.c_int, [voidp, voidp, voidp, voidp, size_t, u64p, size_t] + [ctypes.POINTER(voidp)] * 3),

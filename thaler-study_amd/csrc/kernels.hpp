@@ -253,5 +253,6 @@ __device__ __forceinline__ void transpose_to_pieces(ull2* __restrict__ lds, ull2
 #include "kernels/gram.hpp"
 #include "kernels/mle.hpp"
 #include "kernels/gkr.hpp"
+#include "kernels/circuit.hpp"
 #include "kernels/triangle.hpp"
 #include "kernels/peer.hpp"

@@ -463,6 +463,7 @@ static int multi_prod2_fold_and_sums(sc_ctx* m, const sc_table* a, const sc_tabl
 #include "engine/abi_tables.inc"
 #include "engine/abi_prover.inc"
 #include "engine/abi_gkr.inc"
+#include "engine/abi_circuit.inc"
 #include "engine/abi_triangle.inc"
 #include "engine/abi_restrict.inc"
 #include "engine/abi_multi.inc"

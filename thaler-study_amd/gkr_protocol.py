@@ -3,6 +3,8 @@
   circuit.rs:7-213      GateType, Gate, CircuitLayer, Circuit (evaluate, num_vars_at, add_i, mul_i)
   round_polynomial.rs   W = add_i(r_i,b,c)(W(b)+W(c)) + mul_i(r_i,b,c) W(b) W(c)  (:23-119)
   lib.rs:373-436        Prover::start_round's construction of W for layer i (`start_round_w`)
+  circuit.rs:99-124     Circuit::evaluate on the GPU (`DeviceCircuit`), and the prover's whole side of the protocol in
+                        one native call (`prove_circuit`) or, interactively, `Prover.new(..., device=True)`
 
 The GKR message state machines (gkr-protocol/src/lib.rs Prover/Verifier) are control plane and
 stay on the host side of the reference; they drive `sum_check_protocol.Prover` on a `W` exactly
@@ -172,7 +174,7 @@ def prove_w(ctx, w, seed_r, draw=None):
     return int(c1.value), ev[: 3 * n].reshape(n, 3).copy(), ch[:n].copy()
 
 
-def _gate_arrays(layer):
+def _gate_numpy(layer):
     """the gate list as three contiguous arrays (type 0 = add, 1 = mul; the two input labels), cached on the layer"""
     cached = getattr(layer, "_arrays", None)
     if cached is None:
@@ -180,7 +182,11 @@ def _gate_arrays(layer):
         i0 = np.fromiter((g.inputs[0] for g in layer.layer), dtype=np.uint32, count=len(layer.layer))
         i1 = np.fromiter((g.inputs[1] for g in layer.layer), dtype=np.uint32, count=len(layer.layer))
         cached = layer._arrays = (gt, i0, i1)
-    gt, i0, i1 = cached
+    return cached
+
+
+def _gate_arrays(layer):
+    gt, i0, i1 = _gate_numpy(layer)
     return (gt.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), i0.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
             i1.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
 
@@ -243,6 +249,147 @@ def restrict_poly(b, c, mle):
     out = np.zeros(k + 1, dtype=np.uint64)
     ctx.check(ctx.lib.sc_table_restrict_to_line(ctx.h, mle.h, _u64p(bb), _u64p(cc), k, _u64p(out)))
     return SparsePolynomial.from_dense(ctx.field, [int(v) for v in out])
+
+
+# ---- Circuit on the device (sc_circuit_*) and the whole prover in one call (sc_gkr_prove_circuit) ------------------
+
+def transcript_sizes(k):
+    """words of each output of sc_gkr_prove_circuit for a circuit of layer sizes k (depth + 1 entries, k[depth] = inputs)"""
+    depth = len(k) - 1
+    return {"outputs": 1 << k[0], "c1": depth, "evals": 3 * sum(2 * k[i + 1] for i in range(depth)),
+            "q": sum(k[i + 1] + 1 for i in range(depth)), "draws": k[0] + sum(2 * k[i + 1] + 1 for i in range(depth))}
+
+
+class DeviceCircuit:
+    """a Circuit resident on one GPU context (sc_circuit): the gate lists are checked and uploaded once; evaluate() and
+    the layer provers read them there.  Single-device, unsharded contexts only (SC_ERR_UNSUPPORTED elsewhere)."""
+
+    def __init__(self, ctx, circuit):
+        depth = len(circuit.layers)
+        k = [circuit.num_vars_at(i) for i in range(depth + 1)]
+        self._create(ctx, k, [_gate_numpy(layer) for layer in circuit.layers])
+
+    @classmethod
+    def from_arrays(cls, ctx, k, layers):
+        """k: depth + 1 layer sizes (log2); layers[i] = (types int32, in0 uint32, in1 uint32), each 2^k[i] long.  Checked
+        here before any native call; large circuits never become Python Gate objects."""
+        k = [int(x) for x in k]
+        if len(k) < 2 or len(layers) != len(k) - 1:
+            raise ValueError("from_arrays: %d layers need %d sizes k, got %d" % (len(layers), len(layers) + 1, len(k)))
+        if any(x < 0 for x in k):
+            raise ValueError("from_arrays: negative layer size in k = %r" % (k,))
+        arrays = []
+        for i, triple in enumerate(layers):
+            if len(triple) != 3:
+                raise ValueError("from_arrays: layer %d is not (types, in0, in1)" % i)
+            for name, a, dt in zip(("types", "in0", "in1"), triple, (np.int32, np.uint32, np.uint32)):
+                if not isinstance(a, np.ndarray) or a.dtype != dt or a.ndim != 1:
+                    raise TypeError("from_arrays: layer %d %s must be a 1-D numpy array of %s" % (i, name, np.dtype(dt).name))
+                if a.size != 1 << k[i]:
+                    raise ValueError("from_arrays: layer %d %s has %d entries, 2^k[%d] = %d" % (i, name, a.size, i, 1 << k[i]))
+            arrays.append(tuple(np.ascontiguousarray(a) for a in triple))
+        self = cls.__new__(cls)
+        self._create(ctx, k, arrays)
+        return self
+
+    def _create(self, ctx, k, arrays):
+        self.ctx, self.k, self.h = ctx, list(k), None
+        depth = len(arrays)
+        P32, PU32 = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint32)
+        gt = (P32 * depth)(*[a[0].ctypes.data_as(P32) for a in arrays])
+        i0 = (PU32 * depth)(*[a[1].ctypes.data_as(PU32) for a in arrays])
+        i1 = (PU32 * depth)(*[a[2].ctypes.data_as(PU32) for a in arrays])
+        ks = (ctypes.c_size_t * (depth + 1))(*self.k)
+        h = voidp()
+        ctx.check(ctx.lib.sc_circuit_create(ctx.h, depth, ks, gt, i0, i1, ctypes.byref(h)))
+        self.h = h
+
+    @property
+    def depth(self):
+        return len(self.k) - 1
+
+    def num_vars_at(self, layer):
+        return self.k[layer] if 0 <= layer <= self.depth else None
+
+    def _input(self, input_mle):
+        if isinstance(input_mle, DenseMultilinearExtension):
+            return input_mle
+        return DenseMultilinearExtension.from_evaluations_vec(self.ctx, self.k[-1], np.asarray(input_mle, dtype=np.uint64))
+
+    def evaluate(self, input_mle):
+        """Circuit::evaluate on the device: [W_0, ..., W_{depth-1}] as DenseMultilinearExtension (outputs first)"""
+        inp = self._input(input_mle)
+        hs = (voidp * self.depth)()
+        self.ctx.check(self.ctx.lib.sc_circuit_evaluate(self.ctx.h, self.h, inp.h, hs))
+        return [DenseMultilinearExtension(self.ctx, voidp(h)) for h in hs]
+
+    def close(self):
+        if self.h and self.ctx.h:
+            self.ctx.lib.sc_circuit_destroy(self.ctx.h, self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class CircuitLayerProver(_NativeWProver):
+    """SparseLayerProver over a DeviceCircuit's own gate list and a device table W_{i+1} (sc_gkr_prover_create_circuit):
+    nothing crosses the bus.  Holds the circuit, which must outlive the prover."""
+
+    def __init__(self, ctx, dcircuit, i, r_i, w_next):
+        self.ctx, self._circuit, self._w_next = ctx, dcircuit, w_next
+        r = _words(r_i)
+        h = voidp()
+        ctx.check(ctx.lib.sc_gkr_prover_create_circuit(ctx.h, dcircuit.h, i, _u64p(r), w_next.h, ctypes.byref(h)))
+        self.h = h
+        self._num_vars = 2 * dcircuit.k[i + 1]
+
+    def num_vars(self):
+        return self._num_vars
+
+
+def prove_circuit(ctx, dcircuit, input_mle, draw=None, seed_r=0):
+    """the prover's side of the whole GKR protocol in one native call (sc_gkr_prove_circuit).  draw(t, evals) -> challenge
+    (a Montgomery word) is called with the running draw index t and the round's [H(0), H(1), H(2)], or None for r_0's
+    draws, final_random_point and the line draw; draw=None: the synthetic challenger over t.  Returns Montgomery words:
+    {"circuit_outputs", "r_0", "layers": [{"c_1", "evals" (2k x 3), "challenges" (2k), "q" (k + 1), "r_line", "r_next"}]}"""
+    F, k = ctx.field, dcircuit.k
+    inp = dcircuit._input(input_mle)
+    sz = transcript_sizes(k)
+    bufs = {name: np.zeros(max(n, 1), dtype=np.uint64) for name, n in sz.items()}
+    failure = []
+    if draw is not None:
+        def _cb(_user, t, e):
+            try:
+                return int(draw(t, None if not e else [int(e[0]), int(e[1]), int(e[2])]))
+            except BaseException as ex:    # handed back after the native call (an unreduced word stops it)
+                failure.append(ex)
+                return F.p
+        cb = _lib.DRAW_FN(_cb)
+    else:
+        cb = ctypes.cast(None, _lib.DRAW_FN)
+    rc = ctx.lib.sc_gkr_prove_circuit(ctx.h, dcircuit.h, inp.h, cb, None, seed_r, *[_u64p(bufs[n]) for n in
+                                                                                   ("outputs", "c1", "evals", "q", "draws")])
+    if failure:
+        raise failure[0]
+    ctx.check(rc)
+    d = [int(x) for x in bufs["draws"][:sz["draws"]]]
+    out = {"circuit_outputs": [int(x) for x in bufs["outputs"][:sz["outputs"]]], "r_0": d[:k[0]], "layers": []}
+    t, e_at, q_at = k[0], 0, 0
+    for i in range(dcircuit.depth):
+        kn = k[i + 1]
+        ch = d[t:t + 2 * kn]
+        r_line = d[t + 2 * kn]
+        out["layers"].append({
+            "c_1": int(bufs["c1"][i]), "num_vars": 2 * kn,
+            "evals": bufs["evals"][3 * e_at:3 * (e_at + 2 * kn)].reshape(2 * kn, 3).tolist(),
+            "challenges": ch, "q": [int(x) for x in bufs["q"][q_at:q_at + kn + 1]], "r_line": r_line,
+            "r_next": [F.add(b, F.mul(r_line, F.sub(c, b))) for b, c in zip(ch[:kn], ch[kn:])]})
+        t, e_at, q_at = t + 2 * kn + 1, e_at + 2 * kn, q_at + kn + 1
+    return out
 
 
 # ---- the GKR message state machines (gkr-protocol/src/lib.rs:38-218, :324-474) -----------------------
@@ -391,26 +538,43 @@ class Verifier:
 
 class Prover:
     """:324-474.  `sparse=True` builds each layer's sumcheck straight from the gate list
-    (sc_gkr_prover_create_sparse) instead of the dense add_i / mul_i tables - same messages."""
+    (sc_gkr_prover_create_sparse) instead of the dense add_i / mul_i tables - same messages.
+    `device=True` uploads the circuit once (DeviceCircuit), evaluates it on the GPU and keeps every layer's values
+    there: `evaluation` stays None, start_round makes the layer prover from the device gate list and table
+    (sc_gkr_prover_create_circuit), restrict_poly reads the device table, and only the outputs come back - same messages."""
 
-    def __init__(self, ctx, circuit, input, sparse=False):
+    def __init__(self, ctx, circuit, input, sparse=False, device=False):
         self.ctx, self.field, self.circuit = ctx, ctx.field, circuit
-        self.evaluation = circuit.evaluate(self.field, list(input))           # :346
+        self.device = device
+        if device:
+            self.dcircuit = DeviceCircuit(ctx, circuit)
+            inp = self.dcircuit._input(input)
+            self.tables = self.dcircuit.evaluate(inp) + [inp]                  # :346, W_0 .. W_d on the device
+            self.evaluation = None
+        else:
+            self.evaluation = circuit.evaluate(self.field, list(input))           # :346
         self.i, self.prover, self.w, self.r, self.sparse = 0, None, None, [], sparse
 
     @classmethod
-    def new(cls, ctx, circuit, input, sparse=False):
-        return cls(ctx, circuit, input, sparse)
+    def new(cls, ctx, circuit, input, sparse=False, device=False):
+        return cls(ctx, circuit, input, sparse, device)
 
     def start_protocol(self):
         """:363-367"""
+        if self.device:
+            return ProverMessage.Begin([int(x) for x in self.tables[0].to_evaluations()])
         return ProverMessage.Begin(self.evaluation[0])
 
     def start_round(self, i, r_i):
         """:373-436"""
         from .sum_check_protocol import Prover as SumCheckProver
         k_next = self.circuit.num_vars_at(i + 1)
-        if self.sparse:
+        if self.device:
+            eng = CircuitLayerProver(self.ctx, self.dcircuit, i, r_i, self.tables[i + 1])
+            self.w = self.tables[i + 1]
+            prover = _EngineProver(eng, self.field)
+            num_vars = 2 * k_next
+        elif self.sparse:
             eng = SparseLayerProver(self.ctx, self.circuit, self.evaluation, i, r_i)
             self.w = eng._w_next
             prover = _EngineProver(eng, self.field)
