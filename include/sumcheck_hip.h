@@ -217,6 +217,7 @@ int sc_ctx_kernel_time(sc_ctx* ctx, double out[2], int reset);
 #define SC_KIND_WFOLD_PASS 13  /* wfold_pass_kernel: a fold of kf = 4 / 5 variables of large tables that serves ks = 5 / 3..5 rounds (behind the matrix-core first pass; the pass behind that) */
 /* 12 was gram_finish_kernel (rounds 4: a second launch behind the gram pass; folded into gram_pass_kernel in round 5) */
 #define SC_KIND_CIRCUIT 14     /* circuit_layer_kernel: one layer of sc_circuit_evaluate; log_in = k[i] (gates), kf = k[i+1]; bytes = the streamed 20 B per gate */
+#define SC_KIND_MATMUL 15      /* sc_matmul: kf = 0 the byte repack, 1 matmul_mfma_kernel (int8 matrix cores), 2 matmul_tiled_kernel, 3 matmul_kernel (VALU); ks = n, log_in = 2n */
 typedef struct sc_launch_record {
   int32_t kind;           /* SC_KIND_* */
   int32_t kf, ks;         /* variables folded / rounds served (meaning per kind above) */
@@ -308,6 +309,13 @@ int sc_table_relabel(sc_ctx* ctx, const sc_table* in, size_t a, size_t b, size_t
  * 2^(2n) entries; point has 2n entries; outputs have 2^n entries. */
 int sc_matmul_g_new(sc_ctx* ctx, const sc_table* A, const sc_table* B, size_t n,
                     const uint64_t* point, sc_table** a_out, sc_table** b_out);
+/* C = A * B over the context's field (the product the MatMult protocol proves): A, B, C are 2^n x 2^n row-major
+ * tables of 2^(2n) Montgomery words, column index in the low n bits (as in sc_matmul_g_new), so
+ * C[i][j] = sum_k A[i][k] * B[k][j].  0 <= n <= 14.  The product runs on the int8 matrix cores from n = 5 (option
+ * "matmul_path": 0 auto, 1 matrix cores from n = 4, 2 VALU); C comes from the context's pool and the scratch goes back to
+ * it before the call returns.  SC_ERR_ARG: a null pointer, n > 14 or tables of another length; SC_ERR_UNSUPPORTED:
+ * a sharded context or a multi-device handle. */
+int sc_matmul(sc_ctx* ctx, const sc_table* A, const sc_table* B, size_t n, sc_table** C);
 /* G::to_evaluations (matrix-multiplication/src/lib.rs:137-146): out[i] = a[i]*b[i] */
 int sc_prod2_to_evaluations(sc_ctx* ctx, const sc_table* a, const sc_table* b, sc_table** out);
 /* Prover::new's claim: sum_i a[i]*b[i] (sum-check-protocol/src/lib.rs:89) - never

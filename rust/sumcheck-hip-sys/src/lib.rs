@@ -182,6 +182,13 @@ extern "C" {
         a_out: *mut *mut sc_table,
         b_out: *mut *mut sc_table,
     ) -> c_int;
+    pub fn sc_matmul(
+        ctx: *mut sc_ctx,
+        a: *const sc_table,
+        b: *const sc_table,
+        n: usize,
+        c: *mut *mut sc_table,
+    ) -> c_int;
     pub fn sc_prod2_to_evaluations(
         ctx: *mut sc_ctx,
         a: *const sc_table,

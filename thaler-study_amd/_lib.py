@@ -49,7 +49,10 @@ class ScLaunchRecord(ctypes.Structure):
                 ("bytes_read", u64), ("bytes_written", u64), ("ms", ctypes.c_double)]
 
 
-KIND_NAMES = {0: "pass", 2: "evaluate", 3: "fold", 4: "fix_low", 5: "fold_be", 6: "coldot", 7: "gkr", 8: "matsq", 10: "grid_pass", 11: "gram_pass", 13: "wfold_pass", 14: "circuit"}
+KIND_NAMES = {0: "pass", 2: "evaluate", 3: "fold", 4: "fix_low", 5: "fold_be", 6: "coldot", 7: "gkr", 8: "matsq", 10: "grid_pass", 11: "gram_pass", 13: "wfold_pass", 14: "circuit", 15: "matmul"}
+# SC_KIND_MATMUL records: kf -> the kernel that ran
+MATMUL_KERNELS = {0: "matmul_bytes_kernel", 1: "matmul_mfma_kernel", 2: "matmul_tiled_kernel", 3: "matmul_kernel"}
+MATMUL_PATHS = {"auto": 0, "mfma": 1, "valu": 2}
 
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, voidp, u64p, size_t)
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, voidp, u64p, u64p, size_t)
@@ -91,6 +94,7 @@ SIGNATURES = {
     "sc_table_evaluate_many": (ctypes.c_int, [voidp, voidp, u64p, size_t, size_t, ctypes.c_int, u64p]),
     "sc_table_relabel": (ctypes.c_int, [voidp, voidp, size_t, size_t, size_t, ctypes.POINTER(voidp)]),
     "sc_matmul_g_new": (ctypes.c_int, [voidp, voidp, voidp, size_t, u64p, ctypes.POINTER(voidp), ctypes.POINTER(voidp)]),
+    "sc_matmul": (ctypes.c_int, [voidp, voidp, voidp, size_t, ctypes.POINTER(voidp)]),
     "sc_prod2_to_evaluations": (ctypes.c_int, [voidp, voidp, voidp, ctypes.POINTER(voidp)]),
     "sc_prod2_sum": (ctypes.c_int, [voidp, voidp, voidp, u64p]),
     "sc_prod2_round_sums": (ctypes.c_int, [voidp, voidp, voidp, u64p]),

@@ -192,6 +192,9 @@ extern "C" int sc_ctx_set_option(sc_ctx* ctx, const char* key, int64_t value) {
     ctx->wfold5_min_log = (int)value;
   } else if (k == "wfold_always") {
     ctx->wfold_always = value ? 1 : 0;
+  } else if (k == "matmul_path") {
+    if (value < 0 || value > 2) return fail(ctx, SC_ERR_ARG, "matmul_path must be 0 (auto), 1 (int8 matrix cores) or 2 (VALU)");
+    ctx->matmul_path = (int)value;
   } else if (k == "wfold_min_log") {
     if (value < 12 || value > 40) return fail(ctx, SC_ERR_ARG, "wfold_min_log must be 12..40");
     ctx->wfold_min_log = (int)value;
@@ -261,6 +264,7 @@ extern "C" int sc_ctx_get_option(const sc_ctx* ctx, const char* key, int64_t* va
   else if (k == "wfold_log") *value = ctx->wfold_log;
   else if (k == "wfold_min_log") *value = ctx->wfold_min_log;
   else if (k == "wfold_always") *value = ctx->wfold_always;
+  else if (k == "matmul_path") *value = ctx->matmul_path;
   else if (k == "wfold5_min_log") *value = ctx->wfold5_min_log;
   else if (k == "stat_wait_ns") *value = (int64_t)(is_multi(ctx) ? ctx->subs[0]->stat_wait_ns : ctx->stat_wait_ns);
   else if (k == "stat_launch_ns") *value = (int64_t)(is_multi(ctx) ? ctx->subs[0]->stat_launch_ns : ctx->stat_launch_ns);

@@ -255,4 +255,5 @@ __device__ __forceinline__ void transpose_to_pieces(ull2* __restrict__ lds, ull2
 #include "kernels/gkr.hpp"
 #include "kernels/circuit.hpp"
 #include "kernels/triangle.hpp"
+#include "kernels/matmul.hpp"
 #include "kernels/peer.hpp"

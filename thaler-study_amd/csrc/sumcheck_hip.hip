@@ -156,6 +156,7 @@ struct sc_ctx {
   int wfold5_min_log = 24;           // a grid pass with FIVE challenges to fold over tables of >= 2^this entries runs in the same kernel's (5, ks) form
   int wfold_always = 0;              // 0: where the proof then needs fewer launches (the planner counts both ways); 1: wherever it can run
   int wfold_blocks = 0;              // its resident grid (0 = not asked yet)
+  int matmul_path = 0;               // sc_matmul: 0 auto (the int8 matrix cores from 32 x 32), 1 matrix cores (from 16 x 16), 2 VALU
   int tail_log = 16;  // shard log-size at which a sharded prover gathers: a 512 KiB all-gather per table is
                       // cheaper than the ~25 us of collective latency of each further sharded pass
   // grid cap of the streaming kernels: three 256-thread blocks per CU (set in sc_ctx_create).
@@ -465,5 +466,6 @@ static int multi_prod2_fold_and_sums(sc_ctx* m, const sc_table* a, const sc_tabl
 #include "engine/abi_gkr.inc"
 #include "engine/abi_circuit.inc"
 #include "engine/abi_triangle.inc"
+#include "engine/abi_matmul.inc"
 #include "engine/abi_restrict.inc"
 #include "engine/abi_multi.inc"

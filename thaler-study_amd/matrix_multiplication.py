@@ -177,3 +177,117 @@ def prove(ctx, g, seed_r, draw=None):
     cb = _lib.DRAW_FN(draw) if draw is not None else no_draw
     ctx.check(ctx.lib.sc_prove(ctx.h, g.f_a.h, g.f_b.h, cb, None, seed_r, p_c1, p_ev, p_ch))
     return int(c1.value), ev[: 3 * n].reshape(n, 3).copy(), ch[:n].copy()
+
+
+# ---- the product itself and the MatMult protocol around it (the reference's tests: `randomized_test`, `matrix_test_from_book`) ----
+
+_MASK64 = 2**64 - 1
+_SEED_R = 0xC7C7000000000003   # synthetic.SEED_R: the default challenger of sc_prove
+SEED_PT = 0xD8D8000000000004   # default seed of the point (r1, r2)
+
+
+def _splitmix64(x):
+    z = (x + 0x9E3779B97F4A7C15) & _MASK64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _MASK64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _MASK64
+    return z ^ (z >> 31)
+
+
+def product_point(field, n, seed_pt=SEED_PT):
+    """the point (r1, r2) as 2n Montgomery words, drawn in this order: r1 (the row point of A and C) first, then r2
+    (the column point of B and C); entry i is splitmix64(seed_pt + i + 1) mod p"""
+    return [field.from_int(_splitmix64((seed_pt + i + 1) & _MASK64) % field.p) for i in range(2 * n)]
+
+
+def _as_matrix(ctx, n, M):
+    if isinstance(M, DenseMultilinearExtension):
+        return M
+    return DenseMultilinearExtension.from_evaluations_vec(ctx, 2 * n, M)
+
+
+def matmul(ctx, n, A, B):
+    """C = A * B (sc_matmul) for 2^n x 2^n matrices flattened row-major: device tables or host arrays of Montgomery
+    words; returns C as a device table"""
+    A, B = _as_matrix(ctx, n, A), _as_matrix(ctx, n, B)
+    h = voidp()
+    ctx.check(ctx.lib.sc_matmul(ctx.h, A.h, B.h, n, ctypes.byref(h)))
+    return DenseMultilinearExtension(ctx, h)
+
+
+def product_claim(C, point):
+    """f~_C(r1, r2): C's index is (row << n) | col and its variables are LE, so the column point r2 comes first"""
+    n = len(point) // 2
+    return C.evaluate(list(point[n:]) + list(point[:n]))
+
+
+class ProductProof:
+    """the prover's side of MatMult: C, the point (r1, r2), the claim f~_C(r1, r2), c_1 and the sumcheck transcript over
+    G(z) = f~_A(r1, z) f~_B(z, r2) (evals[j] = g_j(0), g_j(1), g_j(2); challenges[j] = r_j)"""
+
+    def __init__(self, C, point, claim, c_1, evals, challenges):
+        self.C, self.point, self.claim, self.c_1 = C, list(point), claim, c_1
+        self.evals, self.challenges = evals, challenges
+
+
+def prove_product(ctx, n, A, B, C=None, seed_r=_SEED_R, draw=None, point=None, seed_pt=SEED_PT):
+    """MatMult, prover side: C on the device if not given (sc_matmul), the point (product_point order unless given),
+    claim = f~_C(r1, r2) (sc_table_evaluate), G::new on the device tables and the sumcheck (sc_prove)"""
+    A, B = _as_matrix(ctx, n, A), _as_matrix(ctx, n, B)
+    C = matmul(ctx, n, A, B) if C is None else _as_matrix(ctx, n, C)
+    pt = product_point(ctx.field, n, seed_pt) if point is None else [int(x) for x in point]
+    claim = product_claim(C, pt)
+    g = G.new_from_tables(ctx, n, A, B, pt)
+    c_1, evals, challenges = prove(ctx, g, seed_r, draw)
+    return ProductProof(C, pt, claim, c_1, evals, challenges)
+
+
+def verify_transcript(field, n, claim, c_1, evals, challenges, oracle):
+    """the host verifier of MatMult over a transcript: c_1 must equal the claim, then sum_check_protocol.Verifier (strict)
+    round by round with the transcript's challenges, and g_n(r_n) == oracle(r) at the end (also for n = 1, where the
+    reference's Verifier never reaches its final branch).  oracle(point) -> G(point).  Returns True / False."""
+    from .sum_check_protocol import Error, Verifier
+
+    if int(c_1) != int(claim) or len(evals) != n or len(challenges) < n:
+        return False
+
+    class _G:   # oracle access for the verifier's final round
+        def evaluate(self, r):
+            return oracle(r)
+
+    class _Script:
+        def __init__(self):
+            self.j = 0
+
+        def draw(self):
+            r = int(challenges[self.j])
+            self.j += 1
+            return r
+
+    v = Verifier.new(n, _G(), field, strict=True)
+    v.set_c_1(int(c_1))
+    rng, polys = _Script(), []
+    try:
+        for j in range(n):
+            e = [int(x) for x in evals[j]]
+            poly = interpolate_quadratic_poly(field, [(field.zero, e[0]), (field.one, e[1]), (field.two, e[2])])
+            polys.append(poly)
+            res = v.round(poly, rng)
+            if res.is_final() and not res.value:
+                return False
+    except Error:
+        return False
+    if n == 1:
+        r = [int(challenges[0])]
+        return polys[0].evaluate(r[0]) == oracle(r)
+    return True
+
+
+def verify_product(ctx, n, A, B, C, proof):
+    """MatMult, verifier side: the claim is recomputed from C (the product under test), then verify_transcript with
+    G.evaluate on the device tables as the oracle.  A C with a wrong entry changes f~_C(r1, r2) and is rejected."""
+    A, B, C = _as_matrix(ctx, n, A), _as_matrix(ctx, n, B), _as_matrix(ctx, n, C)
+    claim = product_claim(C, proof.point)
+    if claim != proof.claim:
+        return False
+    g = G.new_from_tables(ctx, n, A, B, proof.point)
+    return verify_transcript(ctx.field, n, claim, proof.c_1, proof.evals, proof.challenges, g.evaluate)
