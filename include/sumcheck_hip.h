@@ -218,6 +218,8 @@ int sc_ctx_kernel_time(sc_ctx* ctx, double out[2], int reset);
 /* 12 was gram_finish_kernel (rounds 4: a second launch behind the gram pass; folded into gram_pass_kernel in round 5) */
 #define SC_KIND_CIRCUIT 14     /* circuit_layer_kernel: one layer of sc_circuit_evaluate; log_in = k[i] (gates), kf = k[i+1]; bytes = the streamed 20 B per gate */
 #define SC_KIND_MATMUL 15      /* sc_matmul: kf = 0 the byte repack, 1 matmul_mfma_kernel (int8 matrix cores), 2 matmul_tiled_kernel, 3 matmul_kernel (VALU); ks = n, log_in = 2n */
+#define SC_KIND_BATCH_PASS 16  /* batch_pass_kernel: one pass of every instance of sc_prove_batch; kf, ks and log_in (= n at the first pass) as for a grid
+                                * pass; the batch size is bytes_read / (16 * 2^log_in) */
 typedef struct sc_launch_record {
   int32_t kind;           /* SC_KIND_* */
   int32_t kf, ks;         /* variables folded / rounds served (meaning per kind above) */
@@ -401,6 +403,22 @@ int sc_prover_destroy(sc_prover* pr);
 typedef uint64_t (*sc_draw_fn)(void* user, size_t round, const uint64_t evals[3]);
 int sc_prove(sc_ctx* ctx, const sc_table* a, const sc_table* b, sc_draw_fn draw, void* user,
              uint64_t seed_r, uint64_t* c1, uint64_t* evals, uint64_t* challenges);
+
+/* A batch of `count` independent proofs of the same size, proved together: instance i is G_i = a[i] * b[i] (all tables 2^n
+ * entries, the same n) and gets exactly what sc_prove(ctx, a[i], b[i], ..., seed_r[i], ...) gives it alone - c1[i], its
+ * round polynomials evals[3*(i*n + j) ..] and challenges[i*n + j] (evals and challenges may be NULL).  This is not a random
+ * linear combination of the instances: every transcript is bit-identical to its own sc_prove.  draw == NULL uses the synthetic
+ * challenger of sc_prove over seed_r[i].  For 1 <= n <= 20 one launch (SC_KIND_BATCH_PASS) serves every instance at each pass
+ * of the single-proof schedule (sc_plan_proof), so a batch makes as many launches as one proof.  Order of the draw calls:
+ * round by round, and within a round in instance order 0 .. count-1; draw(user, i, j, evals) is called once instance i's
+ * round-j polynomial is on the host.  For n = 0 and n > 20 the instances are proved one after another through sc_prove (the
+ * same results, nothing gained: the draw calls then come instance by instance).  The tables are only read; one table may
+ * appear in several instances.  Refused before any launch: count == 0, count > 1024 or a NULL array (SC_ERR_ARG), tables
+ * that are not 2^n long or differ in length (SC_ERR_ARG), sharded contexts and multi-device handles (SC_ERR_UNSUPPORTED).
+ * A draw that returns an unreduced challenge ends the call with SC_ERR_ARG, as in sc_prove. */
+typedef uint64_t (*sc_draw_batch_fn)(void* user, size_t instance, size_t round, const uint64_t evals[3]);
+int sc_prove_batch(sc_ctx* ctx, size_t count, const sc_table* const* a, const sc_table* const* b, sc_draw_batch_fn draw, void* user,
+                   const uint64_t* seed_r, uint64_t* c1, uint64_t* evals, uint64_t* challenges);
 
 /* ---- gkr_protocol::round_polynomial::W -----------------------
  *   f(b,c) = add_i(r_i,b,c) (W(b) + W(c)) + mul_i(r_i,b,c) W(b) W(c)

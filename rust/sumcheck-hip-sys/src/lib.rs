@@ -96,6 +96,8 @@ pub type sc_allreduce_fn = Option<unsafe extern "C" fn(user: *mut c_void, buf: *
 pub type sc_allgather_fn =
     Option<unsafe extern "C" fn(user: *mut c_void, send: *const u64, recv: *mut u64, count: usize) -> c_int>;
 pub type sc_draw_fn = Option<unsafe extern "C" fn(user: *mut c_void, round: usize, evals: *const u64) -> u64>;
+/// `sc_prove_batch`: called round by round, within a round in instance order.
+pub type sc_draw_batch_fn = Option<unsafe extern "C" fn(user: *mut c_void, instance: usize, round: usize, evals: *const u64) -> u64>;
 
 extern "C" {
     pub fn sc_field_from_modulus(p: u64, out: *mut sc_field) -> c_int;
@@ -243,6 +245,18 @@ extern "C" {
         draw: sc_draw_fn,
         user: *mut c_void,
         seed_r: u64,
+        c1: *mut u64,
+        evals: *mut u64,
+        challenges: *mut u64,
+    ) -> c_int;
+    pub fn sc_prove_batch(
+        ctx: *mut sc_ctx,
+        count: usize,
+        a: *const *const sc_table,
+        b: *const *const sc_table,
+        draw: sc_draw_batch_fn,
+        user: *mut c_void,
+        seed_r: *const u64,
         c1: *mut u64,
         evals: *mut u64,
         challenges: *mut u64,

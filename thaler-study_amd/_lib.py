@@ -49,7 +49,7 @@ class ScLaunchRecord(ctypes.Structure):
                 ("bytes_read", u64), ("bytes_written", u64), ("ms", ctypes.c_double)]
 
 
-KIND_NAMES = {0: "pass", 2: "evaluate", 3: "fold", 4: "fix_low", 5: "fold_be", 6: "coldot", 7: "gkr", 8: "matsq", 10: "grid_pass", 11: "gram_pass", 13: "wfold_pass", 14: "circuit", 15: "matmul"}
+KIND_NAMES = {0: "pass", 2: "evaluate", 3: "fold", 4: "fix_low", 5: "fold_be", 6: "coldot", 7: "gkr", 8: "matsq", 10: "grid_pass", 11: "gram_pass", 13: "wfold_pass", 14: "circuit", 15: "matmul", 16: "batch_pass"}
 # SC_KIND_MATMUL records: kf -> the kernel that ran
 MATMUL_KERNELS = {0: "matmul_bytes_kernel", 1: "matmul_mfma_kernel", 2: "matmul_tiled_kernel", 3: "matmul_kernel"}
 MATMUL_PATHS = {"auto": 0, "mfma": 1, "valu": 2}
@@ -57,6 +57,7 @@ MATMUL_PATHS = {"auto": 0, "mfma": 1, "valu": 2}
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, voidp, u64p, size_t)
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, voidp, u64p, u64p, size_t)
 DRAW_FN = ctypes.CFUNCTYPE(u64, voidp, size_t, u64p)
+DRAW_BATCH_FN = ctypes.CFUNCTYPE(u64, voidp, size_t, size_t, u64p)
 
 # name -> (restype, argtypes); every symbol include/sumcheck_hip.h declares
 SIGNATURES = {
@@ -110,6 +111,8 @@ SIGNATURES = {
     "sc_prover_round": (ctypes.c_int, [voidp, u64, size_t, u64p]),
     "sc_prover_destroy": (ctypes.c_int, [voidp]),
     "sc_prove": (ctypes.c_int, [voidp, voidp, voidp, DRAW_FN, voidp, u64, u64p, u64p, u64p]),
+    "sc_prove_batch": (ctypes.c_int, [voidp, size_t, ctypes.POINTER(voidp), ctypes.POINTER(voidp), DRAW_BATCH_FN, voidp, u64p, u64p,
+                                       u64p, u64p]),
     "sc_gkr_wiring": (ctypes.c_int, [voidp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint32),
                                       ctypes.POINTER(ctypes.c_uint32), size_t, size_t, u64p, ctypes.POINTER(voidp),
                                       ctypes.POINTER(voidp)]),

@@ -416,6 +416,31 @@ void shard_commit(ProverShard& s, u64* na, u64* nb) {
   s.cur_b = nb;
 }
 
+// out[i] = sum_c w[c] h[2^kf i + c], i < out_len (kf = 0: a copy)
+void host_fold(const sc::MontGeneric& f, const sc::GridW& gw, int kf, const u64* h, u64* dst, size_t out_len) {
+  const int fan = 1 << kf;
+  if (kf == 0) {
+    memcpy(dst, h, out_len * sizeof(u64));
+    return;
+  }
+  for (size_t i = 0; i < out_len; ++i) {   // (four outputs interleaved measured the same: the hand-over is bound by the
+    sc::MontGeneric::Acc3 acc;              // host's first read of what the device wrote, ~0.1 us per KiB, not by the sums)
+    f.acc3_zero(acc);
+    for (int c = 0; c < fan; ++c) f.acc3_mac(acc, h[i * fan + c], gw.w[c]);
+    dst[i] = f.acc3_get(acc);
+  }
+}
+// the host has the whole tables in ha / hb: every round from here on is host_round()
+void enter_host_mode(sc_prover* pr) {
+  pr->cur_log = 0;   // nothing is left on the devices
+  pr->pending.clear();
+  pr->sharded = false;
+  pr->on_host = false;
+  pr->host_mode = true;
+  pr->cache_ks = 0;
+  pr->g_known = -1;
+}
+
 // The host finishes (SC_PLAN_HOST_TAIL).  Every shard's tables of 2^cur_log entries are in its pinned tail slot (written by the
 // pass before, whose sequence word has been seen: plain host reads) - or, for the single-entry shards of a tiny proof on a
 // multi-device handle, wherever they are (fetched with a copy).  Each shard's kf pending challenges are folded first - on a
@@ -425,7 +450,7 @@ void shard_commit(ProverShard& s, u64* na, u64* nb) {
 // Work: <= 2 * 2^host_tail_log multiply-adds per shard thread + ~5 field operations per entry of the whole table per round.
 int host_tail(sc_prover* pr, int kf) {
   sc_ctx* m = pr->ctx;
-  const int n = (int)pr->sh.size(), fan = 1 << kf;
+  const int n = (int)pr->sh.size();
   const size_t in_len = (size_t)1 << pr->cur_log, out_len = in_len >> kf;
   if (pr->cur_log < kf) return fail(m, SC_ERR_STATE, "host tail: 2^%d entries cannot fold %d challenges", pr->cur_log, kf);
   const sc::GridW gw = make_grid_weights(m, pr->pending.data(), kf);
@@ -451,17 +476,7 @@ int host_tail(sc_prover* pr, int kf) {
         SC_HIP(sub, hipStreamSynchronize(sub->stream));
         h = tmp.data();
       }
-      u64* dst = (t ? pr->hb.data() : pr->ha.data()) + (size_t)d * out_len;
-      if (kf == 0) {
-        memcpy(dst, h, out_len * sizeof(u64));
-      } else {
-        for (size_t i = 0; i < out_len; ++i) {   // (four outputs interleaved measured the same: the hand-over is bound by the
-          sc::MontGeneric::Acc3 acc;              // host's first read of what the device wrote, ~0.1 us per KiB, not by the sums)
-          f.acc3_zero(acc);
-          for (int c = 0; c < fan; ++c) f.acc3_mac(acc, h[i * fan + c], gw.w[c]);
-          dst[i] = f.acc3_get(acc);
-        }
-      }
+      host_fold(f, gw, kf, h, (t ? pr->hb.data() : pr->ha.data()) + (size_t)d * out_len, out_len);
     }
     return SC_OK;
   };
@@ -511,13 +526,7 @@ int prover_pass(sc_prover* pr, size_t j) {
   ProverShard& s0 = pr->sh[0];
   if (plan.kind == PassPlan::kHostTail) {
     SC_TRY(host_tail(pr, kf));
-    pr->cur_log = 0;   // nothing is left on the devices: every round from here on is host_round() on ha / hb
-    pr->pending.clear();
-    pr->sharded = false;
-    pr->on_host = false;
-    pr->host_mode = true;
-    pr->cache_ks = 0;
-    pr->g_known = -1;
+    enter_host_mode(pr);
     return SC_OK;
   }
   if (plan.kind == PassPlan::kRankPass) {

@@ -256,4 +256,5 @@ __device__ __forceinline__ void transpose_to_pieces(ull2* __restrict__ lds, ull2
 #include "kernels/circuit.hpp"
 #include "kernels/triangle.hpp"
 #include "kernels/matmul.hpp"
+#include "kernels/batch.hpp"
 #include "kernels/peer.hpp"

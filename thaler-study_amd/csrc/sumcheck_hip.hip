@@ -243,6 +243,14 @@ struct sc_ctx {
   // sc_table_evaluate_many: the points of one launch (16 x 64 words), pinned staging and its device copy (allocated on first use)
   u64* h_points = nullptr;
   u64* d_points = nullptr;
+  // sc_prove_batch (engine/abi_batch.inc), allocated on first use and grown on demand: pinned staging of the per-instance
+  // descriptors, and pinned device-mapped memory for the cells of every instance followed by the tables handed to the host
+  void* h_batch_desc = nullptr;
+  size_t batch_desc_bytes = 0;
+  u64* h_batch = nullptr;
+  u64* d_batch = nullptr;
+  size_t batch_words = 0;
+  int batch_blocks = 0;     // resident grid of batch_pass_kernel (0 = not asked yet)
 
   // kernel timing
   // pass-kernel timing (option "time_kernels"): a ring of event pairs, read back only when the
@@ -467,5 +475,6 @@ static int multi_prod2_fold_and_sums(sc_ctx* m, const sc_table* a, const sc_tabl
 #include "engine/abi_circuit.inc"
 #include "engine/abi_triangle.inc"
 #include "engine/abi_matmul.inc"
+#include "engine/abi_batch.inc"
 #include "engine/abi_restrict.inc"
 #include "engine/abi_multi.inc"

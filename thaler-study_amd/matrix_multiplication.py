@@ -179,6 +179,56 @@ def prove(ctx, g, seed_r, draw=None):
     return int(c1.value), ev[: 3 * n].reshape(n, 3).copy(), ch[:n].copy()
 
 
+def _batch_seeds(seed_r, count):
+    """seed_r of prove_batch: None -> _SEED_R + i for instance i, an int -> the same seed for every instance, a sequence ->
+    one seed per instance"""
+    if seed_r is None:
+        return [(_SEED_R + i) & _MASK64 for i in range(count)]
+    if isinstance(seed_r, (int, np.integer)):
+        return [int(seed_r) & _MASK64] * count
+    seeds = [int(x) for x in seed_r]
+    if len(seeds) != count:
+        raise ValueError("seed_r has %d entries for %d instances" % (len(seeds), count))
+    return [x & _MASK64 for x in seeds]
+
+
+def prove_batch(ctx, gs, seed_r=None, draw=None):
+    """sc_prove_batch: B independent proofs of G_i = f_a * f_b, all with the same num_vars, proved together (one launch per
+    pass for the whole batch).  Instance i gets exactly what prove(ctx, gs[i], seed_r[i], ...) gives it alone.
+    seed_r: None (instance i uses _SEED_R + i), one int for all, or one per instance.  draw(instance, round, evals) -> the
+    challenge (called round by round, within a round in instance order); None: the synthetic challenger.
+    Returns [(c_1, evals[n][3], challenges[n])] per instance."""
+    gs = list(gs)
+    if not gs:
+        raise ValueError("prove_batch needs at least one instance")
+    for g in gs:
+        if not isinstance(g, G):
+            raise TypeError("prove_batch takes matrix_multiplication.G instances, not %s" % type(g).__name__)
+        if g.ctx is not ctx:
+            raise ValueError("every instance must live on the context the batch runs on")
+    if draw is not None and not callable(draw):
+        raise TypeError("draw must be callable (instance, round, evals) -> challenge")
+    seeds = _batch_seeds(seed_r, len(gs))
+    n = gs[0].num_vars()
+    if any(g.num_vars() != n for g in gs):
+        raise ValueError("every instance of a batch must have the same num_vars")
+    B = len(gs)
+    ta = (voidp * B)(*[g.f_a.h for g in gs])
+    tb = (voidp * B)(*[g.f_b.h for g in gs])
+    sd = np.array(seeds, dtype=np.uint64)
+    c1 = np.zeros(B, dtype=np.uint64)
+    ev = np.zeros(3 * max(n, 1) * B, dtype=np.uint64)
+    ch = np.zeros(max(n, 1) * B, dtype=np.uint64)
+    if draw is None:
+        cb = ctypes.cast(None, _lib.DRAW_BATCH_FN)
+    else:
+        cb = _lib.DRAW_BATCH_FN(lambda _user, i, j, e: int(draw(int(i), int(j), [int(e[0]), int(e[1]), int(e[2])])))
+    ctx.check(ctx.lib.sc_prove_batch(ctx.h, B, ta, tb, cb, None, _u64p(sd), _u64p(c1), _u64p(ev), _u64p(ch)))
+    ev = ev[: 3 * n * B].reshape(B, n, 3)
+    ch = ch[: n * B].reshape(B, n)
+    return [(int(c1[i]), ev[i].copy(), ch[i].copy()) for i in range(B)]
+
+
 # ---- the product itself and the MatMult protocol around it (the reference's tests: `randomized_test`, `matrix_test_from_book`) ----
 
 _MASK64 = 2**64 - 1
@@ -239,6 +289,43 @@ def prove_product(ctx, n, A, B, C=None, seed_r=_SEED_R, draw=None, point=None, s
     g = G.new_from_tables(ctx, n, A, B, pt)
     c_1, evals, challenges = prove(ctx, g, seed_r, draw)
     return ProductProof(C, pt, claim, c_1, evals, challenges)
+
+
+def prove_products(ctx, n, pairs, Cs=None, seed_r=None, draw=None, points=None, seed_pt=SEED_PT):
+    """MatMult, prover side, for many products of 2^n x 2^n matrices: per pair (A, B) what prove_product does - C (sc_matmul
+    unless Cs gives it), the point (product_point order unless points gives one per pair), the claim f~_C(r1, r2), G::new -
+    with the sumchecks of all pairs proved together (prove_batch; seed_r and draw as there).  Returns one ProductProof per
+    pair, each accepted by verify_product as it stands."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= int(n) <= 14:
+        raise ValueError("n must be an int in 0..14 (2^n x 2^n matrices)")
+    n = int(n)
+    pairs = list(pairs)
+    if not pairs:
+        raise ValueError("prove_products needs at least one (A, B) pair")
+    if any(not isinstance(pr, (tuple, list)) or len(pr) != 2 for pr in pairs):
+        raise TypeError("pairs must be (A, B) tuples")
+    if Cs is not None:
+        Cs = list(Cs)
+        if len(Cs) != len(pairs):
+            raise ValueError("Cs has %d entries for %d pairs" % (len(Cs), len(pairs)))
+    if points is not None:
+        points = [[int(x) for x in pt] for pt in points]
+        if len(points) != len(pairs) or any(len(pt) != 2 * n for pt in points):
+            raise ValueError("points must hold one point of 2n = %d words per pair" % (2 * n))
+    if draw is not None and not callable(draw):
+        raise TypeError("draw must be callable (instance, round, evals) -> challenge")
+    seeds = _batch_seeds(seed_r, len(pairs))
+    Cm, pts, claims, gs = [], [], [], []
+    for i, (A, B) in enumerate(pairs):
+        A, B = _as_matrix(ctx, n, A), _as_matrix(ctx, n, B)
+        C = matmul(ctx, n, A, B) if Cs is None or Cs[i] is None else _as_matrix(ctx, n, Cs[i])
+        pt = product_point(ctx.field, n, seed_pt) if points is None else points[i]
+        Cm.append(C)
+        pts.append(pt)
+        claims.append(product_claim(C, pt))
+        gs.append(G.new_from_tables(ctx, n, A, B, pt))
+    out = prove_batch(ctx, gs, seeds, draw)
+    return [ProductProof(Cm[i], pts[i], claims[i], *out[i]) for i in range(len(pairs))]
 
 
 def verify_transcript(field, n, claim, c_1, evals, challenges, oracle):
