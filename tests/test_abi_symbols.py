@@ -167,15 +167,17 @@ def test_round_engine_patch_applies_to_the_reference(tmp_path):
         _apply_patch(tmp_path / "tree", open(lib_rs).read().splitlines())
 
 
-def test_rccl_library_selection_and_the_test_double():
+def test_rccl_library_selection_with_the_test_double():
     """SC_RCCL_LIBRARY names the RCCL build the product dlopen()s - that file or nothing.  tests/rccl_double (the stand-in that
     lets the RCCL plane's N > 1 control flow run between processes on one GPU) exports the seven entry points the product
     resolves, and serves sc_comm_unique_id through the product without a GPU; a path that cannot be loaded is an error that
-    says so, never a silent fall back to librccl."""
+    says so, never a silent fall back to librccl.  The double is built here when it is missing or stale (as the compiled
+    callers of the GPU tests are), not assumed to be left behind by an earlier build()."""
     import subprocess
     import sys
-    double = os.path.join(ROOT, "tests", "rccl_double", "librccl_double.so")
-    assert os.path.exists(double), "build it: __graft_entry__.build()"
+    import __graft_entry__ as ge
+    double = ge.build_rccl_double()
+    assert double == os.path.join(ROOT, "tests", "rccl_double", "librccl_double.so") and os.path.exists(double)
     syms = subprocess.run(["nm", "-D", "--defined-only", double], capture_output=True, text=True, check=True).stdout
     for name in ("ncclGetUniqueId", "ncclCommInitRank", "ncclCommDestroy", "ncclCommCount", "ncclAllReduce", "ncclAllGather", "ncclGetErrorString"):
         assert (" T " + name) in syms, name

@@ -57,7 +57,8 @@ def test_options_round_trip_and_validation():
     ctx = pkg.Context(pkg.Field(GOLD))
     for key, good, bad in [("grid_pass", 0, None), ("grid_log", 21, 99), ("grid_max_vars", 3, 0), ("arena_log", 12, 2),
                            ("peer_spin_ms", 100, 0), ("peer_connect_ms", 5000, 0), ("dbg_delay_ms", 3, -1),
-                           ("tail_log", 14, -1), ("vars_per_pass", 1, 3)]:
+                           ("tail_log", 14, -1), ("vars_per_pass", 1, 3), ("fold_dma", 0, None), ("pipe32", 0, None),
+                           ("pipe32_log", 24, 10), ("dbg_skip_tag", 1, None), ("dbg_fold_grab", 4, 17)]:
         ctx.set_option(key, good)
         assert ctx.get_option(key) == good
         if bad is not None:

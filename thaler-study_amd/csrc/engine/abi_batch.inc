@@ -61,19 +61,12 @@ int batch_reserve(sc_ctx* ctx, size_t count, int tail_log) {
 
 // blocks per instance: the resident grid shared among the instances, at least one, at most what the instance has rows for
 int batch_blocks_per_instance(sc_ctx* ctx, size_t count, size_t n_out) {
-  if (ctx->batch_blocks == 0) {
-    int per_cu = 0;
-    const void* fn = ctx->gold ? reinterpret_cast<const void*>(&sc::batch_pass_kernel<sc::GoldilocksMont, 5, false>)
-                               : reinterpret_cast<const void*>(&sc::batch_pass_kernel<sc::MontGeneric, 5, false>);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, sc::kBlock, 0) != hipSuccess || per_cu < 1) {
-      (void)hipGetLastError();
-      per_cu = 2;
-    }
-    ctx->batch_blocks = per_cu * ctx->num_cus;
-  }
+  const int resident = resident_grid(ctx, ctx->gold ? kernel_ptr(&sc::batch_pass_kernel<sc::GoldilocksMont, 5, false>)
+                                                    : kernel_ptr(&sc::batch_pass_kernel<sc::MontGeneric, 5, false>),
+                                     sc::kBlock, 2 * ctx->num_cus);
   constexpr size_t kWaves = sc::kBlock / sc::kWave;
   const size_t n_iter = (n_out + sc::kWgEntries - 1) / sc::kWgEntries;
-  const size_t share = ((size_t)ctx->batch_blocks + count - 1) / count;
+  const size_t share = ((size_t)resident + count - 1) / count;
   return (int)std::max<size_t>(1, std::min({share, (n_iter + kWaves - 1) / kWaves, (size_t)sc::kBatchMaxBlocks}));
 }
 
@@ -106,7 +99,7 @@ int batch_pass(sc_ctx* ctx, std::vector<sc_prover>& pr, BatchBufs& bb, int kf, i
     d.b = pr[i].sh[0].cur_b;
     d.a2 = out_base ? out_base + i * 2 * n_out : nullptr;
     d.b2 = out_base ? d.a2 + n_out : nullptr;
-    d.gw = make_grid_weights(ctx, pr[i].pending.data(), kf);
+    d.gw = make_weights<sc::GridW>(ctx, pr[i].pending.data(), kf);
   }
   const int bpi = batch_blocks_per_instance(ctx, count, n_out);
   constexpr size_t kWaves = sc::kBlock / sc::kWave;
@@ -128,21 +121,11 @@ int batch_pass(sc_ctx* ctx, std::vector<sc_prover>& pr, BatchBufs& bb, int kf, i
     rc = timer_begin(ctx, SC_KIND_BATCH_PASS, kf, ks, log_in, (u64)count * (16ull << log_in), kf > 0 ? (u64)count * (16ull << (log_in - kf)) : 0);
   if (rc == SC_OK) {
     const dim3 grid((unsigned)bpi, (unsigned)count);
-#define SC_BATCH(KS)                                                                                                               \
-  do {                                                                                                                             \
-    if (pf) hipLaunchKernelGGL((sc::batch_pass_kernel<F, KS, true>), grid, dim3(sc::kBlock), 0, ctx->stream, f, dd, kf, n_out, bo);  \
-    else hipLaunchKernelGGL((sc::batch_pass_kernel<F, KS, false>), grid, dim3(sc::kBlock), 0, ctx->stream, f, dd, kf, n_out, bo);    \
-  } while (0)
-    SC_DISPATCH_FIELD(ctx, F, f, {
-      switch (ks) {
-        case 1: SC_BATCH(1); break;
-        case 2: SC_BATCH(2); break;
-        case 3: SC_BATCH(3); break;
-        case 4: SC_BATCH(4); break;
-        default: SC_BATCH(5); break;
-      }
-    });
-#undef SC_BATCH
+    SC_DISPATCH_FIELD(ctx, F, f, with_bool(pf, [&](auto PF) {
+      with_const<1, 2, 3, 4, 5>(ks, [&](auto KS) {
+        hipLaunchKernelGGL((sc::batch_pass_kernel<F, KS, PF>), grid, dim3(sc::kBlock), 0, ctx->stream, f, dd, kf, n_out, bo);
+      });
+    }));
     if (hipGetLastError() != hipSuccess) {
       poison(ctx);
       rc = fail(ctx, SC_ERR_HIP, "batch_pass_kernel launch failed");
@@ -157,8 +140,7 @@ int batch_pass(sc_ctx* ctx, std::vector<sc_prover>& pr, BatchBufs& bb, int kf, i
     pool_release(ctx, folded);
     return rc;
   }
-  int cells = 1;
-  for (int i = 0; i < ks; ++i) cells *= 3;
+  const int cells = pow3(ks);
   for (size_t i = 0; i < count; ++i) {
     sc_prover& p = pr[i];
     memcpy(p.S, ctx->h_batch + i * sc::kGridMaxCells, (size_t)cells * sizeof(u64));
@@ -225,7 +207,7 @@ int prove_batch_impl(sc_ctx* ctx, size_t count, const sc_table* const* a, const 
         const size_t in_len = (size_t)1 << cur_log, out_len = in_len >> kf;
         for (size_t i = 0; i < count; ++i) {
           sc_prover& q = pr[i];
-          const sc::GridW gw = make_grid_weights(ctx, q.pending.data(), kf);
+          const sc::GridW gw = make_weights<sc::GridW>(ctx, q.pending.data(), kf);
           q.ha.resize(out_len);
           q.hb.resize(out_len);
           host_fold(hf.f, gw, kf, h + i * 2 * in_len, q.ha.data(), out_len);

@@ -49,12 +49,9 @@ int circuit_evaluate_impl(sc_ctx* ctx, const sc_circuit* c, const sc_table* inpu
     const unsigned* w = circuit_layer_words(c, i);
     const int grid = grid_for_wide(ctx, std::max<size_t>(n >> 2, 1));
     const bool nt = c->k[i] >= (size_t)ctx->nt_load_log;
-    SC_DISPATCH_FIELD(ctx, F, f, {
-      if (nt)
-        hipLaunchKernelGGL((sc::circuit_layer_kernel<F, true>), dim3(grid), dim3(sc::kBlock), 0, ctx->stream, f, w, n, c->stride[i], in, out);
-      else
-        hipLaunchKernelGGL((sc::circuit_layer_kernel<F, false>), dim3(grid), dim3(sc::kBlock), 0, ctx->stream, f, w, n, c->stride[i], in, out);
-    });
+    SC_DISPATCH_FIELD(ctx, F, f, with_bool(nt, [&](auto NT) {
+      hipLaunchKernelGGL((sc::circuit_layer_kernel<F, NT>), dim3(grid), dim3(sc::kBlock), 0, ctx->stream, f, w, n, c->stride[i], in, out);
+    }));
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
       poison(ctx);

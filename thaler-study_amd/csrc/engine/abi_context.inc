@@ -157,133 +157,80 @@ extern "C" const char* sc_last_error(const sc_ctx* ctx) {
 
 static int prewarm(sc_ctx* ctx, size_t num_vars);   // abi_prover.inc
 
+// The options that are plain settings of the context: sc_ctx_set_option validates and stores them, sc_ctx_get_option reads
+// them back.  A value is accepted in lo..hi, or as 0 too (kOptOff: 0 = never), or is any value stored as 0 / 1 (kOptBool).
+// kOptPeer: the option belongs to the peer transport, and a multi-device handle (no exchange between kernels) refuses it.
+enum : unsigned { kOptBool = 1, kOptOff = 2, kOptPeer = 4 };
+struct OptionSpec {
+  const char* name;
+  int sc_ctx::*member;
+  int64_t lo, hi;
+  unsigned flags;
+};
+const OptionSpec kOptions[] = {
+    {"vars_per_pass", &sc_ctx::vars_per_pass, 1, 2, 0},
+    {"first_pass_vars", &sc_ctx::first_pass_vars, 0, 4, 0},   // 0 auto; 4: the matrix-core pass at any size
+    {"grid_pass", &sc_ctx::grid_pass, 0, 1, kOptBool},
+    {"grid_log", &sc_ctx::grid_log, 0, 26, 0},
+    {"grid_max_vars", &sc_ctx::grid_max_vars, 1, sc::kGridMaxVars, 0},
+    {"grid_sharded", &sc_ctx::grid_sharded, 0, 1, kOptBool},
+    {"grid_blocks", &sc_ctx::grid_blocks, 0, kWgMaxBlocks, 0},
+    {"fold_dma", &sc_ctx::fold_dma, 0, 1, kOptBool},
+    {"pipe32", &sc_ctx::pipe32, 0, 1, kOptBool},
+    {"pipe32_log", &sc_ctx::pipe32_log, 11, 40, 0},
+    {"gram_log", &sc_ctx::gram_log, 14, 40, kOptOff},
+    {"wfold_log", &sc_ctx::wfold_log, 12, 40, kOptOff},
+    {"wfold_min_log", &sc_ctx::wfold_min_log, 12, 40, 0},
+    {"wfold5_min_log", &sc_ctx::wfold5_min_log, 12, 40, 0},
+    {"wfold_always", &sc_ctx::wfold_always, 0, 1, kOptBool},
+    {"matmul_path", &sc_ctx::matmul_path, 0, 2, 0},   // 0 auto, 1 int8 matrix cores, 2 VALU
+    {"host_tail_log", &sc_ctx::host_tail_log, 0, kTailLogMax, 0},
+    {"tail_log", &sc_ctx::tail_log, 0, 40, 0},
+    {"max_blocks", &sc_ctx::max_blocks, 1, INT64_MAX, 0},   // (1..partial_rows: sc_ctx_set_option)
+    {"time_kernels", &sc_ctx::time_kernels, 0, 1, kOptBool},   // recorded pairs stay in the ring until it fills or the totals are read
+    {"use_mailbox", &sc_ctx::use_mailbox, 0, 1, kOptBool},
+    {"nt_load_log", &sc_ctx::nt_load_log, INT64_MIN, INT64_MAX, 0},
+    {"nt_store_log", &sc_ctx::nt_store_log, INT64_MIN, INT64_MAX, 0},
+    {"pool_contiguous", &sc_ctx::pool_contiguous, 0, 1, kOptBool},
+    {"dbg_fold_grab", &sc_ctx::dbg_fold_grab, 0, 16, 0},
+    {"rccl_timeout_ms", &sc_ctx::rccl_timeout_ms, 1, 3600000, 0},
+    {"arena_log", &sc_ctx::arena_log, 4, 26, kOptPeer},   // (only before sc_ctx_comm_peer_export: sc_ctx_set_option)
+    {"peer_spin_ms", &sc_ctx::peer_spin_ms, 1, 600000, kOptPeer},
+    {"peer_connect_ms", &sc_ctx::peer_connect_ms, 1, 3600000, kOptPeer},
+    {"dbg_delay_ms", &sc_ctx::dbg_delay_ms, 0, 10000, kOptPeer},
+    {"dbg_skip_tag", &sc_ctx::dbg_skip_tag, 0, 1, kOptBool | kOptPeer},
+};
+static const OptionSpec* find_option(const char* key) {
+  for (const OptionSpec& o : kOptions)
+    if (strcmp(o.name, key) == 0) return &o;
+  return nullptr;
+}
+
 extern "C" int sc_ctx_set_option(sc_ctx* ctx, const char* key, int64_t value) {
   if (!ctx || !key) return SC_ERR_ARG;
-  std::string k(key);
+  const std::string k(key);
   if (k == "prewarm") return value < 0 ? fail(ctx, SC_ERR_ARG, "prewarm: num_vars must be >= 0") : prewarm(ctx, (size_t)value);   // an action, not a setting
   if (is_multi(ctx)) SC_TRY(multi_set_option(ctx, key, value));   // every shard first (they validate); then the handle's own copy
-  if (k == "vars_per_pass") {
-    if (value != 1 && value != 2) return fail(ctx, SC_ERR_ARG, "vars_per_pass must be 1 or 2");
-    ctx->vars_per_pass = (int)value;
-  } else if (k == "first_pass_vars") {
-    if (value < 0 || value > 4) return fail(ctx, SC_ERR_ARG, "first_pass_vars must be 0 (auto), 1, 2, 3 or 4 (the matrix-core pass at any size)");
-    ctx->first_pass_vars = (int)value;
-  } else if (k == "grid_pass") {
-    ctx->grid_pass = value ? 1 : 0;
-  } else if (k == "grid_log") {
-    if (value < 0 || value > 26) return fail(ctx, SC_ERR_ARG, "grid_log out of range (0..26)");
-    ctx->grid_log = (int)value;
-  } else if (k == "grid_max_vars") {
-    if (value < 1 || value > sc::kGridMaxVars) return fail(ctx, SC_ERR_ARG, "grid_max_vars must be 1..5");
-    ctx->grid_max_vars = (int)value;
-  } else if (k == "fold_dma") {
-    ctx->fold_dma = value ? 1 : 0;
-  } else if (k == "pipe32") {
-    ctx->pipe32 = value ? 1 : 0;
-  } else if (k == "pipe32_log") {
-    if (value < 11 || value > 40) return fail(ctx, SC_ERR_ARG, "pipe32_log out of range (11..40)");
-    ctx->pipe32_log = (int)value;
-  } else if (k == "gram_log") {
-    if (value < 0 || value > 40 || (value > 0 && value < 14)) return fail(ctx, SC_ERR_ARG, "gram_log must be 0 (never) or 14..40");
-    ctx->gram_log = (int)value;
-  } else if (k == "wfold_log") {
-    if (value < 0 || value > 40 || (value > 0 && value < 12)) return fail(ctx, SC_ERR_ARG, "wfold_log must be 0 (never) or 12..40");
-    ctx->wfold_log = (int)value;
-  } else if (k == "wfold5_min_log") {
-    if (value < 12 || value > 40) return fail(ctx, SC_ERR_ARG, "wfold5_min_log must be 12..40");
-    ctx->wfold5_min_log = (int)value;
-  } else if (k == "wfold_always") {
-    ctx->wfold_always = value ? 1 : 0;
-  } else if (k == "matmul_path") {
-    if (value < 0 || value > 2) return fail(ctx, SC_ERR_ARG, "matmul_path must be 0 (auto), 1 (int8 matrix cores) or 2 (VALU)");
-    ctx->matmul_path = (int)value;
-  } else if (k == "wfold_min_log") {
-    if (value < 12 || value > 40) return fail(ctx, SC_ERR_ARG, "wfold_min_log must be 12..40");
-    ctx->wfold_min_log = (int)value;
-  } else if (k == "host_tail_log") {
-    if (value < 0 || value > kTailLogMax) return fail(ctx, SC_ERR_ARG, "host_tail_log must be 0 (off) .. %d", kTailLogMax);
-    ctx->host_tail_log = (int)value;
-  } else if (k == "stat_reset") {
+  if (k == "stat_reset") {
     ctx->stat_wait_ns = ctx->stat_launch_ns = 0;
-  } else if (k == "grid_sharded") {
-    ctx->grid_sharded = value ? 1 : 0;
-  } else if (k == "grid_blocks") {
-    if (value < 0 || value > kWgMaxBlocks) return fail(ctx, SC_ERR_ARG, "grid_blocks must be 0..%d", kWgMaxBlocks);
-    ctx->grid_blocks = (int)value;
-  } else if (k == "tail_log") {
-    if (value < 0 || value > 40) return fail(ctx, SC_ERR_ARG, "tail_log out of range");
-    ctx->tail_log = (int)value;
-  } else if (k == "max_blocks") {
-    if (value < 1 || value > (int64_t)ctx->partial_rows) return fail(ctx, SC_ERR_ARG, "max_blocks out of range");
-    ctx->max_blocks = (int)value;
-  } else if (k == "time_kernels") {
-    ctx->time_kernels = value ? 1 : 0;  // recorded pairs stay in the ring until it fills or the totals are read
-  } else if (k == "use_mailbox") {
-    ctx->use_mailbox = value ? 1 : 0;
-  } else if (k == "arena_log") {
-    if (value < 4 || value > 26) return fail(ctx, SC_ERR_ARG, "arena_log must be in [4, 26]");
-    if (ctx->peer_region) return fail(ctx, SC_ERR_STATE, "arena_log must be set before sc_ctx_comm_peer_export");
-    ctx->arena_log = (int)value;
-  } else if (k == "peer_spin_ms") {
-    if (value < 1 || value > 600000) return fail(ctx, SC_ERR_ARG, "peer_spin_ms out of range");
-    ctx->peer_spin_ms = (int)value;
-  } else if (k == "rccl_timeout_ms") {
-    if (value < 1 || value > 3600000) return fail(ctx, SC_ERR_ARG, "rccl_timeout_ms out of range");
-    ctx->rccl_timeout_ms = (int)value;
-  } else if (k == "peer_connect_ms") {
-    if (value < 1 || value > 3600000) return fail(ctx, SC_ERR_ARG, "peer_connect_ms out of range");
-    ctx->peer_connect_ms = (int)value;
-  } else if (k == "dbg_delay_ms") {
-    if (value < 0 || value > 10000) return fail(ctx, SC_ERR_ARG, "dbg_delay_ms out of range");
-    ctx->dbg_delay_ms = (int)value;
-  } else if (k == "dbg_skip_tag") {
-    ctx->dbg_skip_tag = value ? 1 : 0;
-  } else if (k == "pool_contiguous") {
-    ctx->pool_contiguous = value ? 1 : 0;
-  } else if (k == "dbg_fold_grab") {
-    if (value < 0 || value > 16) return fail(ctx, SC_ERR_ARG, "dbg_fold_grab out of range");
-    ctx->dbg_fold_grab = (int)value;
-  } else if (k == "nt_load_log") {
-    ctx->nt_load_log = (int)value;
-  } else if (k == "nt_store_log") {
-    ctx->nt_store_log = (int)value;
-  } else {
-    return fail(ctx, SC_ERR_ARG, "unknown option '%s'", key);
+    return SC_OK;
   }
+  const OptionSpec* o = find_option(key);
+  if (!o) return fail(ctx, SC_ERR_ARG, "unknown option '%s'", key);
+  if (o->member == &sc_ctx::max_blocks && (value < 1 || value > (int64_t)ctx->partial_rows))
+    return fail(ctx, SC_ERR_ARG, "max_blocks must be 1..%zu", ctx->partial_rows);
+  if (!(o->flags & kOptBool) && (value < o->lo || value > o->hi) && !((o->flags & kOptOff) && value == 0))
+    return fail(ctx, SC_ERR_ARG, "%s must be %s%lld..%lld", key, (o->flags & kOptOff) ? "0 (never) or " : "", (long long)o->lo, (long long)o->hi);
+  if (o->member == &sc_ctx::arena_log && ctx->peer_region) return fail(ctx, SC_ERR_STATE, "arena_log must be set before sc_ctx_comm_peer_export");
+  ctx->*o->member = (o->flags & kOptBool) ? (value ? 1 : 0) : (int)value;
   return SC_OK;
 }
 
 extern "C" int sc_ctx_get_option(const sc_ctx* ctx, const char* key, int64_t* value) {
   if (!ctx || !key || !value) return SC_ERR_ARG;
-  std::string k(key);
-  if (k == "vars_per_pass") *value = ctx->vars_per_pass;
-  else if (k == "first_pass_vars") *value = ctx->first_pass_vars;
-  else if (k == "grid_pass") *value = ctx->grid_pass;
-  else if (k == "grid_log") *value = ctx->grid_log;
-  else if (k == "grid_max_vars") *value = ctx->grid_max_vars;
-  else if (k == "gram_log") *value = ctx->gram_log;
-  else if (k == "host_tail_log") *value = ctx->host_tail_log;
-  else if (k == "wfold_log") *value = ctx->wfold_log;
-  else if (k == "wfold_min_log") *value = ctx->wfold_min_log;
-  else if (k == "wfold_always") *value = ctx->wfold_always;
-  else if (k == "matmul_path") *value = ctx->matmul_path;
-  else if (k == "wfold5_min_log") *value = ctx->wfold5_min_log;
-  else if (k == "stat_wait_ns") *value = (int64_t)(is_multi(ctx) ? ctx->subs[0]->stat_wait_ns : ctx->stat_wait_ns);
+  const std::string k(key);
+  if (k == "stat_wait_ns") *value = (int64_t)(is_multi(ctx) ? ctx->subs[0]->stat_wait_ns : ctx->stat_wait_ns);
   else if (k == "stat_launch_ns") *value = (int64_t)(is_multi(ctx) ? ctx->subs[0]->stat_launch_ns : ctx->stat_launch_ns);
-  else if (k == "grid_sharded") *value = ctx->grid_sharded;
-  else if (k == "grid_blocks") *value = ctx->grid_blocks;
-  else if (k == "tail_log") *value = ctx->tail_log;
-  else if (k == "max_blocks") *value = ctx->max_blocks;
-  else if (k == "time_kernels") *value = ctx->time_kernels;
-  else if (k == "use_mailbox") *value = ctx->use_mailbox;
-  else if (k == "arena_log") *value = ctx->arena_log;
-  else if (k == "peer_spin_ms") *value = ctx->peer_spin_ms;
-  else if (k == "rccl_timeout_ms") *value = ctx->rccl_timeout_ms;
-  else if (k == "nt_load_log") *value = ctx->nt_load_log;
-  else if (k == "nt_store_log") *value = ctx->nt_store_log;
-  else if (k == "peer_connect_ms") *value = ctx->peer_connect_ms;
-  else if (k == "dbg_delay_ms") *value = ctx->dbg_delay_ms;
-  else if (k == "pool_contiguous") *value = ctx->pool_contiguous;
   else if (k == "transport") *value = (int64_t)ctx->transport;   // 0 none, 1 RCCL, 2 host callbacks, 3 peer, 4 local (a multi-device handle and its shards)
   else if (k == "n_devices") *value = is_multi(ctx) ? (int64_t)ctx->subs.size() : 1;
   else if (k == "comm_nranks") {
@@ -295,8 +242,11 @@ extern "C" int sc_ctx_get_option(const sc_ctx* ctx, const char* key, int64_t* va
         return fail(ctx, SC_ERR_RCCL, "ncclCommCount failed");
     }
     *value = n;
+  } else if (const OptionSpec* o = find_option(key)) {
+    *value = ctx->*o->member;
+  } else {
+    return fail(ctx, SC_ERR_ARG, "unknown option '%s'", key);
   }
-  else return fail(ctx, SC_ERR_ARG, "unknown option '%s'", key);
   return SC_OK;
 }
 

@@ -169,14 +169,7 @@ extern "C" int sc_gkr_w_to_evaluations(sc_ctx* ctx, const sc_table* add, const s
   pool_release(ctx, add_full);   // stream-ordered
   pool_release(ctx, mul_full);
   if (rc != SC_OK) return rc;
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = sync_stream(ctx);
-  if (e != hipSuccess) {
-    sc_table_free(ctx, t);
-    return fail(ctx, SC_ERR_HIP, "gkr to_evaluations: %s", hipGetErrorString(e));
-  }
-  *out = t;
-  return SC_OK;
+  return table_done(ctx, t, hipGetLastError(), "gkr to_evaluations", out);
 }
 
 extern "C" int sc_gkr_w_round_sums(sc_ctx* ctx, const sc_table* add, const sc_table* mul, const sc_table* w_b,

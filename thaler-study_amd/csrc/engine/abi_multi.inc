@@ -75,7 +75,7 @@ static int multi_set_option(sc_ctx* m, const char* key, int64_t value) {
   SC_TRY(multi_enter(m));
   const std::string k(key);
   if (k == "use_mailbox" && !value) return fail(m, SC_ERR_UNSUPPORTED, "a multi-device handle adds its shards' sums from their mailboxes");
-  if (k == "arena_log" || k == "peer_spin_ms" || k == "peer_connect_ms" || k == "dbg_delay_ms" || k == "dbg_skip_tag")
+  if (const OptionSpec* o = find_option(key); o && (o->flags & kOptPeer))
     return fail(m, SC_ERR_UNSUPPORTED, "'%s' belongs to the peer transport; a multi-device handle has no exchange between kernels", key);
   for (sc_ctx* s : m->subs) {
     const int rc = sc_ctx_set_option(s, key, value);

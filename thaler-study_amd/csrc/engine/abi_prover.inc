@@ -453,7 +453,7 @@ int host_tail(sc_prover* pr, int kf) {
   const int n = (int)pr->sh.size();
   const size_t in_len = (size_t)1 << pr->cur_log, out_len = in_len >> kf;
   if (pr->cur_log < kf) return fail(m, SC_ERR_STATE, "host tail: 2^%d entries cannot fold %d challenges", pr->cur_log, kf);
-  const sc::GridW gw = make_grid_weights(m, pr->pending.data(), kf);
+  const sc::GridW gw = make_weights<sc::GridW>(m, pr->pending.data(), kf);
   try {   // (within what sc_prover_create reserved, unless an option raised the hand-over size since)
     pr->ha.assign(out_len * (size_t)n, 0);
     pr->hb.assign(out_len * (size_t)n, 0);
@@ -556,8 +556,7 @@ int prover_pass(sc_prover* pr, size_t j) {
     pr->sharded = false;
   }
   const bool by_grid = plan.kind == PassPlan::kGridPass || plan.kind == PassPlan::kGramPass || plan.kind == PassPlan::kWfoldPass;   // (they leave their cells like a grid pass)
-  int cells = 1;
-  for (int i = 0; i < ks; ++i) cells *= 3;
+  const int cells = pow3(ks);
 
   if (is_multi(ctx)) {
     // every shard launches on its own thread and fetches its own sums; this thread adds them: the exchange step
@@ -633,8 +632,7 @@ int prover_pass(sc_prover* pr, size_t j) {
 // after it are summed over {0,1}.
 void prover_answer(const sc_prover* pr, size_t j, u64 e[3]) {
   HostField hf(pr->ctx->fp);
-  int total = 1;
-  for (int i = 0; i < pr->cache_ks; ++i) total *= 3;
+  const int total = pow3(pr->cache_ks);
   const int known = (int)(j - pr->cache_round);  // == pr->pending.size()
   u64* g = pr->G;
   if (pr->g_known < 0 || pr->g_known > known) {

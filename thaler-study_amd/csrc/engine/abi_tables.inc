@@ -11,14 +11,7 @@ extern "C" int sc_table_upload(sc_ctx* ctx, const uint64_t* host, size_t len, sc
   SC_TRY(set_device(ctx));
   sc_table* t = nullptr;
   SC_TRY(new_table(ctx, len, &t));
-  hipError_t e = hipMemcpyAsync(t->d, host, len * sizeof(u64), hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) e = sync_stream(ctx);
-  if (e != hipSuccess) {
-    sc_table_free(ctx, t);
-    return fail(ctx, SC_ERR_HIP, "upload: %s", hipGetErrorString(e));
-  }
-  *out = t;
-  return SC_OK;
+  return table_done(ctx, t, hipMemcpyAsync(t->d, host, len * sizeof(u64), hipMemcpyHostToDevice, ctx->stream), "upload", out);
 }
 
 // A table over device memory the CALLER owns (built by its own kernels, another library, a virtual-memory mapping it
@@ -53,14 +46,7 @@ extern "C" int sc_table_generate(sc_ctx* ctx, uint64_t seed, uint64_t start, siz
   int grid = grid_for_wide(ctx, len);
   SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::generate_kernel<F>), dim3(grid), dim3(sc::kBlock), 0, ctx->stream,
                                                   f, (u64)seed, (u64)start, len, t->d));
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = sync_stream(ctx);
-  if (e != hipSuccess) {
-    sc_table_free(ctx, t);
-    return fail(ctx, SC_ERR_HIP, "generate: %s", hipGetErrorString(e));
-  }
-  *out = t;
-  return SC_OK;
+  return table_done(ctx, t, hipGetLastError(), "generate", out);
 }
 
 extern "C" int sc_table_clone(sc_ctx* ctx, const sc_table* t, sc_table** out) {
@@ -168,12 +154,9 @@ static int evaluate_local(sc_ctx* ctx, const u64* d, size_t len, const u64* pt_l
   const sc::PassOut out = next_pass_out(ctx, across, challenge_digest(pt_le, std::min(nv, 3), 0, nv), from_mailbox);
   const int nt = nv >= ctx->nt_load_log ? 1 : 0;
   SC_TRY(timer_begin(ctx, SC_KIND_EVALUATE, nv, 0, nv, (u64)8 << nv, 0));
-  if (nt)
-    SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::evaluate_kernel<F, true>), dim3(grid), dim3(threads), 0, ctx->stream,
-                                                    f, d, nv, rv, ta, chunk_log, w_extra, out));
-  else
-    SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::evaluate_kernel<F, false>), dim3(grid), dim3(threads), 0, ctx->stream,
-                                                    f, d, nv, rv, ta, chunk_log, w_extra, out));
+  SC_DISPATCH_FIELD(ctx, F, f, with_bool(nt, [&](auto NT) {
+    hipLaunchKernelGGL((sc::evaluate_kernel<F, NT>), dim3(grid), dim3(threads), 0, ctx->stream, f, d, nv, rv, ta, chunk_log, w_extra, out);
+  }));
   SC_TRY(commit_pass_out(ctx, out, grid));
   SC_TRY(timer_end(ctx));
   return SC_OK;
@@ -348,14 +331,7 @@ extern "C" int sc_table_relabel(sc_ctx* ctx, const sc_table* in, size_t a, size_
   int grid = grid_for_wide(ctx, in->len);
   hipLaunchKernelGGL(sc::relabel_kernel, dim3(grid), dim3(sc::kBlock), 0, ctx->stream, (const u64*)in->d, t->d, in->len,
                      (unsigned)a, (unsigned)b, (unsigned)k);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = sync_stream(ctx);
-  if (e != hipSuccess) {
-    sc_table_free(ctx, t);
-    return fail(ctx, SC_ERR_HIP, "relabel: %s", hipGetErrorString(e));
-  }
-  *out = t;
-  return SC_OK;
+  return table_done(ctx, t, hipGetLastError(), "relabel", out);
 }
 
 // =====================================================================================
@@ -466,14 +442,7 @@ extern "C" int sc_prod2_to_evaluations(sc_ctx* ctx, const sc_table* a, const sc_
   int grid = grid_for(ctx, a->len);
   SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::mul_kernel<F>), dim3(grid), dim3(sc::kBlock), 0, ctx->stream, f,
                                                   (const u64*)a->d, (const u64*)b->d, t->d, a->len));
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = sync_stream(ctx);
-  if (e != hipSuccess) {
-    sc_table_free(ctx, t);
-    return fail(ctx, SC_ERR_HIP, "to_evaluations: %s", hipGetErrorString(e));
-  }
-  *out = t;
-  return SC_OK;
+  return table_done(ctx, t, hipGetLastError(), "to_evaluations", out);
 }
 
 // Round sums of (a, b) as they are (no fold); handles the degenerate 1-entry tables.

@@ -46,14 +46,7 @@ extern "C" int sc_tri_to_evaluations(sc_ctx* ctx, const sc_table* f1, const sc_t
   SC_TRY(new_table(ctx, total, &t));
   SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::tri_to_evaluations_kernel<F>), dim3(grid_for_wide(ctx, total)),
                                                   dim3(sc::kBlock), 0, ctx->stream, f, v.f1, v.f2, v.f3, v.xv, v.yv, v.zv, t->d));
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = sync_stream(ctx);
-  if (e != hipSuccess) {
-    sc_table_free(ctx, t);
-    return fail(ctx, SC_ERR_HIP, "triangle to_evaluations: %s", hipGetErrorString(e));
-  }
-  *out = t;
-  return SC_OK;
+  return table_done(ctx, t, hipGetLastError(), "triangle to_evaluations", out);
 }
 
 extern "C" int sc_tri_round_sums(sc_ctx* ctx, const sc_table* f1, const sc_table* f2, const sc_table* f3, size_t var_len,

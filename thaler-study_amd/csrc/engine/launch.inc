@@ -19,38 +19,51 @@ namespace {
     }                                          \
   } while (0)
 
-// w[c] = prod_j (bit_j(c) ? r[j] : 1 - r[j]), c < 2^kf   (kernels.hpp: FoldW)
-sc::FoldW make_fold_weights(const sc_ctx* ctx, const u64* r, int kf) {
-  HostField hf(ctx->fp);
-  sc::FoldW fw;
-  for (int c = 0; c < 16; ++c) fw.w[c] = 0;
-  fw.w[0] = hf.one();
-  for (int j = 0; j < kf; ++j) {
-    const int half = 1 << j;
-    for (int c = half - 1; c >= 0; --c) {
-      const u64 base = fw.w[c];
-      fw.w[c + half] = hf.mul(base, r[j]);
-      fw.w[c] = hf.mul(base, hf.sub(hf.one(), r[j]));
-    }
-  }
-  return fw;
+// The one way a run-time choice (a streaming flag, ks, a (kf, ks) shape) becomes a template argument of a kernel:
+// fn(std::integral_constant<int, V>) for the V of Vs equal to v.  Only the listed values are instantiated; any other v calls
+// nothing.
+template <int V>
+using IntC = std::integral_constant<int, V>;
+template <int... Vs, class Fn>
+void with_const(int v, Fn&& fn) {
+  (void)((v == Vs && (fn(IntC<Vs>{}), true)) || ...);
+}
+template <class Fn>
+void with_bool(bool b, Fn&& fn) {
+  if (b) fn(std::true_type{});
+  else fn(std::false_type{});
+}
+// fn(KF, KS) for the (kf, ks) shapes pass_kernel is instantiated for (launch_pass admits exactly these)
+template <class Fn>
+void with_pass_shape(int kf, int ks, Fn&& fn) {
+  with_const<0 * 4 + 1, 0 * 4 + 2, 0 * 4 + 3, 1 * 4 + 1, 1 * 4 + 2, 2 * 4 + 1, 2 * 4 + 2, 3 * 4 + 1, 3 * 4 + 2, 4 * 4 + 2>(
+      kf * 4 + ks, [&](auto c) { fn(IntC<c / 4>{}, IntC<c % 4>{}); });
 }
 
-// the same for the passes on the smallest tables (kernels.hpp: GridW), kf <= 5
-sc::GridW make_grid_weights(const sc_ctx* ctx, const u64* r, int kf) {
+// w[c] = prod_j (bit_j(c) ? r[j] : 1 - r[j]), c < 2^kf: the weights of a kf-challenge fold, as sc::FoldW (kernels.hpp, kf <= 4)
+// or sc::GridW (kernels/grid_pass.hpp, kf <= 5)
+template <class W>
+W make_weights(const sc_ctx* ctx, const u64* r, int kf) {
   HostField hf(ctx->fp);
-  sc::GridW gw;
-  for (int c = 0; c < (1 << sc::kGridMaxVars); ++c) gw.w[c] = 0;
-  gw.w[0] = hf.one();
+  W out;
+  for (u64& w : out.w) w = 0;
+  out.w[0] = hf.one();
   for (int j = 0; j < kf; ++j) {
     const int half = 1 << j;
     for (int c = half - 1; c >= 0; --c) {
-      const u64 base = gw.w[c];
-      gw.w[c + half] = hf.mul(base, r[j]);
-      gw.w[c] = hf.mul(base, hf.sub(hf.one(), r[j]));
+      const u64 base = out.w[c];
+      out.w[c + half] = hf.mul(base, r[j]);
+      out.w[c] = hf.mul(base, hf.sub(hf.one(), r[j]));
     }
   }
-  return gw;
+  return out;
+}
+
+// 3^k: the cells of a pass that serves k rounds
+inline int pow3(int k) {
+  int c = 1;
+  while (k-- > 0) c *= 3;
+  return c;
 }
 
 // (H(0), H(1), H(inf)) -> H(2) = 2 H(1) - H(0) + 2 H(inf)   (H quadratic, inf = leading coefficient)
@@ -102,61 +115,41 @@ int timer_end(sc_ctx* ctx) {
   return SC_OK;
 }
 
+// The resident grid of a kernel at a block size: blocks per CU x CUs, asked once per context (prewarm asks ahead of the first
+// proof); `fallback` where the runtime cannot tell.  The callers cap it as their launches need.
+int resident_grid(sc_ctx* ctx, const void* fn, int block, int fallback) {
+  int& slot = ctx->resident_grid[fn];
+  if (slot == 0) {
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, block, 0) != hipSuccess || per_cu < 1) {
+      (void)hipGetLastError();
+      slot = fallback;
+    } else {
+      slot = per_cu * ctx->num_cus;
+    }
+  }
+  return slot;
+}
+template <class K>
+const void* kernel_ptr(K* k) {
+  return reinterpret_cast<const void*>(k);
+}
+
 // A pass is launched with at most as many blocks as are resident at once (occupancy x CUs) and
 // grid-strides over the rest: with 4x more blocks than fit (the old fixed cap of 2048) the chip
 // drains and refills between block generations and the last block has 4x more partial sums to
 // reduce - 7 % of an n = 28 proof (measured with the max_blocks option: 2048 -> 2.31 ms,
 // 1024 -> 2.20, 512 -> 2.13, 256 -> 2.27).
-template <class F>
-int pass_resident_blocks_t(sc_ctx* ctx, int kf, int ks) {
+int pass_resident_blocks(sc_ctx* ctx, int kf, int ks) {
   const void* fn = nullptr;
-#define SC_FN(KF, KS) fn = reinterpret_cast<const void*>(&sc::pass_kernel<F, KF, KS, 1>)
-  switch (kf * 4 + ks) {
-    case 0 * 4 + 1: SC_FN(0, 1); break;
-    case 0 * 4 + 2: SC_FN(0, 2); break;
-    case 0 * 4 + 3: SC_FN(0, 3); break;
-    case 1 * 4 + 1: SC_FN(1, 1); break;
-    case 1 * 4 + 2: SC_FN(1, 2); break;
-    case 2 * 4 + 1: SC_FN(2, 1); break;
-    case 2 * 4 + 2: SC_FN(2, 2); break;
-    case 3 * 4 + 1: SC_FN(3, 1); break;
-    case 3 * 4 + 2: SC_FN(3, 2); break;
-    case 4 * 4 + 2: SC_FN(4, 2); break;
-    default: break;
-  }
-#undef SC_FN
-  int per_cu = 0;
-  if (!fn || hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, sc::pass_block_threads(kf, ks), 0) != hipSuccess || per_cu < 1) {
-    (void)hipGetLastError();
-    return ctx->max_blocks;
-  }
-  return per_cu * ctx->num_cus;
+  SC_DISPATCH_FIELD(ctx, F, f, (void)f; with_pass_shape(kf, ks, [&](auto KF, auto KS) { fn = kernel_ptr(&sc::pass_kernel<F, KF, KS, 1>); }));
+  return fn ? resident_grid(ctx, fn, sc::pass_block_threads(kf, ks), ctx->max_blocks) : ctx->max_blocks;
 }
 
 // the pipelined whole-tile form of the three-variable fold (pass_kernel<F, 3, 2, NT | 4>): its own block size and occupancy
 int pipe32_resident_blocks(sc_ctx* ctx) {
-  if (ctx->pipe32_blocks == 0) {
-    int per_cu = 0;
-    const void* fn = ctx->gold ? reinterpret_cast<const void*>(&sc::pass_kernel<sc::GoldilocksMont, 3, 2, 5>)
-                               : reinterpret_cast<const void*>(&sc::pass_kernel<sc::MontGeneric, 3, 2, 5>);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, sc::kPipe32Threads, 0) != hipSuccess || per_cu < 1) {
-      (void)hipGetLastError();
-      per_cu = 1;
-    }
-    ctx->pipe32_blocks = per_cu * ctx->num_cus;
-  }
-  return ctx->pipe32_blocks;
-}
-
-int pass_resident_blocks(sc_ctx* ctx, int kf, int ks) {
-  const int fi = ctx->gold ? 1 : 0;
-  int& slot = ctx->resident_blocks[fi][kf][ks];
-  if (slot == 0) {
-    int v = 0;
-    SC_DISPATCH_FIELD(ctx, F, f, { (void)f; v = pass_resident_blocks_t<F>(ctx, kf, ks); });
-    slot = v > 0 ? v : ctx->max_blocks;
-  }
-  return slot;
+  const void* fn = ctx->gold ? kernel_ptr(&sc::pass_kernel<sc::GoldilocksMont, 3, 2, 5>) : kernel_ptr(&sc::pass_kernel<sc::MontGeneric, 3, 2, 5>);
+  return resident_grid(ctx, fn, sc::kPipe32Threads, ctx->num_cus);
 }
 
 template <class F>
@@ -165,47 +158,20 @@ void launch_pass_t(sc_ctx* ctx, const F& f, int kf, int ks, const u64* A, const 
   dim3 g(grid), b(sc::pass_block_threads(kf, ks, pipe32 ? 4 : 0));
   hipStream_t s = ctx->stream;
   // streaming hints are compile-time (kernels.hpp, ld16/st16): 0 = cached, 1 = stream the inputs,
-  // 3 = stream inputs and outputs
+  // 3 = stream inputs and outputs; FORM adds 4 (the pipelined form) or 8 (the LDS-DMA form)
   const int nt = (log_in >= ctx->nt_load_log ? 1 : 0) | ((kf > 0 && (log_in - kf) >= ctx->nt_store_log) ? 2 : 0);
-#define SC_PASS(KF, KS)                                                                                            \
-  do {                                                                                                             \
-    if (nt == 3)                                                                                                   \
-      hipLaunchKernelGGL((sc::pass_kernel<F, KF, KS, 3>), g, b, 0, s, f, A, B, A2, B2, fw, n_units, out);          \
-    else if (nt & 1)                                                                                               \
-      hipLaunchKernelGGL((sc::pass_kernel<F, KF, KS, 1>), g, b, 0, s, f, A, B, A2, B2, fw, n_units, out);          \
-    else                                                                                                           \
-      hipLaunchKernelGGL((sc::pass_kernel<F, KF, KS, 0>), g, b, 0, s, f, A, B, A2, B2, fw, n_units, out);          \
-  } while (0)
+  auto go = [&](auto KF, auto KS, auto FORM) {
+    with_const<3, 1, 0>(nt == 3 ? 3 : nt & 1, [&](auto NT) {
+      hipLaunchKernelGGL((sc::pass_kernel<F, KF, KS, FORM | NT>), g, b, 0, s, f, A, B, A2, B2, fw, n_units, out);
+    });
+  };
   if constexpr (std::is_same<F, sc::GoldilocksMont>::value) {
     // the LDS-DMA form of the four-variable fold (whole tiles: launch_pass checks).  Goldilocks only: with the generic field's
     // constants in registers the form does not fit 256 VGPRs (20 bytes of scratch), and that field keeps the register-staged one
-    if (kf == 4 && ks == 2 && ctx->fold_dma) {
-      if (nt == 3) hipLaunchKernelGGL((sc::pass_kernel<F, 4, 2, 11>), g, b, 0, s, f, A, B, A2, B2, fw, n_units, out);
-      else if (nt & 1) hipLaunchKernelGGL((sc::pass_kernel<F, 4, 2, 9>), g, b, 0, s, f, A, B, A2, B2, fw, n_units, out);
-      else hipLaunchKernelGGL((sc::pass_kernel<F, 4, 2, 8>), g, b, 0, s, f, A, B, A2, B2, fw, n_units, out);
-      return;
-    }
+    if (kf == 4 && ks == 2 && ctx->fold_dma) return go(IntC<4>{}, IntC<2>{}, IntC<8>{});
   }
-  if (pipe32) {   // (kf, ks) = (3, 2), whole tiles
-    if (nt == 3) hipLaunchKernelGGL((sc::pass_kernel<F, 3, 2, 7>), g, b, 0, s, f, A, B, A2, B2, fw, n_units, out);
-    else if (nt & 1) hipLaunchKernelGGL((sc::pass_kernel<F, 3, 2, 5>), g, b, 0, s, f, A, B, A2, B2, fw, n_units, out);
-    else hipLaunchKernelGGL((sc::pass_kernel<F, 3, 2, 4>), g, b, 0, s, f, A, B, A2, B2, fw, n_units, out);
-    return;
-  }
-  switch (kf * 4 + ks) {
-    case 0 * 4 + 1: SC_PASS(0, 1); break;
-    case 0 * 4 + 2: SC_PASS(0, 2); break;
-    case 0 * 4 + 3: SC_PASS(0, 3); break;
-    case 1 * 4 + 1: SC_PASS(1, 1); break;
-    case 1 * 4 + 2: SC_PASS(1, 2); break;
-    case 2 * 4 + 1: SC_PASS(2, 1); break;
-    case 2 * 4 + 2: SC_PASS(2, 2); break;
-    case 3 * 4 + 1: SC_PASS(3, 1); break;
-    case 3 * 4 + 2: SC_PASS(3, 2); break;
-    case 4 * 4 + 2: SC_PASS(4, 2); break;
-    default: break;
-  }
-#undef SC_PASS
+  if (pipe32) return go(IntC<3>{}, IntC<2>{}, IntC<4>{});   // (kf, ks) = (3, 2), whole tiles
+  with_pass_shape(kf, ks, [&](auto KF, auto KS) { go(KF, KS, IntC<0>{}); });
 }
 
 constexpr size_t kInboxRegionWords = 2 * (size_t)sc::kMaxPeers * sc::kInboxWords;   // two parities
@@ -253,8 +219,69 @@ inline void commit_peer(sc_ctx* ctx) {
   ctx->xchg_next = 0;
 }
 
-sc::PassOut next_pass_out(sc_ctx* ctx, bool across_ranks = false, unsigned digest = 0, bool* from_mailbox = nullptr);
-int commit_pass_out(sc_ctx* ctx, const sc::PassOut& out, int grid);
+// PassOut of the next launch that ends in finish_pass.  across_ranks: its sums are summed over the ranks - inside the
+// kernel on the peer transport (digest = what the ranks must agree on), by a collective on the stream for RCCL (the
+// limbs stay in d_sums), by the host for a host transport.  *from_mailbox tells collect_sums where the limbs are.
+// Nothing is committed here: call commit_pass_out() once the launch is known to be in the stream.
+sc::PassOut next_pass_out(sc_ctx* ctx, bool across_ranks = false, unsigned digest = 0, bool* from_mailbox = nullptr) {
+  const bool peer = across_ranks && ctx->transport == Transport::kPeer;
+  const bool mailbox = (ctx->use_mailbox || peer) && !(across_ranks && ctx->transport == Transport::kRccl);
+  sc::PassOut out;
+  out.partials = ctx->d_partials;
+  out.n_rows = (int)ctx->partial_rows;
+  out.ticket = ctx->d_ticket;
+  out.ticket_base = ctx->ticket_base;
+  out.sums_dev = ctx->d_sums;
+  out.mailbox = mailbox ? ctx->d_mailbox : nullptr;
+  out.seq = mailbox ? ctx->mailbox_seq + 1 : 0;
+  if (peer) fill_peer(ctx, out.px, digest);
+  if (from_mailbox) *from_mailbox = mailbox;
+  return out;
+}
+int commit_pass_out(sc_ctx* ctx, const sc::PassOut& out, int grid) {
+  SC_HIP(ctx, hipGetLastError());
+  if (out.px.world > 0) commit_peer(ctx);
+  if (out.mailbox) ctx->mailbox_seq += 1;
+  if (grid > 1) ctx->ticket_base += (unsigned)grid;
+  return SC_OK;
+}
+
+// WgOut of the next launch that leaves its cells in the wide mailbox (collect_grid).  tables: the kernel hands its partial
+// rows over through the grid-pass partials, group rows and tickets; host_out: its folded tables go to the pinned tail buffer.
+// across_ranks: the peer transport exchanges the cells inside the kernel (digest: salted per kind of pass), RCCL sums their
+// limbs behind it (commit_wide_out), a host transport gets this rank's residues and sums them itself.  Nothing is committed
+// here: call commit_wide_out() right after the launch.
+sc::WgOut next_wide_out(sc_ctx* ctx, bool across_ranks, unsigned digest, bool tables, bool host_out) {
+  sc::WgOut wo;
+  wo.partials = tables ? ctx->d_wg_partials : nullptr;
+  wo.group_rows = tables ? ctx->d_wg_groups : nullptr;
+  wo.tickets = tables ? ctx->d_wg_tickets : nullptr;
+  wo.mailbox = ctx->d_mailbox;
+  wo.seq = ctx->mailbox_seq + 1;
+  wo.limbs_dev = across_ranks && ctx->transport == Transport::kRccl ? ctx->d_sums : nullptr;
+  wo.host_out = host_out ? 1 : 0;
+  if (across_ranks && ctx->transport == Transport::kPeer) fill_peer(ctx, wo.px, digest);
+  return wo;
+}
+// the launch is in the stream: only now do the exchange tag and the mailbox sequence move.  On RCCL the cells' 2 x cells limbs
+// are summed on the stream behind the kernel and a small kernel hands the totals to the mailbox under the launch's sequence word.
+int commit_wide_out(sc_ctx* ctx, const sc::WgOut& wo, int cells) {
+  SC_HIP(ctx, hipGetLastError());
+  if (wo.px.world > 0) commit_peer(ctx);
+  SC_TRY(timer_end(ctx));
+  if (wo.limbs_dev) {
+    ncclResult_t nr = g_rccl.AllReduce(ctx->d_sums, ctx->d_sums, 2 * (size_t)cells, ncclUint64, ncclSum, ctx->comm, ctx->stream);
+    if (nr != ncclSuccess) return fail(ctx, SC_ERR_RCCL, "ncclAllReduce: %s", g_rccl.GetErrorString ? g_rccl.GetErrorString(nr) : "?");
+    hipLaunchKernelGGL(sc::mailbox_copy_wide_kernel, dim3(1), dim3(sc::kBlock), 0, ctx->stream, (const u64*)ctx->d_sums, 2 * cells,
+                       ctx->d_mailbox, wo.seq);
+    SC_HIP(ctx, hipGetLastError());
+  }
+  ctx->mailbox_seq += 1;
+  return SC_OK;
+}
+
+// the pinned tail buffer: a pass's outputs there are read by the host (option "host_tail_log")
+bool in_tail(const sc_ctx* ctx, const u64* p) { return p && ctx->d_tail && p >= ctx->d_tail && p < ctx->d_tail + kTailSlots * kTailSlotWords; }
 
 // Launch one pass over tables of 2^log_in entries.  The 2*NS split limbs end up in the
 // host mailbox (*from_mailbox = true; wait with collect_sums) or in ctx->d_sums when they
@@ -263,7 +290,7 @@ int launch_pass(sc_ctx* ctx, int kf, int ks, const u64* A, const u64* B, u64* A2
                 int log_in, bool across_ranks, bool* from_mailbox) {
   if (kf < 0 || kf > 4 || ks < 1 || ks > 3 || (ks == 3 && kf != 0) || (kf == 4 && (ks != 2 || log_in < 12)) || log_in < kf + ks)
     return fail(ctx, SC_ERR_ARG, "launch_pass: kf=%d ks=%d log_in=%d", kf, ks, log_in);
-  const sc::FoldW fw = make_fold_weights(ctx, r, kf);
+  const sc::FoldW fw = make_weights<sc::FoldW>(ctx, r, kf);
   size_t n_units = (size_t)1 << (log_in - kf - ks);
   // the three-variable fold on whole tiles of a large table: the pipelined form (kernels/pass.hpp)
   const bool pipe32 = kf == 3 && ks == 2 && ctx->pipe32 && n_units % sc::kWave == 0 && log_in >= ctx->pipe32_log;
@@ -275,8 +302,7 @@ int launch_pass(sc_ctx* ctx, int kf, int ks, const u64* A, const u64* B, u64* A2
   // sequence word leaves, nobody else has stored.  The planner hands over from pass_kernel only at <= 2^kTailSmallLog entries;
   // this is where that invariant is checked instead of assumed (ADVICE r05): anything larger must go through wgrid_pass_kernel,
   // whose hand-over is write-through at system scope (WgOut::host_out)
-  if (kf > 0 && A2 && ctx->d_tail && A2 >= ctx->d_tail && A2 < ctx->d_tail + kTailSlots * kTailSlotWords &&
-      (grid != 1 || ((size_t)1 << (log_in - kf)) > (size_t)sc::kWave))
+  if (kf > 0 && in_tail(ctx, A2) && (grid != 1 || ((size_t)1 << (log_in - kf)) > (size_t)sc::kWave))
     return fail(ctx, SC_ERR_STATE, "launch_pass: a pass_kernel launch of %d blocks would hand 2^%d-entry tables to the host with plain stores", grid,
                 log_in - kf);
   const sc::PassOut out = next_pass_out(ctx, across_ranks, challenge_digest(r, kf, ks, log_in), from_mailbox);
@@ -304,138 +330,63 @@ int check_exchange(sc_ctx* ctx, const char* what) {
 }
 
 // One pass by wgrid_pass_kernel: folds kf <= 5 pending challenges of tables of 2^log_in entries and leaves the 3^ks
-// cells of the next ks <= 5 rounds in the wide mailbox (collect_grid).  Its counters rest at zero.  Sharded passes:
-// the peer transport exchanges the cells inside the kernel; RCCL sums their limbs on the stream behind the kernel and
-// a small kernel hands the totals to the mailbox; a host transport gets this rank's residues and sums them itself.
+// cells of the next ks <= 5 rounds in the wide mailbox (collect_grid).  Its counters rest at zero.  Sharded passes hand
+// their cells over as next_wide_out describes.
 int launch_grid_pass(sc_ctx* ctx, int kf, int ks, const u64* A, const u64* B, u64* A2, u64* B2, const u64* r, int log_in, bool across_ranks) {
   if (kf < 0 || kf > sc::kGridMaxVars || ks < 1 || ks > sc::kGridMaxVars || log_in < kf + ks)
     return fail(ctx, SC_ERR_ARG, "launch_grid_pass: kf=%d ks=%d log_in=%d", kf, ks, log_in);
   if (!ctx->use_mailbox) return fail(ctx, SC_ERR_STATE, "launch_grid_pass needs the host mailbox");
-  const sc::GridW gw = make_grid_weights(ctx, r, kf);
+  const sc::GridW gw = make_weights<sc::GridW>(ctx, r, kf);
   const size_t n_out = (size_t)1 << (log_in - kf);
-  if (ctx->wgrid_blocks == 0) {
-    int per_cu = 0;
-    const void* fn = ctx->gold ? reinterpret_cast<const void*>(&sc::wgrid_pass_kernel<sc::GoldilocksMont, 5, false>)
-                               : reinterpret_cast<const void*>(&sc::wgrid_pass_kernel<sc::MontGeneric, 5, false>);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, sc::kBlock, 0) != hipSuccess || per_cu < 1) {
-      (void)hipGetLastError();
-      per_cu = 2;
-    }
-    ctx->wgrid_blocks = std::min(per_cu * ctx->num_cus, kWgMaxBlocks);
-  }
+  const int resident = std::min(resident_grid(ctx, ctx->gold ? kernel_ptr(&sc::wgrid_pass_kernel<sc::GoldilocksMont, 5, false>)
+                                                             : kernel_ptr(&sc::wgrid_pass_kernel<sc::MontGeneric, 5, false>),
+                                              sc::kBlock, 2 * ctx->num_cus),
+                                kWgMaxBlocks);
   constexpr size_t kWaves = sc::kBlock / sc::kWave;
   const size_t n_iter = (n_out + sc::kWgEntries - 1) / sc::kWgEntries;   // one per wave
-  const size_t cap = ctx->grid_blocks > 0 ? (size_t)std::min(ctx->grid_blocks, ctx->wgrid_blocks) : (size_t)ctx->wgrid_blocks;
+  const size_t cap = ctx->grid_blocks > 0 ? (size_t)std::min(ctx->grid_blocks, resident) : (size_t)resident;
   const int grid = (int)std::max<size_t>(1, std::min<size_t>((n_iter + kWaves - 1) / kWaves, cap));
-  const bool peer = across_ranks && ctx->transport == Transport::kPeer;
-  const bool rccl = across_ranks && ctx->transport == Transport::kRccl;
-  int cells = 1;
-  for (int i = 0; i < ks; ++i) cells *= 3;
-  sc::WgOut wo;
-  wo.partials = ctx->d_wg_partials;
-  wo.group_rows = ctx->d_wg_groups;
-  wo.tickets = ctx->d_wg_tickets;
-  wo.mailbox = ctx->d_mailbox;
-  wo.seq = ctx->mailbox_seq + 1;
-  wo.limbs_dev = rccl ? ctx->d_sums : nullptr;
   // outputs in the pinned tail buffer (the host finishes from them): stored write-through at system scope (WgOut::host_out)
-  wo.host_out = (A2 && ctx->d_tail && A2 >= ctx->d_tail && A2 < ctx->d_tail + kTailSlots * kTailSlotWords) ? 1 : 0;
-  if (peer) fill_peer(ctx, wo.px, challenge_digest(r, kf, ks, log_in));
+  const sc::WgOut wo = next_wide_out(ctx, across_ranks, challenge_digest(r, kf, ks, log_in), true, in_tail(ctx, A2));
   SC_TRY(timer_begin(ctx, SC_KIND_GRID_PASS, kf, ks, log_in, (u64)16 << log_in, kf > 0 ? (u64)16 << (log_in - kf) : 0));
   // the prefetching instantiation: fan-ins 0 and 2 on tables that give a wave more than one iteration (kernels.hpp)
   const bool pf = (kf == 0 || kf == 2) && n_iter > (size_t)grid * kWaves;
-#define SC_WG(KS)                                                                                                                       \
-  do {                                                                                                                                  \
-    if (pf) hipLaunchKernelGGL((sc::wgrid_pass_kernel<F, KS, true>), dim3(grid), dim3(sc::kBlock), 0, ctx->stream, f, A, B, A2, B2, gw, kf, n_out, wo); \
-    else hipLaunchKernelGGL((sc::wgrid_pass_kernel<F, KS, false>), dim3(grid), dim3(sc::kBlock), 0, ctx->stream, f, A, B, A2, B2, gw, kf, n_out, wo);   \
-  } while (0)
-  SC_DISPATCH_FIELD(ctx, F, f, {
-    switch (ks) {
-      case 1: SC_WG(1); break;
-      case 2: SC_WG(2); break;
-      case 3: SC_WG(3); break;
-      case 4: SC_WG(4); break;
-      default: SC_WG(5); break;
-    }
-  });
-#undef SC_WG
-  SC_HIP(ctx, hipGetLastError());
-  if (peer) commit_peer(ctx);
-  SC_TRY(timer_end(ctx));
-  if (rccl) {
-    ncclResult_t nr = g_rccl.AllReduce(ctx->d_sums, ctx->d_sums, 2 * (size_t)cells, ncclUint64, ncclSum, ctx->comm, ctx->stream);
-    if (nr != ncclSuccess) return fail(ctx, SC_ERR_RCCL, "ncclAllReduce: %s", g_rccl.GetErrorString ? g_rccl.GetErrorString(nr) : "?");
-    hipLaunchKernelGGL(sc::mailbox_copy_wide_kernel, dim3(1), dim3(sc::kBlock), 0, ctx->stream, (const u64*)ctx->d_sums, 2 * cells,
-                       ctx->d_mailbox, wo.seq);
-    SC_HIP(ctx, hipGetLastError());
-  }
-  ctx->mailbox_seq += 1;
-  return SC_OK;
+  SC_DISPATCH_FIELD(ctx, F, f, with_bool(pf, [&](auto PF) {
+    with_const<1, 2, 3, 4, 5>(ks, [&](auto KS) {
+      hipLaunchKernelGGL((sc::wgrid_pass_kernel<F, KS, PF>), dim3(grid), dim3(sc::kBlock), 0, ctx->stream, f, A, B, A2, B2, gw, kf, n_out, wo);
+    });
+  }));
+  return commit_wide_out(ctx, wo, pow3(ks));
 }
 // wfold_pass_kernel (kernels/grid_pass.hpp): folds kf = 4 or 5 pending challenges of LARGE tables of 2^log_in entries (whole
 // tiles: log_in >= 12) into A2 / B2 and leaves the 3^ks cells of the next ks rounds exactly as launch_grid_pass does
 // (collect_grid(ctx, ks, across_ranks, .)).  Instantiated for (4, 5) - the fold behind the matrix-core first pass - and
 // (5, 3..5) - the pass behind that on the largest tables; wfold_has() tells the planner.
 bool wfold_has(int kf, int ks) { return (kf == 4 && ks == 5) || (kf == 5 && ks >= 3 && ks <= 5); }
-#define SC_WFOLD_LAUNCH(KF, KS)                                                                                                              \
-  do {                                                                                                                                       \
-    if (nt) hipLaunchKernelGGL((sc::wfold_pass_kernel<F, KF, KS, true>), dim3(grid), dim3(sc::kWfThreads), 0, ctx->stream, f, A, B, A2, B2, fw, r_top, n_tiles, wo); \
-    else hipLaunchKernelGGL((sc::wfold_pass_kernel<F, KF, KS, false>), dim3(grid), dim3(sc::kWfThreads), 0, ctx->stream, f, A, B, A2, B2, fw, r_top, n_tiles, wo);  \
-  } while (0)
-// its resident grid: one block per CU (asked once per context; prewarm asks ahead of the first proof)
+// its resident grid: one block per CU
 int wfold_resident_blocks(sc_ctx* ctx) {
-  if (ctx->wfold_blocks == 0) {
-    int per_cu = 0;
-    const void* fn = ctx->gold ? reinterpret_cast<const void*>(&sc::wfold_pass_kernel<sc::GoldilocksMont, 4, 5, true>)
-                               : reinterpret_cast<const void*>(&sc::wfold_pass_kernel<sc::MontGeneric, 4, 5, true>);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, sc::kWfThreads, 0) != hipSuccess || per_cu < 1) {
-      (void)hipGetLastError();
-      per_cu = 1;
-    }
-    ctx->wfold_blocks = std::min(per_cu * ctx->num_cus, kWgMaxBlocks);
-  }
-  return ctx->wfold_blocks;
+  const void* fn = ctx->gold ? kernel_ptr(&sc::wfold_pass_kernel<sc::GoldilocksMont, 4, 5, true>)
+                             : kernel_ptr(&sc::wfold_pass_kernel<sc::MontGeneric, 4, 5, true>);
+  return std::min(resident_grid(ctx, fn, sc::kWfThreads, ctx->num_cus), kWgMaxBlocks);
 }
 int launch_wfold_pass(sc_ctx* ctx, int kf, int ks, const u64* A, const u64* B, u64* A2, u64* B2, const u64* r, int log_in, bool across_ranks) {
   if (log_in < 12 || !A2 || !B2 || !wfold_has(kf, ks)) return fail(ctx, SC_ERR_ARG, "launch_wfold_pass: kf=%d ks=%d log_in=%d", kf, ks, log_in);
   if (!ctx->use_mailbox) return fail(ctx, SC_ERR_STATE, "launch_wfold_pass needs the host mailbox");
-  int cells = 1;
-  for (int i = 0; i < ks; ++i) cells *= 3;
-  const sc::FoldW fw = make_fold_weights(ctx, r, 4);   // (the fifth challenge rides alone: out = h0 + r_5 (h1 - h0))
+  const sc::FoldW fw = make_weights<sc::FoldW>(ctx, r, 4);   // (the fifth challenge rides alone: out = h0 + r_5 (h1 - h0))
   const u64 r_top = kf == 5 ? r[4] : 0;
   const size_t n_tiles = (size_t)1 << (log_in - 12);
   const int grid = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(n_tiles, (size_t)wfold_resident_blocks(ctx)), (size_t)ctx->max_blocks));
-  const bool peer = across_ranks && ctx->transport == Transport::kPeer;
-  const bool rccl = across_ranks && ctx->transport == Transport::kRccl;
-  sc::WgOut wo;
-  wo.partials = ctx->d_wg_partials;
-  wo.group_rows = ctx->d_wg_groups;
-  wo.tickets = ctx->d_wg_tickets;
-  wo.mailbox = ctx->d_mailbox;
-  wo.seq = ctx->mailbox_seq + 1;
-  wo.limbs_dev = rccl ? ctx->d_sums : nullptr;
-  if (peer) fill_peer(ctx, wo.px, challenge_digest(r, kf, ks, log_in) ^ 0x77666f6cu);
+  const sc::WgOut wo = next_wide_out(ctx, across_ranks, challenge_digest(r, kf, ks, log_in) ^ 0x77666f6cu, true, false);
   SC_TRY(timer_begin(ctx, SC_KIND_WFOLD_PASS, kf, ks, log_in, (u64)16 << log_in, (u64)16 << (log_in - kf)));
-  const bool nt = log_in >= ctx->nt_load_log;
-  SC_DISPATCH_FIELD(ctx, F, f, {
-    if (kf == 4) SC_WFOLD_LAUNCH(4, 5);
-    else if (ks == 3) SC_WFOLD_LAUNCH(5, 3);
-    else if (ks == 4) SC_WFOLD_LAUNCH(5, 4);
-    else SC_WFOLD_LAUNCH(5, 5);
-  });
-  SC_HIP(ctx, hipGetLastError());
-  if (peer) commit_peer(ctx);
-  SC_TRY(timer_end(ctx));
-  if (rccl) {
-    ncclResult_t nr = g_rccl.AllReduce(ctx->d_sums, ctx->d_sums, 2 * (size_t)cells, ncclUint64, ncclSum, ctx->comm, ctx->stream);
-    if (nr != ncclSuccess) return fail(ctx, SC_ERR_RCCL, "ncclAllReduce: %s", g_rccl.GetErrorString ? g_rccl.GetErrorString(nr) : "?");
-    hipLaunchKernelGGL(sc::mailbox_copy_wide_kernel, dim3(1), dim3(sc::kBlock), 0, ctx->stream, (const u64*)ctx->d_sums, 2 * cells, ctx->d_mailbox, wo.seq);
-    SC_HIP(ctx, hipGetLastError());
-  }
-  ctx->mailbox_seq += 1;
-  return SC_OK;
+  SC_DISPATCH_FIELD(ctx, F, f, with_bool(log_in >= ctx->nt_load_log, [&](auto NT) {
+    auto go = [&](auto KF, auto KS) {
+      hipLaunchKernelGGL((sc::wfold_pass_kernel<F, KF, KS, NT>), dim3(grid), dim3(sc::kWfThreads), 0, ctx->stream, f, A, B, A2, B2, fw, r_top, n_tiles, wo);
+    };
+    if (kf == 4) go(IntC<4>{}, IntC<5>{});
+    else with_const<3, 4, 5>(ks, [&](auto KS) { go(IntC<5>{}, KS); });
+  }));
+  return commit_wide_out(ctx, wo, pow3(ks));
 }
-#undef SC_WFOLD_LAUNCH
 
 // The four-round first pass of a large proof (kernels/gram.hpp): gram_pass_kernel accumulates the exact limb products of the
 // Gram matrix of the tables' sixteen slices on the int8 matrix cores, every block reduces what it holds to the 81 cells of
@@ -479,50 +430,24 @@ int launch_gram_pass(sc_ctx* ctx, const u64* A, const u64* B, int log_in, bool a
   const size_t spp = n_steps / n_partials;
   const int grid = (int)std::min(blocks, n_partials);
   SC_TRY(gram_workspace(ctx));
-  // the cells leave as a grid pass's do (launch_grid_pass): in-kernel exchange on the peer transport, one collective on RCCL,
-  // this rank's residues for the host to sum on a host transport or a multi-device handle
-  const bool peer = across_ranks && ctx->transport == Transport::kPeer;
-  const bool rccl = across_ranks && ctx->transport == Transport::kRccl;
-  constexpr int kCells = 81;
-  sc::WgOut wo;
-  wo.partials = nullptr;
-  wo.group_rows = nullptr;
-  wo.tickets = nullptr;
-  wo.mailbox = ctx->d_mailbox;
-  wo.seq = ctx->mailbox_seq + 1;
-  wo.limbs_dev = rccl ? ctx->d_sums : nullptr;
-  if (peer) fill_peer(ctx, wo.px, challenge_digest(nullptr, 0, kGramK, log_in) ^ 0x6772616du);
+  // the cells leave as a grid pass's do (next_wide_out; a multi-device handle sums the shards' residues on the host)
+  const sc::WgOut wo = next_wide_out(ctx, across_ranks, challenge_digest(nullptr, 0, kGramK, log_in) ^ 0x6772616du, false, false);
   unsigned* ticket = reinterpret_cast<unsigned*>(ctx->d_gram_rows + (size_t)kGramMaxBlocks * sc::kGramRowWords);
   SC_TRY(timer_begin(ctx, SC_KIND_GRAM_PASS, 0, kGramK, log_in, (u64)16 << log_in, (u64)grid * sc::kGramRowWords * sizeof(u64)));
   const unsigned char* a8 = reinterpret_cast<const unsigned char*>(A);
   const unsigned char* b8 = reinterpret_cast<const unsigned char*>(B);
   const int lds = sc::kGramStages * sc::kGramStageBytes;
-  SC_DISPATCH_FIELD(ctx, F, f, {
-    if (log_in >= ctx->nt_load_log)   // streaming hint as in launch_pass_t
-      hipLaunchKernelGGL((sc::gram_pass_kernel<F, kGramK, true>), dim3(grid), dim3(sc::kGramThreads), lds, ctx->stream, f, a8, b8,
-                         (unsigned)n_partials, (unsigned)spp, ctx->d_gram_rows, ticket, wo);
-    else
-      hipLaunchKernelGGL((sc::gram_pass_kernel<F, kGramK, false>), dim3(grid), dim3(sc::kGramThreads), lds, ctx->stream, f, a8, b8,
-                         (unsigned)n_partials, (unsigned)spp, ctx->d_gram_rows, ticket, wo);
-  });
-  SC_HIP(ctx, hipGetLastError());
-  if (peer) commit_peer(ctx);
-  SC_TRY(timer_end(ctx));
-  if (rccl) {
-    ncclResult_t nr = g_rccl.AllReduce(ctx->d_sums, ctx->d_sums, 2 * (size_t)kCells, ncclUint64, ncclSum, ctx->comm, ctx->stream);
-    if (nr != ncclSuccess) return fail(ctx, SC_ERR_RCCL, "ncclAllReduce: %s", g_rccl.GetErrorString ? g_rccl.GetErrorString(nr) : "?");
-    hipLaunchKernelGGL(sc::mailbox_copy_wide_kernel, dim3(1), dim3(sc::kBlock), 0, ctx->stream, (const u64*)ctx->d_sums, 2 * kCells, ctx->d_mailbox, wo.seq);
-    SC_HIP(ctx, hipGetLastError());
-  }
-  ctx->mailbox_seq += 1;
-  return SC_OK;
+  SC_DISPATCH_FIELD(ctx, F, f, with_bool(log_in >= ctx->nt_load_log, [&](auto NT) {   // streaming hint as in launch_pass_t
+    hipLaunchKernelGGL((sc::gram_pass_kernel<F, kGramK, NT>), dim3(grid), dim3(sc::kGramThreads), lds, ctx->stream, f, a8, b8,
+                       (unsigned)n_partials, (unsigned)spp, ctx->d_gram_rows, ticket, wo);
+  }));
+  return commit_wide_out(ctx, wo, pow3(kGramK));
 }
 
 // its cells: wait for the sequence word; the residues, or (sharded) the limb totals of all ranks recombined mod p
 int collect_grid(sc_ctx* ctx, int ks, bool across_ranks, u64* out) {
   SC_TRY(wait_mailbox(ctx, ctx->mailbox_seq));
-  int cells = 1;
-  for (int i = 0; i < ks; ++i) cells *= 3;
+  const int cells = pow3(ks);
   const u64* wide = ctx->h_mailbox + sc::kMailboxWide;
   if (!across_ranks) {
     for (int c = 0; c < cells; ++c) out[c] = wide[c];
@@ -552,56 +477,16 @@ int collect_grid(sc_ctx* ctx, int ks, bool across_ranks, u64* out) {
 int rank_pass(sc_ctx* ctx, int kf, const u64* A, const u64* B, u64* A2, u64* B2, const u64* r, u64* out) {
   if (ctx->transport != Transport::kPeer || !ctx->use_mailbox || kf < 0 || kf > sc::kGridMaxVars || ctx->log_world < 1 || ctx->log_world > 3)
     return fail(ctx, SC_ERR_STATE, "rank_pass: needs the peer transport, the mailbox and 2..8 ranks");
-  const sc::GridW gw = make_grid_weights(ctx, r, kf);
-  sc::WgOut wo;
-  wo.partials = ctx->d_wg_partials;
-  wo.group_rows = ctx->d_wg_groups;
-  wo.tickets = ctx->d_wg_tickets;
-  wo.mailbox = ctx->d_mailbox;
-  wo.seq = ctx->mailbox_seq + 1;
-  wo.limbs_dev = nullptr;
-  fill_peer(ctx, wo.px, challenge_digest(r, kf, ctx->log_world, kf) ^ 0x72616e6bu);
+  const sc::GridW gw = make_weights<sc::GridW>(ctx, r, kf);
+  const sc::WgOut wo = next_wide_out(ctx, true, challenge_digest(r, kf, ctx->log_world, kf) ^ 0x72616e6bu, true, false);
   SC_TRY(timer_begin(ctx, SC_KIND_GRID_PASS, kf, ctx->log_world, kf, (u64)16 << kf, (u64)16 << ctx->log_world));
   SC_DISPATCH_FIELD(ctx, F, f,
                     hipLaunchKernelGGL((sc::rank_pass_kernel<F>), dim3(1), dim3(sc::kBlock), 0, ctx->stream, f, A, B, A2, B2, gw, kf, wo));
-  SC_HIP(ctx, hipGetLastError());
-  commit_peer(ctx);
-  ctx->mailbox_seq += 1;
-  SC_TRY(timer_end(ctx));
+  SC_TRY(commit_wide_out(ctx, wo, 0));
   SC_TRY(wait_mailbox(ctx, ctx->mailbox_seq));
   SC_TRY(check_exchange(ctx, "entries"));
-  int cells = 1;
-  for (int i = 0; i < ctx->log_world; ++i) cells *= 3;
-  for (int c = 0; c < cells; ++c) out[c] = ctx->h_mailbox[sc::kMailboxWide + c];
+  for (int c = 0, cells = pow3(ctx->log_world); c < cells; ++c) out[c] = ctx->h_mailbox[sc::kMailboxWide + c];
   return SC_OK;
 }
-
-// PassOut of the next launch that ends in finish_pass.  across_ranks: its sums are summed over the ranks - inside the
-// kernel on the peer transport (digest = what the ranks must agree on), by a collective on the stream for RCCL (the
-// limbs stay in d_sums), by the host for a host transport.  *from_mailbox tells collect_sums where the limbs are.
-// Nothing is committed here: call commit_pass_out() once the launch is known to be in the stream.
-sc::PassOut next_pass_out(sc_ctx* ctx, bool across_ranks, unsigned digest, bool* from_mailbox) {
-  const bool peer = across_ranks && ctx->transport == Transport::kPeer;
-  const bool mailbox = (ctx->use_mailbox || peer) && !(across_ranks && ctx->transport == Transport::kRccl);
-  sc::PassOut out;
-  out.partials = ctx->d_partials;
-  out.n_rows = (int)ctx->partial_rows;
-  out.ticket = ctx->d_ticket;
-  out.ticket_base = ctx->ticket_base;
-  out.sums_dev = ctx->d_sums;
-  out.mailbox = mailbox ? ctx->d_mailbox : nullptr;
-  out.seq = mailbox ? ctx->mailbox_seq + 1 : 0;
-  if (peer) fill_peer(ctx, out.px, digest);
-  if (from_mailbox) *from_mailbox = mailbox;
-  return out;
-}
-int commit_pass_out(sc_ctx* ctx, const sc::PassOut& out, int grid) {
-  SC_HIP(ctx, hipGetLastError());
-  if (out.px.world > 0) commit_peer(ctx);
-  if (out.mailbox) ctx->mailbox_seq += 1;
-  if (grid > 1) ctx->ticket_base += (unsigned)grid;
-  return SC_OK;
-}
-
 
 }  // namespace

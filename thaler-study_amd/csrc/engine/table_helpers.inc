@@ -6,6 +6,18 @@ namespace {
 // shared helpers for the table API
 // =====================================================================================
 
+// The end of a call that launched a kernel (or queued a copy: e) into the fresh table t: the stream drained, t handed out - or
+// freed and `what` reported
+int table_done(sc_ctx* ctx, sc_table* t, hipError_t e, const char* what, sc_table** out) {
+  if (e == hipSuccess) e = sync_stream(ctx);
+  if (e != hipSuccess) {
+    sc_table_free(ctx, t);
+    return fail(ctx, SC_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+  }
+  *out = t;
+  return SC_OK;
+}
+
 sc::RVec make_rvec(const u64* r, size_t n) {
   sc::RVec rv;
   memset(&rv, 0, sizeof(rv));
@@ -154,12 +166,9 @@ int fold_chain(sc_ctx* ctx, const u64* in, size_t len, const u64* r, size_t k, i
       }
       const int nt = cur_len >= ((size_t)1 << ctx->nt_load_log) ? 1 : 0;
       SC_CHAIN(timer_begin(ctx, SC_KIND_FIX_LOW, step, 0, log2_of(cur_len), (u64)8 * cur_len, (u64)8 * nlen));
-      if (nt)
-        SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::fix_low_kernel<F, true>), dim3(grid), dim3(threads), 0,
-                                                        ctx->stream, f, cur, nxt, step, rv, nlen));
-      else
-        SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::fix_low_kernel<F, false>), dim3(grid), dim3(threads), 0,
-                                                        ctx->stream, f, cur, nxt, step, rv, nlen));
+      SC_DISPATCH_FIELD(ctx, F, f, with_bool(nt, [&](auto NT) {
+        hipLaunchKernelGGL((sc::fix_low_kernel<F, NT>), dim3(grid), dim3(threads), 0, ctx->stream, f, cur, nxt, step, rv, nlen);
+      }));
       SC_CHAIN(timer_end(ctx));
       cur_len = nlen;
     } else if (order == SC_ORDER_LE && k - done >= 4 && cur_len <= ((size_t)1 << 20) && (cur_len >> std::min<size_t>(5, k - done)) >= 1) {
@@ -167,7 +176,7 @@ int fold_chain(sc_ctx* ctx, const u64* in, size_t len, const u64* r, size_t k, i
       step = (int)std::min<size_t>(5, k - done);
       const size_t nlen = cur_len >> step;
       SC_CHAIN(pool_alloc(ctx, nlen, &nxt));
-      const sc::GridW gw = make_grid_weights(ctx, r + done, step);
+      const sc::GridW gw = make_weights<sc::GridW>(ctx, r + done, step);
       SC_CHAIN(timer_begin(ctx, SC_KIND_FOLD, step, 0, log2_of(cur_len), (u64)8 * cur_len, (u64)8 * nlen));
       const int grid = grid_for(ctx, nlen);
       SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::fold_wide_kernel<F>), dim3(grid), dim3(sc::kBlock), 0, ctx->stream, f, cur, nxt,
@@ -179,7 +188,7 @@ int fold_chain(sc_ctx* ctx, const u64* in, size_t len, const u64* r, size_t k, i
       while (step > 1 && (cur_len >> step) < 2) --step;
       size_t nlen = cur_len >> step;
       SC_CHAIN(pool_alloc(ctx, nlen, &nxt));
-      const sc::FoldW fw = make_fold_weights(ctx, r + done, step);
+      const sc::FoldW fw = make_weights<sc::FoldW>(ctx, r + done, step);
       SC_CHAIN(timer_begin(ctx, SC_KIND_FOLD, step, 0, log2_of(cur_len), (u64)8 * cur_len, (u64)8 * nlen));
       if (nlen >= 2) {
         size_t n_units = nlen / 2;
@@ -190,29 +199,21 @@ int fold_chain(sc_ctx* ctx, const u64* in, size_t len, const u64* r, size_t k, i
           grab = sc::kFoldGrab;
         }
         const int nt = cur_len >= ((size_t)1 << ctx->nt_load_log) ? 1 : 0;
-#define SC_FOLD(KF)                                                                                                  \
-  do {                                                                                                               \
-    if (sc::fold_kernel_lds_bytes(KF, threads) > 65536 && !ctx->fold_lds_allowed[KF][nt]) {   /* more dynamic LDS than a launch gets by default: once per kernel */ \
-      hipError_t ea_ = hipSuccess;                                                                                   \
-      SC_DISPATCH_FIELD(ctx, F, f, {                                                                                 \
-        (void)f;                                                                                                     \
-        ea_ = hipFuncSetAttribute(reinterpret_cast<const void*>(nt ? &sc::fold_kernel<F, KF, true> : &sc::fold_kernel<F, KF, false>), \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)sc::fold_kernel_lds_bytes(KF, sc::kFoldBlock)); \
-      });                                                                                                            \
-      if (ea_ != hipSuccess) SC_CHAIN(fail(ctx, SC_ERR_HIP, "fold_kernel: %s", hipGetErrorString(ea_)));              \
-      ctx->fold_lds_allowed[KF][nt] = true;                                                                          \
-    }                                                                                                                \
-    if (nt)                                                                                                          \
-      SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::fold_kernel<F, KF, true>), dim3(grid), dim3(threads), sc::fold_kernel_lds_bytes(KF, threads), \
-                                                      ctx->stream, f, cur, nxt, fw, n_units, grab));                 \
-    else                                                                                                             \
-      SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::fold_kernel<F, KF, false>), dim3(grid), dim3(threads), sc::fold_kernel_lds_bytes(KF, threads), \
-                                                      ctx->stream, f, cur, nxt, fw, n_units, grab));                 \
-  } while (0)
-        if (step == 3) SC_FOLD(3);
-        else if (step == 2) SC_FOLD(2);
-        else SC_FOLD(1);
-#undef SC_FOLD
+        hipError_t ea = hipSuccess;
+        SC_DISPATCH_FIELD(ctx, F, f, with_const<1, 2, 3>(step, [&](auto KF) {
+          with_bool(nt, [&](auto NT) {
+            // more dynamic LDS than a launch gets by default: asked for once per kernel
+            if (sc::fold_kernel_lds_bytes(KF, threads) > 65536 && !ctx->fold_lds_allowed[KF][NT]) {
+              ea = hipFuncSetAttribute(kernel_ptr(&sc::fold_kernel<F, KF, NT>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)sc::fold_kernel_lds_bytes(KF, sc::kFoldBlock));
+              if (ea != hipSuccess) return;
+              ctx->fold_lds_allowed[KF][NT] = true;
+            }
+            hipLaunchKernelGGL((sc::fold_kernel<F, KF, NT>), dim3(grid), dim3(threads), sc::fold_kernel_lds_bytes(KF, threads), ctx->stream, f,
+                               cur, nxt, fw, n_units, grab);
+          });
+        }));
+        if (ea != hipSuccess) SC_CHAIN(fail(ctx, SC_ERR_HIP, "fold_kernel: %s", hipGetErrorString(ea)));
       } else {
         SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::fold_le_small_kernel<F>), dim3(1), dim3(64), 0,
                                                         ctx->stream, f, cur, nxt, r[done], nlen));

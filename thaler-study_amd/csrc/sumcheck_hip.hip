@@ -141,21 +141,19 @@ struct sc_ctx {
   int grid_max_vars = 5;    // most rounds one of them serves (1..5)
   int grid_sharded = 1;     // sharded passes too (cells exchanged inside the kernel on the peer transport, summed by the
                             // collective on the others), down to shards that hold only their pending challenges
-  int wgrid_blocks = 0;     // resident grid of wgrid_pass_kernel (0 = not asked yet)
   int grid_blocks = 0;      // cap on the blocks of such a launch (0 = as many as are resident; tests use it to reach both ticket levels)
   u64* d_wg_partials = nullptr;   // [kWgMaxBlocks][kGridChunk]
   u64* d_wg_groups = nullptr;     // [kWgMaxBlocks / 32][kGridChunk]
   unsigned* d_wg_tickets = nullptr;
   u64* d_gram_rows = nullptr;     // gram_pass_kernel: the blocks' rows of 81 cells + its ticket (zero at rest); allocated on first use
   int fold_dma = 1;       // pass_kernel<4,2>: the LDS-DMA form (kernels/pass.hpp; Goldilocks)
-  int pipe32 = 1, pipe32_log = 20, pipe32_blocks = 0;   // pass_kernel<3,2>: the pipelined whole-tile form on tables of >= 2^pipe32_log entries
+  int pipe32 = 1, pipe32_log = 20;   // pass_kernel<3,2>: the pipelined whole-tile form on tables of >= 2^pipe32_log entries
   int gram_log = 21;              // first pass of an unsharded proof on tables of >= 2^gram_log entries: kernels/gram.hpp (0: never)
   int host_tail_log = kTailLogMax;   // folded tables of <= 2^this entries go to pinned host memory and the host finishes the proof (0: off)
   int wfold_log = 40;                // the fold behind the matrix-core first pass serves FIVE rounds (wfold_pass_kernel) on tables of <= 2^this entries (0: never)
   int wfold_min_log = 21;            // ... and of >= 2^this entries (below, a five-round grid pass folds the four challenges)
   int wfold5_min_log = 24;           // a grid pass with FIVE challenges to fold over tables of >= 2^this entries runs in the same kernel's (5, ks) form
   int wfold_always = 0;              // 0: where the proof then needs fewer launches (the planner counts both ways); 1: wherever it can run
-  int wfold_blocks = 0;              // its resident grid (0 = not asked yet)
   int matmul_path = 0;               // sc_matmul: 0 auto (the int8 matrix cores from 32 x 32), 1 matrix cores (from 16 x 16), 2 VALU
   int tail_log = 16;  // shard log-size at which a sharded prover gathers: a 512 KiB all-gather per table is
                       // cheaper than the ~25 us of collective latency of each further sharded pass
@@ -164,9 +162,8 @@ struct sc_ctx {
   // 629 with 512 - more blocks than that only add concurrent DRAM streams and a longer final reduction
   int max_blocks = 768;
   int num_cus = 256;
-  // blocks of each pass-kernel instantiation that fit on the chip at once ([generic|goldilocks][kf][ks],
-  // 0 = not asked yet)
-  int resident_blocks[2][5][4] = {};
+  // blocks of a kernel that fit on the chip at once, by kernel (launch.inc, resident_grid; asked once per context)
+  std::map<const void*, int> resident_grid;
   int time_kernels = 0;
   // where a proof's wall time goes on the HOST side (always on: four clock reads per pass): ns spent spinning on the mailbox (the
   // kernels + their launch latency) and ns spent inside the pass launches (buffers, weights, hipLaunchKernelGGL); the rest of a
@@ -250,7 +247,6 @@ struct sc_ctx {
   u64* h_batch = nullptr;
   u64* d_batch = nullptr;
   size_t batch_words = 0;
-  int batch_blocks = 0;     // resident grid of batch_pass_kernel (0 = not asked yet)
 
   // kernel timing
   // pass-kernel timing (option "time_kernels"): a ring of event pairs, read back only when the
