@@ -220,6 +220,10 @@ int sc_ctx_kernel_time(sc_ctx* ctx, double out[2], int reset);
 #define SC_KIND_MATMUL 15      /* sc_matmul: kf = 0 the byte repack, 1 matmul_mfma_kernel (int8 matrix cores), 2 matmul_tiled_kernel, 3 matmul_kernel (VALU); ks = n, log_in = 2n */
 #define SC_KIND_BATCH_PASS 16  /* batch_pass_kernel: one pass of every instance of sc_prove_batch; kf, ks and log_in (= n at the first pass) as for a grid
                                 * pass; the batch size is bytes_read / (16 * 2^log_in) */
+#define SC_KIND_GRID_EXTEND 17 /* grid_extend_kernel: one axis of sc_table_extend_grid; kf = the variable extended, ks = log_in = m.  One launch
+                                * per variable (not fused): bytes = what that launch reads and writes, about p/(p-2) times the output in all */
+#define SC_KIND_MERKLE 18      /* sc_merkle_*: kf = 0 merkle_leaf_kernel (leaves up to level ks = min(n, 4)), 1 merkle_level_kernel (level ks),
+                                * 2 merkle_top_kernel (levels ks .. n in one block), 3 merkle_open_kernel (an opening's gather); log_in = n */
 typedef struct sc_launch_record {
   int32_t kind;           /* SC_KIND_* */
   int32_t kf, ks;         /* variables folded / rounds served (meaning per kind above) */
@@ -487,6 +491,33 @@ int sc_gkr_prover_destroy(sc_gkr_prover* pr);
  * split by its top index bits like every table there.  The reference returns a SparsePolynomial: drop zero terms. */
 int sc_table_restrict_to_line(sc_ctx* ctx, const sc_table* t, const uint64_t* b, const uint64_t* c, size_t k,
                               uint64_t* out_coeffs);
+
+/* ---- relaxed_pcs: the prover's grid evaluation and a SHA-256 Merkle commitment (relaxed-pcs/src/lib.rs) -----------------
+ * Leaf order: all_multidimentional_values(m) (:46-63) lists the p^m points (v_0, .., v_{m-1}) of F^m sorted by canonical value,
+ * v_0 the most significant digit: the point's leaf index is o = sum_j v_j p^(m-1-j), and its value is the dense LE MLE at it
+ * (point[0] binds index bit 0 of the table; so variable 0 has input stride 1 but output stride p^(m-1)).
+ * Merkle tree over N = 2^n leaves (this project's configuration: the reference's test hashes with Pedersen over JubJub):
+ * leaf digest SHA-256(le64(canonical value)), node digest SHA-256(left || right) at every level; the root of a one-leaf tree is
+ * its leaf's digest.  Digests are 32 bytes (SHA-256's own byte order).  Meant to equal arkworks' MerkleTree with Sha256 as both
+ * hashes and IdentityDigestConverter; that byte identity is not pinned.  Sharded contexts and multi-device handles:
+ * SC_ERR_UNSUPPORTED from every call below, before any work. */
+
+/* :166-181: W~ at every point of F^m in that leaf order, t holding 2^m entries; *out has 2^ceil(log2 p^m) entries, Montgomery
+ * like every table, zero past p^m.  One launch per variable (SC_KIND_GRID_EXTEND).  SC_ERR_ARG: t is not 2^m long;
+ * SC_ERR_UNSUPPORTED: p^m > 2^28 (the Relaxed PCS also needs p > m for restrict_poly, sc_table_restrict_to_line). */
+int sc_table_extend_grid(sc_ctx* ctx, const sc_table* t, size_t m, sc_table** out);
+/* MerkleTree::new over the 2^n entries of t, n <= 28 (:185-186).  t is borrowed: it must outlive the tree, unchanged.  The
+ * device keeps the levels from min(n, 4) up (N * 4 bytes of digests); an opening recomputes its 16-leaf bottom subtree. */
+typedef struct sc_merkle_tree sc_merkle_tree;
+int sc_merkle_commit(sc_ctx* ctx, const sc_table* t, sc_merkle_tree** out);
+int sc_merkle_root(const sc_merkle_tree* tr, uint8_t root[32]);
+/* depth = n = log2 N: the number of sibling digests in a path */
+int sc_merkle_depth(const sc_merkle_tree* tr, size_t* depth);
+/* MerkleTree::generate_proof (:207-213) for `count` leaves in one call: leaves[q] = the canonical value of leaf index[q],
+ * paths[q][depth][32] its sibling digests bottom up.  To verify: h = leaf digest; at level l, h = H(h || s_l) if bit l of the
+ * index is 0, else H(s_l || h); then h must equal the root.  SC_ERR_ARG: an index >= N. */
+int sc_merkle_open(sc_ctx* ctx, const sc_merkle_tree* tr, const uint64_t* index, size_t count, uint64_t* leaves, uint8_t* paths);
+int sc_merkle_tree_destroy(sc_ctx* ctx, sc_merkle_tree* tr);
 
 /* ---- gkr_protocol::circuit::Circuit on the device, and the whole GKR prover over it ----------------------------------
  * A circuit lives on ONE context of one device and one rank: sharded contexts (world > 1) and multi-device handles get

@@ -91,6 +91,10 @@ pub struct sc_tri_prover {
 pub struct sc_circuit {
     _private: [u8; 0],
 }
+#[repr(C)]
+pub struct sc_merkle_tree {
+    _private: [u8; 0],
+}
 
 pub type sc_allreduce_fn = Option<unsafe extern "C" fn(user: *mut c_void, buf: *mut u64, count: usize) -> c_int>;
 pub type sc_allgather_fn =
@@ -449,4 +453,21 @@ extern "C" {
     pub fn sc_tri_prover_c1(pr: *const sc_tri_prover, out: *mut u64) -> c_int;
     pub fn sc_tri_prover_round(pr: *mut sc_tri_prover, r_prev: u64, j: usize, out_e: *mut u64) -> c_int;
     pub fn sc_tri_prover_destroy(pr: *mut sc_tri_prover) -> c_int;
+
+    /// relaxed-pcs: W~ at every point of F^m in the reference's leaf order (v_0 the most significant digit), zero-padded
+    pub fn sc_table_extend_grid(ctx: *mut sc_ctx, t: *const sc_table, m: usize, out: *mut *mut sc_table) -> c_int;
+    /// SHA-256 Merkle commitment of a table of 2^n entries (n <= 28); `t` is borrowed and must outlive the tree
+    pub fn sc_merkle_commit(ctx: *mut sc_ctx, t: *const sc_table, out: *mut *mut sc_merkle_tree) -> c_int;
+    pub fn sc_merkle_root(tr: *const sc_merkle_tree, root: *mut u8) -> c_int;
+    pub fn sc_merkle_depth(tr: *const sc_merkle_tree, depth: *mut usize) -> c_int;
+    /// `count` openings: leaves[count] canonical, paths[count][depth][32] bottom up
+    pub fn sc_merkle_open(
+        ctx: *mut sc_ctx,
+        tr: *const sc_merkle_tree,
+        index: *const u64,
+        count: usize,
+        leaves: *mut u64,
+        paths: *mut u8,
+    ) -> c_int;
+    pub fn sc_merkle_tree_destroy(ctx: *mut sc_ctx, tr: *mut sc_merkle_tree) -> c_int;
 }

@@ -49,7 +49,10 @@ class ScLaunchRecord(ctypes.Structure):
                 ("bytes_read", u64), ("bytes_written", u64), ("ms", ctypes.c_double)]
 
 
-KIND_NAMES = {0: "pass", 2: "evaluate", 3: "fold", 4: "fix_low", 5: "fold_be", 6: "coldot", 7: "gkr", 8: "matsq", 10: "grid_pass", 11: "gram_pass", 13: "wfold_pass", 14: "circuit", 15: "matmul", 16: "batch_pass"}
+KIND_NAMES = {0: "pass", 2: "evaluate", 3: "fold", 4: "fix_low", 5: "fold_be", 6: "coldot", 7: "gkr", 8: "matsq", 10: "grid_pass", 11: "gram_pass", 13: "wfold_pass", 14: "circuit", 15: "matmul", 16: "batch_pass",
+              17: "grid_extend", 18: "merkle"}
+# SC_KIND_MERKLE records: kf -> the kernel that ran
+MERKLE_KERNELS = {0: "merkle_leaf_kernel", 1: "merkle_level_kernel", 2: "merkle_top_kernel", 3: "merkle_open_kernel"}
 # SC_KIND_MATMUL records: kf -> the kernel that ran
 MATMUL_KERNELS = {0: "matmul_bytes_kernel", 1: "matmul_mfma_kernel", 2: "matmul_tiled_kernel", 3: "matmul_kernel"}
 MATMUL_PATHS = {"auto": 0, "mfma": 1, "valu": 2}
@@ -129,6 +132,12 @@ SIGNATURES = {
     "sc_gkr_prover_round": (ctypes.c_int, [voidp, u64, size_t, u64p]),
     "sc_gkr_prover_destroy": (ctypes.c_int, [voidp]),
     "sc_table_restrict_to_line": (ctypes.c_int, [voidp, voidp, u64p, u64p, size_t, u64p]),
+    "sc_table_extend_grid": (ctypes.c_int, [voidp, voidp, size_t, ctypes.POINTER(voidp)]),
+    "sc_merkle_commit": (ctypes.c_int, [voidp, voidp, ctypes.POINTER(voidp)]),
+    "sc_merkle_root": (ctypes.c_int, [voidp, ctypes.POINTER(ctypes.c_uint8)]),
+    "sc_merkle_depth": (ctypes.c_int, [voidp, ctypes.POINTER(size_t)]),
+    "sc_merkle_open": (ctypes.c_int, [voidp, voidp, u64p, size_t, u64p, ctypes.POINTER(ctypes.c_uint8)]),
+    "sc_merkle_tree_destroy": (ctypes.c_int, [voidp, voidp]),
     "sc_circuit_create": (ctypes.c_int, [voidp, size_t, ctypes.POINTER(size_t), ctypes.POINTER(ctypes.POINTER(ctypes.c_int32)),
                                           ctypes.POINTER(ctypes.POINTER(ctypes.c_uint32)), ctypes.POINTER(ctypes.POINTER(ctypes.c_uint32)),
                                           ctypes.POINTER(voidp)]),

@@ -473,4 +473,5 @@ static int multi_prod2_fold_and_sums(sc_ctx* m, const sc_table* a, const sc_tabl
 #include "engine/abi_matmul.inc"
 #include "engine/abi_batch.inc"
 #include "engine/abi_restrict.inc"
+#include "engine/abi_pcs.inc"
 #include "engine/abi_multi.inc"
