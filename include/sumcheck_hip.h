@@ -182,6 +182,10 @@ const char* sc_last_error(const sc_ctx* ctx);
  *                      weights, hipLaunchKernelGGL); the rest is host arithmetic between them.  Always on (four clock reads per pass).
  *                      On a multi-device handle both read the FIRST device's context only (the devices run side by side: their
  *                      waits overlap, a sum would count the same wall time N times)
+ *   "stat_pool_live_blocks" / "stat_pool_live_words" / "stat_pool_peak_words"  (get) the device-buffer pool's bookkeeping: blocks
+ *                      handed out and not yet given back (tables, prover state, buffers of a call in flight), their total capacity
+ *                      in 64-bit words, and the high-water mark of that total; "stat_reset" sets the mark to the current total.
+ *                      Host-side counters only.  On a multi-device handle each is the SUM over its devices' contexts
  *   "nt_load_log" / "nt_store_log"  table log-size from which loads / stores are nontemporal
  * Environment: SC_RCCL_LIBRARY = the RCCL build sc_ctx_comm_init_rccl / sc_comm_unique_id dlopen (a path; default librccl.so.1).
  * That library or nothing: a path that cannot be loaded is an error, never a silent second choice. */

@@ -71,24 +71,23 @@ int batch_blocks_per_instance(sc_ctx* ctx, size_t count, size_t n_out) {
 }
 
 // The device buffers of one call: descriptors, partial rows, tickets (zeroed once; every launch leaves them at zero).
+// (Declared in the reverse of the order they go back in.)
 struct BatchBufs {
-  u64* desc = nullptr;
-  u64* partials = nullptr;
-  u64* tickets = nullptr;
-  u64* folded = nullptr;   // the instances' current folded tables, [instance][table][2^cur_log] (null: the caller's tables)
+  PoolBuf tickets, partials, desc;
+  PoolBuf folded;   // the instances' current folded tables, [instance][table][2^cur_log] (null: the caller's tables)
 };
 
 // One pass over every instance: fold its kf pending challenges of tables of 2^log_in entries, the 3^ks cells of the next ks
 // rounds into its S.  to_host: the folded tables go to the pinned batch memory (after the cells), the host finishes from them.
 int batch_pass(sc_ctx* ctx, std::vector<sc_prover>& pr, BatchBufs& bb, int kf, int ks, int log_in, bool to_host, size_t j) {
   const size_t count = pr.size(), n_out = (size_t)1 << (log_in - kf);
-  u64* folded = nullptr;
+  PoolBuf folded;
   u64* out_base = nullptr;
   if (kf > 0) {
     if (to_host) {
       out_base = ctx->d_batch + count * sc::kGridMaxCells;
     } else {
-      SC_TRY(pool_alloc(ctx, count * 2 * n_out, &folded));
+      SC_TRY(folded.alloc(ctx, count * 2 * n_out));
       out_base = folded;
     }
   }
@@ -107,19 +106,17 @@ int batch_pass(sc_ctx* ctx, std::vector<sc_prover>& pr, BatchBufs& bb, int kf, i
   const bool pf = (kf == 0 || kf == 2) && n_iter > (size_t)bpi * kWaves;   // (launch_grid_pass's rule)
   sc::BatchOut bo;
   bo.partials = bb.partials;
-  bo.tickets = reinterpret_cast<unsigned*>(bb.tickets);
+  bo.tickets = reinterpret_cast<unsigned*>(bb.tickets.get());
   bo.cells = ctx->d_batch;
   bo.mailbox = ctx->d_mailbox;
   bo.seq = ctx->mailbox_seq + 1;
   bo.host_out = to_host ? 1 : 0;
-  const sc::BatchDesc* dd = reinterpret_cast<const sc::BatchDesc*>(bb.desc);
-  int rc = SC_OK;
+  const sc::BatchDesc* dd = reinterpret_cast<const sc::BatchDesc*>(bb.desc.get());
   if (hipMemcpyAsync(bb.desc, hd, count * sizeof(sc::BatchDesc), hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-    rc = fail(ctx, SC_ERR_HIP, "sc_prove_batch: descriptor copy failed");
+    return fail(ctx, SC_ERR_HIP, "sc_prove_batch: descriptor copy failed");
   // the launch log: log_in and kf / ks as a grid pass's; the batch size is bytes_read / (16 * 2^log_in)
-  if (rc == SC_OK)
-    rc = timer_begin(ctx, SC_KIND_BATCH_PASS, kf, ks, log_in, (u64)count * (16ull << log_in), kf > 0 ? (u64)count * (16ull << (log_in - kf)) : 0);
-  if (rc == SC_OK) {
+  SC_TRY(timer_begin(ctx, SC_KIND_BATCH_PASS, kf, ks, log_in, (u64)count * (16ull << log_in), kf > 0 ? (u64)count * (16ull << (log_in - kf)) : 0));
+  {
     const dim3 grid((unsigned)bpi, (unsigned)count);
     SC_DISPATCH_FIELD(ctx, F, f, with_bool(pf, [&](auto PF) {
       with_const<1, 2, 3, 4, 5>(ks, [&](auto KS) {
@@ -128,18 +125,12 @@ int batch_pass(sc_ctx* ctx, std::vector<sc_prover>& pr, BatchBufs& bb, int kf, i
     }));
     if (hipGetLastError() != hipSuccess) {
       poison(ctx);
-      rc = fail(ctx, SC_ERR_HIP, "batch_pass_kernel launch failed");
+      return fail(ctx, SC_ERR_HIP, "batch_pass_kernel launch failed");
     }
   }
-  if (rc == SC_OK) rc = timer_end(ctx);
-  if (rc == SC_OK) {
-    ctx->mailbox_seq += 1;
-    rc = wait_mailbox(ctx, ctx->mailbox_seq);
-  }
-  if (rc != SC_OK) {
-    pool_release(ctx, folded);
-    return rc;
-  }
+  SC_TRY(timer_end(ctx));
+  ctx->mailbox_seq += 1;
+  SC_TRY(wait_mailbox(ctx, ctx->mailbox_seq));
   const int cells = pow3(ks);
   for (size_t i = 0; i < count; ++i) {
     sc_prover& p = pr[i];
@@ -155,10 +146,7 @@ int batch_pass(sc_ctx* ctx, std::vector<sc_prover>& pr, BatchBufs& bb, int kf, i
     p.cache_round = j;
     p.g_known = -1;
   }
-  if (kf > 0) {   // the tables of the pass before are read: their block goes back (stream-ordered reuse)
-    pool_release(ctx, bb.folded);
-    bb.folded = folded;
-  }
+  if (kf > 0) bb.folded = std::move(folded);   // the tables of the pass before are read: their block goes back (stream-ordered reuse)
   return SC_OK;
 }
 
@@ -189,9 +177,9 @@ int prove_batch_impl(sc_ctx* ctx, size_t count, const sc_table* const* a, const 
   SC_TRY(batch_reserve(ctx, count, tail_log));
   BatchBufs bb;
   const size_t rows = count * (size_t)batch_blocks_per_instance(ctx, count, (size_t)1 << n);   // (the most: the first pass's)
-  int rc = pool_alloc(ctx, (count * sizeof(sc::BatchDesc) + 7) / 8, &bb.desc);
-  if (rc == SC_OK) rc = pool_alloc(ctx, rows * sc::kGridChunk, &bb.partials);
-  if (rc == SC_OK) rc = pool_alloc(ctx, (count + 1 + 1) / 2, &bb.tickets);
+  int rc = bb.desc.alloc(ctx, (count * sizeof(sc::BatchDesc) + 7) / 8);
+  if (rc == SC_OK) rc = bb.partials.alloc(ctx, rows * sc::kGridChunk);
+  if (rc == SC_OK) rc = bb.tickets.alloc(ctx, (count + 1 + 1) / 2);
   if (rc == SC_OK && hipMemsetAsync(bb.tickets, 0, (count + 1) * sizeof(unsigned), ctx->stream) != hipSuccess)
     rc = fail(ctx, SC_ERR_HIP, "sc_prove_batch: memset failed");
   const PlanOpts o = plan_opts_of(ctx, true);
@@ -240,10 +228,6 @@ int prove_batch_impl(sc_ctx* ctx, size_t count, const sc_table* const* a, const 
       q.pending.push_back(r);
     }
   }
-  pool_release(ctx, bb.folded);
-  pool_release(ctx, bb.desc);
-  pool_release(ctx, bb.partials);
-  pool_release(ctx, bb.tickets);
   return rc;
 }
 

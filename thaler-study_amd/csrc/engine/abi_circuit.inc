@@ -13,7 +13,7 @@ struct sc_circuit {
   size_t depth = 0;
   std::vector<size_t> k;        // depth + 1 entries; k[depth] = input variables
   std::vector<size_t> off, stride;
-  u64* words = nullptr;
+  PoolBuf words;
 };
 
 namespace {
@@ -31,21 +31,19 @@ int check_circuit_ctx(sc_ctx* ctx, const sc_circuit* c, const char* what) {
   return SC_OK;
 }
 
-const unsigned* circuit_layer_words(const sc_circuit* c, size_t i) { return (const unsigned*)c->words + c->off[i]; }
+const unsigned* circuit_layer_words(const sc_circuit* c, size_t i) { return (const unsigned*)c->words.get() + c->off[i]; }
 
 // values[i] of every layer, from the input up (one launch per layer on the context's stream, no host sync between them)
-int circuit_evaluate_impl(sc_ctx* ctx, const sc_circuit* c, const sc_table* input, std::vector<sc_table*>* values) {
-  values->assign(c->depth, nullptr);
-  int rc = SC_OK;
-  for (size_t i = c->depth; i-- > 0 && rc == SC_OK;) {
+// (on failure none is left)
+int circuit_evaluate_impl(sc_ctx* ctx, const sc_circuit* c, const sc_table* input, std::vector<TableBuf>* values) {
+  std::vector<TableBuf> v(c->depth);
+  for (size_t i = c->depth; i-- > 0;) {
     const size_t n = (size_t)1 << c->k[i];
-    const u64* in = i + 1 == c->depth ? input->d : (*values)[i + 1]->d;
-    rc = new_table(ctx, n, &(*values)[i]);
-    if (rc != SC_OK) break;
-    u64* out = (*values)[i]->d;
+    const u64* in = i + 1 == c->depth ? input->d : v[i + 1]->d;
+    SC_TRY(v[i].alloc(ctx, n));
+    u64* out = v[i]->d;
     // streamed: 12 B of gate words in, 8 B out per gate (the two gathers are served from the layer the previous launch wrote)
-    rc = timer_begin(ctx, SC_KIND_CIRCUIT, (int)c->k[i + 1], 0, (int)c->k[i], (u64)12 * n, (u64)8 * n);
-    if (rc != SC_OK) break;
+    SC_TRY(timer_begin(ctx, SC_KIND_CIRCUIT, (int)c->k[i + 1], 0, (int)c->k[i], (u64)12 * n, (u64)8 * n));
     const unsigned* w = circuit_layer_words(c, i);
     const int grid = grid_for_wide(ctx, std::max<size_t>(n >> 2, 1));
     const bool nt = c->k[i] >= (size_t)ctx->nt_load_log;
@@ -55,18 +53,12 @@ int circuit_evaluate_impl(sc_ctx* ctx, const sc_circuit* c, const sc_table* inpu
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
       poison(ctx);
-      rc = fail(ctx, SC_ERR_HIP, "circuit_layer_kernel (layer %zu) launch failed: %s", i, hipGetErrorString(e));
-      break;
+      return fail(ctx, SC_ERR_HIP, "circuit_layer_kernel (layer %zu) launch failed: %s", i, hipGetErrorString(e));
     }
-    rc = timer_end(ctx);
+    SC_TRY(timer_end(ctx));
   }
-  if (rc != SC_OK) {
-    for (sc_table*& t : *values) {
-      (void)sc_table_free(ctx, t);
-      t = nullptr;
-    }
-  }
-  return rc;
+  *values = std::move(v);
+  return SC_OK;
 }
 
 int check_circuit_input(sc_ctx* ctx, const sc_circuit* c, const sc_table* input, const char* what) {
@@ -142,11 +134,11 @@ extern "C" int sc_circuit_create(sc_ctx* ctx, size_t depth, const size_t* k, con
     c->stride.push_back(circuit_stride(k[i]));
     total += 3 * c->stride[i];
   }
-  int rc = pool_alloc(ctx, (total + 1) / 2, &c->words);
+  int rc = c->words.alloc(ctx, (total + 1) / 2);
   hipError_t e = hipSuccess;
   for (size_t i = 0; i < depth && rc == SC_OK && e == hipSuccess; ++i) {
     const size_t n = (size_t)1 << k[i];
-    unsigned* w = (unsigned*)c->words + c->off[i];
+    unsigned* w = (unsigned*)c->words.get() + c->off[i];
     e = hipMemcpyAsync(w, gate_type[i], n * 4, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(w + c->stride[i], in0[i], n * 4, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(w + 2 * c->stride[i], in1[i], n * 4, hipMemcpyHostToDevice, ctx->stream);
@@ -154,7 +146,6 @@ extern "C" int sc_circuit_create(sc_ctx* ctx, size_t depth, const size_t* k, con
   if (rc == SC_OK && e == hipSuccess) e = sync_stream(ctx);   // the host arrays may go away after return
   if (rc == SC_OK && e != hipSuccess) rc = fail(ctx, SC_ERR_HIP, "sc_circuit_create: %s", hipGetErrorString(e));
   if (rc != SC_OK) {
-    pool_release(ctx, c->words);
     delete c;
     return rc;
   }
@@ -166,8 +157,7 @@ extern "C" int sc_circuit_destroy(sc_ctx* ctx, sc_circuit* c) {
   if (!c) return SC_OK;
   if (!ctx) return SC_ERR_ARG;
   if (c->ctx != ctx) return fail(ctx, SC_ERR_ARG, "sc_circuit_destroy: the circuit was made on another context");
-  pool_release(ctx, c->words);   // stream-ordered, like every pool block
-  delete c;
+  delete c;   // (its words go back stream-ordered, like every pool block)
   return SC_OK;
 }
 
@@ -177,9 +167,9 @@ extern "C" int sc_circuit_evaluate(sc_ctx* ctx, const sc_circuit* c, const sc_ta
   if (!values) return fail(ctx, SC_ERR_ARG, "sc_circuit_evaluate: values is null");
   SC_TRY(check_circuit_input(ctx, c, input, "sc_circuit_evaluate"));
   SC_TRY(set_device(ctx));
-  std::vector<sc_table*> v;
+  std::vector<TableBuf> v;
   SC_TRY(circuit_evaluate_impl(ctx, c, input, &v));
-  for (size_t i = 0; i < c->depth; ++i) values[i] = v[i];
+  for (size_t i = 0; i < c->depth; ++i) values[i] = v[i].release();
   return SC_OK;
 }
 
@@ -205,7 +195,7 @@ extern "C" int sc_gkr_prove_circuit(sc_ctx* ctx, const sc_circuit* c, const sc_t
   SC_TRY(check_circuit_input(ctx, c, input, "sc_gkr_prove_circuit"));
   SC_TRY(set_device(ctx));
   HostField hf(ctx->fp);
-  std::vector<sc_table*> values;
+  std::vector<TableBuf> values;   // (freed on return)
   SC_TRY(circuit_evaluate_impl(ctx, c, input, &values));   // Prover::new (lib.rs:346)
   int rc = SC_OK;
   if (outputs) {   // Begin (:363-367)
@@ -228,7 +218,7 @@ extern "C" int sc_gkr_prove_circuit(sc_ctx* ctx, const sc_circuit* c, const sc_t
   size_t round_base = 0, q_base = 0;
   for (size_t i = 0; i < c->depth && rc == SC_OK; ++i) {
     const size_t kn = c->k[i + 1], n = 2 * kn;
-    const sc_table* w_next = i + 1 == c->depth ? input : values[i + 1];
+    const sc_table* w_next = i + 1 == c->depth ? input : values[i + 1].get();
     sc_gkr_prover* pr = nullptr;
     rc = gkr_prover_create_circuit_impl(ctx, c, i, r.data(), w_next, &pr);   // start_round (:373-436)
     if (rc != SC_OK) break;
@@ -261,6 +251,5 @@ extern "C" int sc_gkr_prove_circuit(sc_ctx* ctx, const sc_circuit* c, const sc_t
     round_base += n;
     q_base += kn + 1;
   }
-  for (sc_table* v : values) (void)sc_table_free(ctx, v);
   return rc;
 }

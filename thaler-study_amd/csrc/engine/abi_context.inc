@@ -213,6 +213,7 @@ extern "C" int sc_ctx_set_option(sc_ctx* ctx, const char* key, int64_t value) {
   if (is_multi(ctx)) SC_TRY(multi_set_option(ctx, key, value));   // every shard first (they validate); then the handle's own copy
   if (k == "stat_reset") {
     ctx->stat_wait_ns = ctx->stat_launch_ns = 0;
+    ctx->pool_peak_words = ctx->pool_live_words;
     return SC_OK;
   }
   const OptionSpec* o = find_option(key);
@@ -226,11 +227,22 @@ extern "C" int sc_ctx_set_option(sc_ctx* ctx, const char* key, int64_t value) {
   return SC_OK;
 }
 
+// a pool statistic of one context, or its sum over the shards of a multi-device handle
+static int64_t pool_stat(const sc_ctx* ctx, size_t (*of)(const sc_ctx*)) {
+  if (!is_multi(ctx)) return (int64_t)of(ctx);
+  int64_t sum = 0;
+  for (const sc_ctx* sub : ctx->subs) sum += (int64_t)of(sub);
+  return sum;
+}
+
 extern "C" int sc_ctx_get_option(const sc_ctx* ctx, const char* key, int64_t* value) {
   if (!ctx || !key || !value) return SC_ERR_ARG;
   const std::string k(key);
   if (k == "stat_wait_ns") *value = (int64_t)(is_multi(ctx) ? ctx->subs[0]->stat_wait_ns : ctx->stat_wait_ns);
   else if (k == "stat_launch_ns") *value = (int64_t)(is_multi(ctx) ? ctx->subs[0]->stat_launch_ns : ctx->stat_launch_ns);
+  else if (k == "stat_pool_live_blocks") *value = pool_stat(ctx, [](const sc_ctx* c) { return c->pool_live.size(); });
+  else if (k == "stat_pool_live_words") *value = pool_stat(ctx, [](const sc_ctx* c) { return c->pool_live_words; });
+  else if (k == "stat_pool_peak_words") *value = pool_stat(ctx, [](const sc_ctx* c) { return c->pool_peak_words; });
   else if (k == "transport") *value = (int64_t)ctx->transport;   // 0 none, 1 RCCL, 2 host callbacks, 3 peer, 4 local (a multi-device handle and its shards)
   else if (k == "n_devices") *value = is_multi(ctx) ? (int64_t)ctx->subs.size() : 1;
   else if (k == "comm_nranks") {

@@ -86,7 +86,7 @@ static int multi_gkr_w_evaluate(sc_ctx* m, const sc_table* add, const sc_table* 
                                 const uint64_t* point, size_t n, uint64_t* out);
 static int multi_gkr_prover_create(sc_ctx* m, const sc_table* add, const sc_table* mul, const sc_table* w_b, const sc_table* w_c,
                                    sc_gkr_prover** out);
-static int multi_gather_to(sc_ctx* m, const sc_table* t, sc_ctx* dst, u64** out);
+static int multi_gather_to(sc_ctx* m, const sc_table* t, sc_ctx* dst, PoolBuf* out);
 
 extern "C" int sc_gkr_wiring(sc_ctx* ctx, const int32_t* gate_type, const uint32_t* in0, const uint32_t* in1, size_t k_i,
                              size_t k_next, const uint64_t* r_i, sc_table** add_out, sc_table** mul_out) {
@@ -103,41 +103,31 @@ extern "C" int sc_gkr_wiring(sc_ctx* ctx, const int32_t* gate_type, const uint32
     if ((gate_type[a] != 0 && gate_type[a] != 1) || in0[a] >= n_next || in1[a] >= n_next)
       return fail(ctx, SC_ERR_ARG, "sc_gkr_wiring: gate %zu is malformed", a);
   }
-  u64* eq = nullptr;
-  u64* gates = nullptr;  // [type | in0 | in1] as 32-bit words
-  sc_table *ta = nullptr, *tm = nullptr;
-  int rc = build_eq_table(ctx, r_i, (int)k_i, &eq);
-  if (rc == SC_OK) rc = pool_alloc(ctx, (3 * n_gates * 4 + 7) / 8 + 1, &gates);
-  if (rc == SC_OK) rc = new_table(ctx, len, &ta);
-  if (rc == SC_OK) rc = new_table(ctx, len, &tm);
-  if (rc == SC_OK) {
-    int* d_type = (int*)gates;
-    unsigned* d_in0 = (unsigned*)gates + n_gates;
-    unsigned* d_in1 = (unsigned*)gates + 2 * n_gates;
-    hipError_t e = hipMemcpyAsync(d_type, gate_type, n_gates * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_in0, in0, n_gates * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_in1, in1, n_gates * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(ta->d, 0, len * sizeof(u64), ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(tm->d, 0, len * sizeof(u64), ctx->stream);
-    if (e == hipSuccess) {
-      SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::gkr_wiring_scatter_kernel<F>), dim3(grid_for_wide(ctx, n_gates)),
-                                                      dim3(sc::kBlock), 0, ctx->stream, f, (const u64*)eq, (const int*)d_type,
-                                                      (const unsigned*)d_in0, (const unsigned*)d_in1, n_gates, (int)k_next,
-                                                      row_lo, (unsigned)rows, ta->d, tm->d));
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = sync_stream(ctx);
-    if (e != hipSuccess) rc = fail(ctx, SC_ERR_HIP, "sc_gkr_wiring: %s", hipGetErrorString(e));
+  TableBuf tm, ta;
+  PoolBuf gates, eq;  // gates: [type | in0 | in1] as 32-bit words
+  SC_TRY(build_eq_table(ctx, r_i, (int)k_i, &eq));
+  SC_TRY(gates.alloc(ctx, (3 * n_gates * 4 + 7) / 8 + 1));
+  SC_TRY(ta.alloc(ctx, len));
+  SC_TRY(tm.alloc(ctx, len));
+  int* d_type = (int*)gates.get();
+  unsigned* d_in0 = (unsigned*)gates.get() + n_gates;
+  unsigned* d_in1 = (unsigned*)gates.get() + 2 * n_gates;
+  hipError_t e = hipMemcpyAsync(d_type, gate_type, n_gates * 4, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_in0, in0, n_gates * 4, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_in1, in1, n_gates * 4, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(ta->d, 0, len * sizeof(u64), ctx->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(tm->d, 0, len * sizeof(u64), ctx->stream);
+  if (e == hipSuccess) {
+    SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::gkr_wiring_scatter_kernel<F>), dim3(grid_for_wide(ctx, n_gates)),
+                                                    dim3(sc::kBlock), 0, ctx->stream, f, (const u64*)eq, (const int*)d_type,
+                                                    (const unsigned*)d_in0, (const unsigned*)d_in1, n_gates, (int)k_next,
+                                                    row_lo, (unsigned)rows, ta->d, tm->d));
+    e = hipGetLastError();
   }
-  pool_release(ctx, eq);
-  pool_release(ctx, gates);
-  if (rc != SC_OK) {
-    sc_table_free(ctx, ta);
-    sc_table_free(ctx, tm);
-    return rc;
-  }
-  *add_out = ta;
-  *mul_out = tm;
+  if (e == hipSuccess) e = sync_stream(ctx);
+  if (e != hipSuccess) return fail(ctx, SC_ERR_HIP, "sc_gkr_wiring: %s", hipGetErrorString(e));
+  *add_out = ta.release();
+  *mul_out = tm.release();
   return SC_OK;
 }
 
@@ -152,23 +142,20 @@ extern "C" int sc_gkr_w_to_evaluations(sc_ctx* ctx, const sc_table* add, const s
   // is this rank's contiguous shard of the OUTPUT (top index bits = rank, i.e. a range of b), which needs every rank's
   // rows of add and mul - they are gathered whole for the duration of the call (round 4; SC_ERR_UNSUPPORTED before).
   const bool sharded = is_sharded(ctx) && ctx->world > 1;
-  u64 *add_full = nullptr, *mul_full = nullptr;
+  PoolBuf add_full, mul_full;
   if (sharded) {
     if (w.kb < ctx->log_world) return fail(ctx, SC_ERR_UNSUPPORTED, "gkr W to_evaluations: fewer values of b than ranks");
     SC_TRY(gather_pair(ctx, w.add, w.mul, add->len, &add_full, &mul_full));
   }
   const size_t total = (size_t)1 << (w.kb + w.kc), count = sharded ? total / (size_t)ctx->world : total;
   const size_t begin = sharded ? (size_t)ctx->rank * count : 0;
-  sc_table* t = nullptr;
-  int rc = new_table(ctx, count, &t);
-  if (rc == SC_OK) {
-    SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::gkr_to_evaluations_kernel<F>), dim3(grid_for_wide(ctx, count)),
-                                                    dim3(sc::kBlock), 0, ctx->stream, f, sharded ? add_full : w.add, sharded ? mul_full : w.mul,
-                                                    w.w_b, w.kb, w.w_c, w.kc, begin, count, t->d));
-  }
-  pool_release(ctx, add_full);   // stream-ordered
-  pool_release(ctx, mul_full);
-  if (rc != SC_OK) return rc;
+  TableBuf t;
+  SC_TRY(t.alloc(ctx, count));
+  SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::gkr_to_evaluations_kernel<F>), dim3(grid_for_wide(ctx, count)),
+                                                  dim3(sc::kBlock), 0, ctx->stream, f, sharded ? add_full.get() : w.add,
+                                                  sharded ? mul_full.get() : w.mul, w.w_b, w.kb, w.w_c, w.kc, begin, count, t->d));
+  add_full.reset();   // stream-ordered
+  mul_full.reset();
   return table_done(ctx, t, hipGetLastError(), "gkr to_evaluations", out);
 }
 
@@ -190,22 +177,15 @@ extern "C" int sc_gkr_w_fix_variables(sc_ctx* ctx, const sc_table* add, const sc
   SC_TRY(check_w(ctx, add, mul, w_b, w_c, &w));   // stay inside the shards, through the first device across the device bits)
   if (k > (size_t)(w.kb + w.kc)) return fail(ctx, SC_ERR_ARG, "gkr fix_variables: k=%zu > num_vars=%d", k, w.kb + w.kc);
   const size_t k_b = std::min<size_t>(k, (size_t)w.kb), k_c = k - k_b;   // round_polynomial.rs:60-63
-  sc_table *oa = nullptr, *om = nullptr, *ob = nullptr, *oc = nullptr;
-  int rc = sc_table_fix_variables(ctx, add, r, k, SC_ORDER_LE, &oa);
-  if (rc == SC_OK) rc = sc_table_fix_variables(ctx, mul, r, k, SC_ORDER_LE, &om);
-  if (rc == SC_OK) rc = sc_table_fix_variables(ctx, w_b, r, k_b, SC_ORDER_LE, &ob);
-  if (rc == SC_OK) rc = sc_table_fix_variables(ctx, w_c, r + k_b, k_c, SC_ORDER_LE, &oc);
-  if (rc != SC_OK) {
-    sc_table_free(ctx, oa);
-    sc_table_free(ctx, om);
-    sc_table_free(ctx, ob);
-    sc_table_free(ctx, oc);
-    return rc;
-  }
-  *add_out = oa;
-  *mul_out = om;
-  *w_b_out = ob;
-  *w_c_out = oc;
+  TableBuf oc, ob, om, oa;
+  SC_TRY(sc_table_fix_variables(ctx, add, r, k, SC_ORDER_LE, oa.out(ctx)));
+  SC_TRY(sc_table_fix_variables(ctx, mul, r, k, SC_ORDER_LE, om.out(ctx)));
+  SC_TRY(sc_table_fix_variables(ctx, w_b, r, k_b, SC_ORDER_LE, ob.out(ctx)));
+  SC_TRY(sc_table_fix_variables(ctx, w_c, r + k_b, k_c, SC_ORDER_LE, oc.out(ctx)));
+  *add_out = oa.release();
+  *mul_out = om.release();
+  *w_b_out = ob.release();
+  *w_c_out = oc.release();
   return SC_OK;
 }
 
@@ -243,21 +223,22 @@ struct sc_gkr_prover {
   size_t n_gates = 0;
   int* sp_type = nullptr;
   unsigned *sp_in0 = nullptr, *sp_in1 = nullptr;
-  u64* sp_val = nullptr;
-  u64* sp_words = nullptr;   // pool block backing sp_type / sp_in0 / sp_in1
+  PoolBuf sp_val;
+  PoolBuf sp_words;   // pool block backing sp_type / sp_in0 / sp_in1 (empty: the words are a circuit's)
   size_t num_vars = 0, next_round = 0;
   u64 c1 = 0;
   std::vector<u64> r;        // challenges received
   // current phase
   sc_prover* sub = nullptr;
   sc_table ta, tb;
-  u64 *TA = nullptr, *TB = nullptr;
+  PoolBuf TA, TB;
   // multi-device handle (round 4): `ctx` above is the handle's FIRST device - the 2^(k+1)-entry product proofs of both
   // phases run there, on whole tables - and every device streams its own rows of c of add / mul: dev[d] is a view of this
   // prover on device d (its parts of add and mul, its own whole copy of W_c).  W_b and W_c whole on the first device.
   sc_ctx* handle = nullptr;
   std::vector<sc_gkr_prover> dev;
-  std::vector<u64*> owned;     // [device] the whole copy of W_c (pool memory of that device); [n + 0] W_b whole on the first device
+  std::vector<PoolBuf> owned;  // [device] the whole copy of W_c (pool memory of that device); [n + 0] W_b whole on the first device
+                               // (a dev[] view owns nothing: its pointers are borrowed from the prover it belongs to)
 };
 
 namespace {
@@ -281,18 +262,15 @@ int gkr_dense_phase1(sc_gkr_prover* pr, u64* P, u64* L) {
   const size_t gx = rw.gx, chunks = rw.chunks, rows_per_chunk = rw.rows_per_chunk;
   if (rows_per_chunk > sc::GoldilocksMont::kAccMaxTerms)
     return fail(ctx, SC_ERR_UNSUPPORTED, "gkr: %zu rows per chunk exceed the lazy accumulator's capacity", rows_per_chunk);
-  u64 *pP = P, *pL = L;
+  PoolBuf rows_L, rows_P;   // the chunks' partial rows (given back on return, P's first)
   if (chunks > 1) {
-    SC_TRY(pool_alloc(ctx, chunks * M, &pP));
-    int rc = pool_alloc(ctx, chunks * M, &pL);
-    if (rc != SC_OK) {
-      pool_release(ctx, pP);
-      return rc;
-    }
+    SC_TRY(rows_P.alloc(ctx, chunks * M));
+    SC_TRY(rows_L.alloc(ctx, chunks * M));
   }
+  u64 *const pP = chunks > 1 ? rows_P.get() : P, *const pL = chunks > 1 ? rows_L.get() : L;
   const int nt = pr->add_len >= ((size_t)1 << ctx->nt_load_log) ? 1 : 0;
-  int rc = timer_begin(ctx, SC_KIND_GKR, pr->kc, 0, log2_of(pr->add_len), (u64)16 * pr->add_len + 8 * rows, (u64)16 * M);
-  if (rc == SC_OK) {
+  SC_TRY(timer_begin(ctx, SC_KIND_GKR, pr->kc, 0, log2_of(pr->add_len), (u64)16 * pr->add_len + 8 * rows, (u64)16 * M));
+  {
 #define SC_PHASE1(NT, PW)                                                                                                   \
   SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::gkr_phase1_kernel<F, NT, PW>), dim3((unsigned)gx, (unsigned)chunks),  \
                                                   dim3(sc::kBlock), 0, ctx->stream, f, pr->add, pr->mul, w, rows, rows_per_chunk, M, pP, pL))
@@ -313,31 +291,23 @@ int gkr_dense_phase1(sc_gkr_prover* pr, u64* P, u64* L) {
     }
     if (hipGetLastError() != hipSuccess) {
       poison(ctx);
-      rc = fail(ctx, SC_ERR_HIP, "gkr phase-1 launch failed");
+      return fail(ctx, SC_ERR_HIP, "gkr phase-1 launch failed");
     }
   }
-  if (rc == SC_OK) rc = timer_end(ctx);
-  if (chunks > 1) {
-    pool_release(ctx, pP);
-    pool_release(ctx, pL);
-  }
-  return rc;
+  return timer_end(ctx);
 }
 
 // sum a vector of residues over the ranks of a sharded context (split limbs, exact), in place
 int allreduce_residues(sc_ctx* ctx, u64* v, size_t n) {
   if (!is_sharded(ctx) || ctx->world == 1) return SC_OK;
-  u64* limbs = nullptr;
-  SC_TRY(pool_alloc(ctx, 2 * n, &limbs));
-  hipLaunchKernelGGL(sc::split_limbs_kernel, dim3(grid_for(ctx, n)), dim3(sc::kBlock), 0, ctx->stream, (const u64*)v, n, limbs);
-  int rc = allreduce_device(ctx, limbs, 2 * n);
-  if (rc == SC_OK) {
-    SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::recombine_limbs_kernel<F>), dim3(grid_for(ctx, n)), dim3(sc::kBlock), 0,
-                                                    ctx->stream, f, (const u64*)limbs, n, v));
-    if (hipGetLastError() != hipSuccess) rc = fail(ctx, SC_ERR_HIP, "recombine_limbs_kernel launch failed");
-  }
-  pool_release(ctx, limbs);
-  return rc;
+  PoolBuf limbs;
+  SC_TRY(limbs.alloc(ctx, 2 * n));
+  hipLaunchKernelGGL(sc::split_limbs_kernel, dim3(grid_for(ctx, n)), dim3(sc::kBlock), 0, ctx->stream, (const u64*)v, n, limbs.get());
+  SC_TRY(allreduce_device(ctx, limbs, 2 * n));
+  SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::recombine_limbs_kernel<F>), dim3(grid_for(ctx, n)), dim3(sc::kBlock), 0,
+                                                  ctx->stream, f, (const u64*)limbs, n, v));
+  if (hipGetLastError() != hipSuccess) return fail(ctx, SC_ERR_HIP, "recombine_limbs_kernel launch failed");
+  return SC_OK;
 }
 
 // Build the phase's tables and start its product prover.  which = 0: b variables; 1: c variables (b fixed at
@@ -347,138 +317,123 @@ int gkr_start_phase(sc_gkr_prover* pr, int which) {
   HostField hf(ctx->fp);
   if (pr->sub) sc_prover_destroy(pr->sub);
   pr->sub = nullptr;
-  pool_release(ctx, pr->TA);
-  pool_release(ctx, pr->TB);
-  pr->TA = pr->TB = nullptr;
+  pr->TA.reset();   // (before the new pair is built: its blocks are what the phase's tables are made in)
+  pr->TB.reset();
   const int kv = which == 0 ? pr->kb : pr->kc;   // variables of this phase
   const size_t n = (size_t)1 << kv;
-  u64 *X = nullptr, *Y = nullptr;   // P, L  or  add_r, mul_r
+  PoolBuf X, Y;   // P, L  or  add_r, mul_r
   u64 wstar = 0;
-  int rc = SC_OK;
   const bool sharded_dense = !pr->sparse && !pr->handle && is_sharded(ctx) && ctx->world > 1;
   if (pr->handle && !pr->sparse && pr->handle->subs.size() > 1) {
     // every device streams its rows of c; the first device adds / concatenates what the others send (hipMemcpyPeerAsync: xGMI)
     sc_ctx* m = pr->handle;
     const size_t N = m->subs.size();
-    u64* stage = nullptr;   // which == 0: [P rows | L rows], N rows of n words each; which == 1: [add_r | mul_r], n words each
-    rc = pool_alloc(ctx, 2 * N * n, &stage);
+    PoolBuf stage_buf;   // which == 0: [P rows | L rows], N rows of n words each; which == 1: [add_r | mul_r], n words each
+    SC_TRY(stage_buf.alloc(ctx, 2 * N * n));
+    u64* const stage = stage_buf;
     // (the other devices' streams write into it: nothing of this context's stream may still be using the recycled block)
-    if (rc == SC_OK && sync_stream(ctx) != hipSuccess) rc = fail(ctx, SC_ERR_HIP, "gkr: draining the first device's stream failed");
-    if (rc == SC_OK && which == 1) rc = evaluate_replicated(ctx, pr->w_b, (size_t)1 << pr->kb, pr->r.data(), &wstar);
-    if (rc == SC_OK)
-      rc = multi_run(m, [&](int d, sc_ctx* sub) -> int {
-        sc_gkr_prover& v = pr->dev[d];
-        SC_TRY(set_device(sub));
-        u64 *x = nullptr, *y = nullptr;
-        size_t lx = n, ly = n;
-        int r2;
-        if (which == 0) {
-          SC_TRY(pool_alloc(sub, n, &x));
-          r2 = pool_alloc(sub, n, &y);
-          if (r2 == SC_OK) r2 = gkr_dense_phase1(&v, x, y);
-        } else {
-          r2 = fold_chain(sub, v.add, v.add_len, pr->r.data(), (size_t)pr->kb, SC_ORDER_LE, &x, &lx);
-          if (r2 == SC_OK) r2 = fold_chain(sub, v.mul, v.add_len, pr->r.data(), (size_t)pr->kb, SC_ORDER_LE, &y, &ly);
-        }
-        if (r2 == SC_OK) {
-          // which == 0: row d of the P block and of the L block; which == 1: slice d of add_r and of mul_r
-          u64* dx = which == 0 ? stage + (size_t)d * n : stage + (size_t)d * lx;
-          u64* dy = which == 0 ? stage + N * n + (size_t)d * n : stage + n + (size_t)d * ly;
-          hipError_t e = hipMemcpyPeerAsync(dx, ctx->device, x, sub->device, lx * sizeof(u64), sub->stream);
-          if (e == hipSuccess) e = hipMemcpyPeerAsync(dy, ctx->device, y, sub->device, ly * sizeof(u64), sub->stream);
-          if (e == hipSuccess) e = hipStreamSynchronize(sub->stream);
-          if (e != hipSuccess) r2 = fail(sub, SC_ERR_HIP, "gkr: sending a device's part to the first device: %s", hipGetErrorString(e));
-        }
-        pool_release(sub, x);
-        pool_release(sub, y);
-        return r2;
-      });
-    if (rc == SC_OK) rc = set_device(ctx);
-    if (rc == SC_OK) rc = pool_alloc(ctx, n, &X);
-    if (rc == SC_OK) rc = pool_alloc(ctx, n, &Y);
-    if (rc == SC_OK) {
+    if (sync_stream(ctx) != hipSuccess) return fail(ctx, SC_ERR_HIP, "gkr: draining the first device's stream failed");
+    if (which == 1) SC_TRY(evaluate_replicated(ctx, pr->w_b, (size_t)1 << pr->kb, pr->r.data(), &wstar));
+    SC_TRY(multi_run(m, [&](int d, sc_ctx* sub) -> int {
+      sc_gkr_prover& v = pr->dev[d];
+      SC_TRY(set_device(sub));
+      PoolBuf y, x;   // (given back on return, x first: the copies are drained)
+      size_t lx = n, ly = n;
       if (which == 0) {
-        SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::sum_rows_kernel<F>), dim3(grid_for_wide(ctx, n), 2), dim3(sc::kBlock), 0, ctx->stream,
-                                                        f, (const u64*)stage, (const u64*)(stage + N * n), N, n, X, Y));
-        if (hipGetLastError() != hipSuccess) rc = fail(ctx, SC_ERR_HIP, "gkr: sum of the devices' P and L failed to launch");
+        SC_TRY(x.alloc(sub, n));
+        SC_TRY(y.alloc(sub, n));
+        SC_TRY(gkr_dense_phase1(&v, x, y));
       } else {
-        hipError_t e = hipMemcpyAsync(X, stage, n * sizeof(u64), hipMemcpyDeviceToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(Y, stage + n, n * sizeof(u64), hipMemcpyDeviceToDevice, ctx->stream);
-        if (e != hipSuccess) rc = fail(ctx, SC_ERR_HIP, "gkr: %s", hipGetErrorString(e));
+        SC_TRY(fold_chain(sub, v.add, v.add_len, pr->r.data(), (size_t)pr->kb, SC_ORDER_LE, &x, &lx));
+        SC_TRY(fold_chain(sub, v.mul, v.add_len, pr->r.data(), (size_t)pr->kb, SC_ORDER_LE, &y, &ly));
       }
+      // which == 0: row d of the P block and of the L block; which == 1: slice d of add_r and of mul_r
+      u64* dx = which == 0 ? stage + (size_t)d * n : stage + (size_t)d * lx;
+      u64* dy = which == 0 ? stage + N * n + (size_t)d * n : stage + n + (size_t)d * ly;
+      hipError_t e = hipMemcpyPeerAsync(dx, ctx->device, x, sub->device, lx * sizeof(u64), sub->stream);
+      if (e == hipSuccess) e = hipMemcpyPeerAsync(dy, ctx->device, y, sub->device, ly * sizeof(u64), sub->stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(sub->stream);
+      if (e != hipSuccess) return fail(sub, SC_ERR_HIP, "gkr: sending a device's part to the first device: %s", hipGetErrorString(e));
+      return SC_OK;
+    }));
+    SC_TRY(set_device(ctx));
+    SC_TRY(X.alloc(ctx, n));
+    SC_TRY(Y.alloc(ctx, n));
+    if (which == 0) {
+      SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::sum_rows_kernel<F>), dim3(grid_for_wide(ctx, n), 2), dim3(sc::kBlock), 0, ctx->stream,
+                                                      f, (const u64*)stage, (const u64*)(stage + N * n), N, n, X.get(), Y.get()));
+      if (hipGetLastError() != hipSuccess) return fail(ctx, SC_ERR_HIP, "gkr: sum of the devices' P and L failed to launch");
+    } else {
+      hipError_t e = hipMemcpyAsync(X, stage, n * sizeof(u64), hipMemcpyDeviceToDevice, ctx->stream);
+      if (e == hipSuccess) e = hipMemcpyAsync(Y, stage + n, n * sizeof(u64), hipMemcpyDeviceToDevice, ctx->stream);
+      if (e != hipSuccess) return fail(ctx, SC_ERR_HIP, "gkr: %s", hipGetErrorString(e));
     }
-    pool_release(ctx, stage);   // stream-ordered
+    // (the stage goes back here, stream-ordered)
   } else if (which == 0) {
-    rc = pool_alloc(ctx, n, &X);
-    if (rc == SC_OK) rc = pool_alloc(ctx, n, &Y);
-    if (rc == SC_OK && pr->sparse) {
+    SC_TRY(X.alloc(ctx, n));
+    SC_TRY(Y.alloc(ctx, n));
+    if (pr->sparse) {
       hipError_t e = hipMemsetAsync(X, 0, n * sizeof(u64), ctx->stream);
       if (e == hipSuccess) e = hipMemsetAsync(Y, 0, n * sizeof(u64), ctx->stream);
       if (e == hipSuccess) {
         SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::gkr_sparse_phase1_kernel<F>), dim3(grid_for_wide(ctx, pr->n_gates)),
                                                         dim3(sc::kBlock), 0, ctx->stream, f, (const u64*)pr->sp_val,
                                                         (const int*)pr->sp_type, (const unsigned*)pr->sp_in0,
-                                                        (const unsigned*)pr->sp_in1, pr->n_gates, pr->w_c, X, Y));
+                                                        (const unsigned*)pr->sp_in1, pr->n_gates, pr->w_c, X.get(), Y.get()));
         e = hipGetLastError();
       }
-      if (e != hipSuccess) rc = fail(ctx, SC_ERR_HIP, "gkr sparse phase 1: %s", hipGetErrorString(e));
-    } else if (rc == SC_OK) {
-      rc = gkr_dense_phase1(pr, X, Y);
+      if (e != hipSuccess) return fail(ctx, SC_ERR_HIP, "gkr sparse phase 1: %s", hipGetErrorString(e));
+    } else {
+      SC_TRY(gkr_dense_phase1(pr, X, Y));
       // sharded: every rank summed its own rows of c; P and L are the sums over the ranks
-      if (rc == SC_OK && sharded_dense) rc = allreduce_residues(ctx, X, n);
-      if (rc == SC_OK && sharded_dense) rc = allreduce_residues(ctx, Y, n);
+      if (sharded_dense) SC_TRY(allreduce_residues(ctx, X, n));
+      if (sharded_dense) SC_TRY(allreduce_residues(ctx, Y, n));
     }
   } else {
     // w* = W_b(r_b)
-    rc = evaluate_replicated(ctx, pr->w_b, (size_t)1 << pr->kb, pr->r.data(), &wstar);
-    if (rc == SC_OK && pr->sparse) {
-      u64* eqb = nullptr;
-      rc = build_eq_table(ctx, pr->r.data(), pr->kb, &eqb);
-      if (rc == SC_OK) rc = pool_alloc(ctx, n, &X);
-      if (rc == SC_OK) rc = pool_alloc(ctx, n, &Y);
-      if (rc == SC_OK) {
-        hipError_t e = hipMemsetAsync(X, 0, n * sizeof(u64), ctx->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(Y, 0, n * sizeof(u64), ctx->stream);
-        if (e == hipSuccess) {
-          SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::gkr_sparse_phase2_kernel<F>), dim3(grid_for_wide(ctx, pr->n_gates)),
-                                                          dim3(sc::kBlock), 0, ctx->stream, f, (const u64*)pr->sp_val,
-                                                          (const int*)pr->sp_type, (const unsigned*)pr->sp_in0,
-                                                          (const unsigned*)pr->sp_in1, pr->n_gates, (const u64*)eqb, X, Y));
-          e = hipGetLastError();
-        }
-        if (e != hipSuccess) rc = fail(ctx, SC_ERR_HIP, "gkr sparse phase 2: %s", hipGetErrorString(e));
+    SC_TRY(evaluate_replicated(ctx, pr->w_b, (size_t)1 << pr->kb, pr->r.data(), &wstar));
+    if (pr->sparse) {
+      PoolBuf eqb;   // (given back at the end of this block)
+      SC_TRY(build_eq_table(ctx, pr->r.data(), pr->kb, &eqb));
+      SC_TRY(X.alloc(ctx, n));
+      SC_TRY(Y.alloc(ctx, n));
+      hipError_t e = hipMemsetAsync(X, 0, n * sizeof(u64), ctx->stream);
+      if (e == hipSuccess) e = hipMemsetAsync(Y, 0, n * sizeof(u64), ctx->stream);
+      if (e == hipSuccess) {
+        SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::gkr_sparse_phase2_kernel<F>), dim3(grid_for_wide(ctx, pr->n_gates)),
+                                                        dim3(sc::kBlock), 0, ctx->stream, f, (const u64*)pr->sp_val,
+                                                        (const int*)pr->sp_type, (const unsigned*)pr->sp_in0,
+                                                        (const unsigned*)pr->sp_in1, pr->n_gates, (const u64*)eqb, X.get(), Y.get()));
+        e = hipGetLastError();
       }
-      pool_release(ctx, eqb);
-    } else if (rc == SC_OK) {
+      if (e != hipSuccess) return fail(ctx, SC_ERR_HIP, "gkr sparse phase 2: %s", hipGetErrorString(e));
+    } else {
       // add(r_b, .) and mul(r_b, .): fix the kb low variables of both tables (one streaming pass each)
       size_t la = 0, lm = 0;
-      rc = fold_chain(ctx, pr->add, pr->add_len, pr->r.data(), (size_t)pr->kb, SC_ORDER_LE, &X, &la);
-      if (rc == SC_OK) rc = fold_chain(ctx, pr->mul, pr->add_len, pr->r.data(), (size_t)pr->kb, SC_ORDER_LE, &Y, &lm);
-      if (rc == SC_OK && sharded_dense) {
-        // every rank holds its rows of c: gather the whole 2^kc-entry tables
-        u64 *gx = nullptr, *gy = nullptr;
-        rc = gather_pair(ctx, X, Y, la, &gx, &gy);
-        pool_release(ctx, X);
-        pool_release(ctx, Y);
-        X = gx;
-        Y = gy;
+      SC_TRY(fold_chain(ctx, pr->add, pr->add_len, pr->r.data(), (size_t)pr->kb, SC_ORDER_LE, &X, &la));
+      SC_TRY(fold_chain(ctx, pr->mul, pr->add_len, pr->r.data(), (size_t)pr->kb, SC_ORDER_LE, &Y, &lm));
+      if (sharded_dense) {
+        // every rank holds its rows of c: gather the whole 2^kc-entry tables (the rows go back as the gathered tables move in)
+        PoolBuf gx, gy;
+        SC_TRY(gather_pair(ctx, X, Y, la, &gx, &gy));
+        X = std::move(gx);
+        Y = std::move(gy);
       }
     }
   }
-  if (rc == SC_OK) rc = pool_alloc(ctx, 2 * n, &pr->TA);
-  if (rc == SC_OK) rc = pool_alloc(ctx, 2 * n, &pr->TB);
-  if (rc == SC_OK) {
+  SC_TRY(pr->TA.alloc(ctx, 2 * n));
+  SC_TRY(pr->TB.alloc(ctx, 2 * n));
+  {
     const u64 sY = which == 0 ? 0 : wstar, sZ = which == 0 ? hf.one() : wstar;
     const u64* Z = which == 0 ? Y : X;
     const u64* V = which == 0 ? pr->w_b : pr->w_c;
     SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::gkr_combine_kernel<F>), dim3(grid_for_wide(ctx, n)), dim3(sc::kBlock), 0,
                                                     ctx->stream, f, (const u64*)X, (const u64*)(which == 0 ? X : Y), sY, Z, sZ, V, n,
-                                                    pr->TA, pr->TB));
-    if (hipGetLastError() != hipSuccess) rc = fail(ctx, SC_ERR_HIP, "gkr_combine_kernel launch failed");
+                                                    pr->TA.get(), pr->TB.get()));
+    if (hipGetLastError() != hipSuccess) return fail(ctx, SC_ERR_HIP, "gkr_combine_kernel launch failed");
   }
-  pool_release(ctx, X);   // stream-ordered: the combine kernel is ahead of any reuse
-  pool_release(ctx, Y);
-  if (rc != SC_OK) return rc;
+  X.reset();   // stream-ordered: the combine kernel is ahead of any reuse
+  Y.reset();
   pr->ta.d = pr->TA;
   pr->ta.len = 2 * n;
   pr->tb.d = pr->TB;
@@ -505,20 +460,17 @@ extern "C" int sc_gkr_prover_create_sparse(sc_ctx* ctx, const int32_t* gate_type
     SC_TRY(multi_enter(ctx));
     SC_TRY(check_table(ctx, w_next, "sc_gkr_prover_create_sparse"));
     sc_ctx* first = ctx->subs[0];
-    u64* whole = nullptr;
+    PoolBuf whole;
     int rc = multi_gather_to(ctx, w_next, first, &whole);
     sc_table view;
     view.d = whole;
     view.len = w_next->len;
     sc_gkr_prover* pr = nullptr;
     if (rc == SC_OK) rc = sc_gkr_prover_create_sparse(first, gate_type, in0, in1, k_i, k_next, r_i, &view, &pr);
-    if (rc != SC_OK) {
-      pool_release(first, whole);
-      return fail(ctx, rc, "%s", first->err.c_str());
-    }
+    if (rc != SC_OK) return fail(ctx, rc, "%s", first->err.c_str());
     pr->handle = ctx;
-    pr->owned.assign(ctx->subs.size() + 1, nullptr);
-    pr->owned[ctx->subs.size()] = whole;   // released with the prover (on its context: the first device)
+    pr->owned.resize(ctx->subs.size() + 1);
+    pr->owned[ctx->subs.size()] = std::move(whole);   // released with the prover (on its context: the first device)
     *out = pr;
     return SC_OK;
   }
@@ -537,12 +489,12 @@ extern "C" int sc_gkr_prover_create_sparse(sc_ctx* ctx, const int32_t* gate_type
   pr->n_gates = n_gates;
   pr->w_b = pr->w_c = w_next->d;   // on a sharded context: the whole table, on every rank
   pr->kb = pr->kc = (int)k_next;
-  int rc = pool_alloc(ctx, (3 * n_gates * 4 + 7) / 8 + 1, &pr->sp_words);   // type | in0 | in1 as 32-bit words
+  int rc = pr->sp_words.alloc(ctx, (3 * n_gates * 4 + 7) / 8 + 1);   // type | in0 | in1 as 32-bit words
   if (rc == SC_OK) rc = build_eq_table(ctx, r_i, (int)k_i, &pr->sp_val);  // eq(r_i, a): the gate's weight
   if (rc == SC_OK) {
-    pr->sp_type = (int*)pr->sp_words;
-    pr->sp_in0 = (unsigned*)pr->sp_words + n_gates;
-    pr->sp_in1 = (unsigned*)pr->sp_words + 2 * n_gates;
+    pr->sp_type = (int*)pr->sp_words.get();
+    pr->sp_in0 = (unsigned*)pr->sp_words.get() + n_gates;
+    pr->sp_in1 = (unsigned*)pr->sp_words.get() + 2 * n_gates;
     hipError_t e = hipMemcpyAsync(pr->sp_type, gate_type, n_gates * 4, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(pr->sp_in0, in0, n_gates * 4, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(pr->sp_in1, in1, n_gates * 4, hipMemcpyHostToDevice, ctx->stream);
@@ -670,15 +622,7 @@ extern "C" int sc_gkr_prove(sc_ctx* ctx, const sc_table* add, const sc_table* mu
 extern "C" int sc_gkr_prover_destroy(sc_gkr_prover* pr) {
   if (!pr) return SC_OK;
   if (pr->sub) sc_prover_destroy(pr->sub);
-  pool_release(pr->ctx, pr->TA);
-  pool_release(pr->ctx, pr->TB);
-  pool_release(pr->ctx, pr->sp_words);
-  pool_release(pr->ctx, pr->sp_val);
-  if (pr->handle) {
-    const size_t N = pr->handle->subs.size();
-    for (size_t d = 0; d < pr->owned.size(); ++d) pool_release(d < N ? pr->handle->subs[d] : pr->ctx, pr->owned[d]);
-  }
-  delete pr;
+  delete pr;   // (every buffer it owns goes back to the pool of the context it came from)
   return SC_OK;
 }
 
@@ -698,17 +642,12 @@ static int multi_gkr_wiring(sc_ctx* m, const int32_t* gate_type, const uint32_t*
   const size_t N = m->subs.size();
   if (k_next > 15 || ((size_t)1 << k_next) < N) return fail(m, SC_ERR_ARG, "sc_gkr_wiring: 2^%zu rows of c over %zu devices", k_next, N);
   const size_t len = (size_t)1 << (2 * k_next);
-  sc_table *ta = new_multi_table(N, len), *tm = new_multi_table(N, len);
-  int rc = (ta && tm) ? multi_run(m, [&](int d, sc_ctx* sub) { return sc_gkr_wiring(sub, gate_type, in0, in1, k_i, k_next, r_i, &ta->parts[d], &tm->parts[d]); },
-                                  /*recoverable=*/true)
-                      : fail(m, SC_ERR_OOM, "host allocation failed");
-  if (rc != SC_OK) {
-    drop_multi_table(m, ta);
-    drop_multi_table(m, tm);
-    return rc;
-  }
-  *add_out = ta;
-  *mul_out = tm;
+  TableBuf tm(m, new_multi_table(N, len), /*multi=*/true), ta(m, new_multi_table(N, len), /*multi=*/true);
+  if (!ta.get() || !tm.get()) return fail(m, SC_ERR_OOM, "host allocation failed");
+  SC_TRY(multi_run(m, [&](int d, sc_ctx* sub) { return sc_gkr_wiring(sub, gate_type, in0, in1, k_i, k_next, r_i, &ta->parts[d], &tm->parts[d]); },
+                   /*recoverable=*/true));
+  *add_out = ta.release();
+  *mul_out = tm.release();
   return SC_OK;
 }
 
@@ -734,30 +673,22 @@ static int multi_gkr_w_evaluate(sc_ctx* m, const sc_table* add, const sc_table* 
 }
 
 // a whole copy of a handle's table on one of its devices (pool memory of `dst`)
-static int multi_gather_to(sc_ctx* m, const sc_table* t, sc_ctx* dst, u64** out) {
+static int multi_gather_to(sc_ctx* m, const sc_table* t, sc_ctx* dst, PoolBuf* out) {
   const size_t N = t->parts.size(), part = t->len / N;   // (N = 1: a table that lives whole on the first device)
   SC_TRY(set_device(dst));
-  u64* whole = nullptr;
-  SC_TRY(pool_alloc(dst, t->len, &whole));
+  PoolBuf whole;
+  SC_TRY(whole.alloc(dst, t->len));
   // the parts are read on dst's stream: whatever their own devices' streams are still writing into them (a table call of the
   // handle returns unsynchronised by design, e.g. sc_table_fix_variables) must have landed first - ADVICE r04
   for (size_t q = 0; q < N; ++q)
-    if (m->subs[q] != dst && hipStreamSynchronize(m->subs[q]->stream) != hipSuccess) {
-      pool_release(dst, whole);
+    if (m->subs[q] != dst && hipStreamSynchronize(m->subs[q]->stream) != hipSuccess)
       return fail(dst, SC_ERR_HIP, "gathering a table of the handle: draining device %zu's stream failed", q);
-    }
   for (size_t q = 0; q < N; ++q) {
     const hipError_t e = hipMemcpyPeerAsync(whole + q * part, dst->device, t->parts[q]->d, m->subs[q]->device, part * sizeof(u64), dst->stream);
-    if (e != hipSuccess) {
-      pool_release(dst, whole);
-      return fail(dst, SC_ERR_HIP, "gathering a table of the handle: %s", hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(dst, SC_ERR_HIP, "gathering a table of the handle: %s", hipGetErrorString(e));
   }
-  if (hipStreamSynchronize(dst->stream) != hipSuccess) {
-    pool_release(dst, whole);
-    return fail(dst, SC_ERR_HIP, "gathering a table of the handle: synchronize failed");
-  }
-  *out = whole;
+  if (hipStreamSynchronize(dst->stream) != hipSuccess) return fail(dst, SC_ERR_HIP, "gathering a table of the handle: synchronize failed");
+  *out = std::move(whole);
   return SC_OK;
 }
 
@@ -784,7 +715,7 @@ static int multi_gkr_prover_create(sc_ctx* m, const sc_table* add, const sc_tabl
   pr->add_len = add->parts[0]->len;
   pr->add = add->parts[0]->d;
   pr->mul = mul->parts[0]->d;
-  pr->owned.assign(N + 1, nullptr);
+  pr->owned.resize(N + 1);
   // W_c whole on every device (phase 1 reads the rows a device owns), W_b whole on the first one
   int rc = multi_run(m, [&](int d, sc_ctx* sub) { return multi_gather_to(m, w_c, sub, &pr->owned[d]); });
   if (rc == SC_OK) {

@@ -17,21 +17,20 @@ int matmul_impl(sc_ctx* ctx, const u64* A, const u64* B, size_t n, u64* C) {
   const size_t N = (size_t)1 << n, len = N * N;
   const int k = (int)n;
   const int which = matmul_kernel_of(ctx, n);
-  int rc = SC_OK;
   if (which == 1) {
     // scratch: A8 | B8t (eight byte planes each, rows padded to KP) | SA | SB (eight u32 sums per row / column)
     const size_t KP = std::max<size_t>(N, sc::kMatmulStepK), plane = N * KP;
     const size_t bytes = 16 * plane + 2 * 8 * N * sizeof(unsigned);
-    u64* scratch = nullptr;
-    SC_TRY(pool_alloc(ctx, (bytes + 7) / 8, &scratch));
-    unsigned char* a8 = reinterpret_cast<unsigned char*>(scratch);
+    PoolBuf scratch;   // (given back on return: stream-ordered reuse)
+    SC_TRY(scratch.alloc(ctx, (bytes + 7) / 8));
+    unsigned char* a8 = reinterpret_cast<unsigned char*>(scratch.get());
     unsigned char* b8t = a8 + 8 * plane;
     unsigned* sa = reinterpret_cast<unsigned*>(b8t + 8 * plane);
     unsigned* sb = sa + 8 * N;
-    if (hipMemsetAsync(sa, 0, 2 * 8 * N * sizeof(unsigned), ctx->stream) != hipSuccess) rc = fail(ctx, SC_ERR_HIP, "sc_matmul: memset failed");
+    if (hipMemsetAsync(sa, 0, 2 * 8 * N * sizeof(unsigned), ctx->stream) != hipSuccess) return fail(ctx, SC_ERR_HIP, "sc_matmul: memset failed");
     // repack: reads both matrices, writes the planes and the sums
-    if (rc == SC_OK) rc = timer_begin(ctx, SC_KIND_MATMUL, 0, k, 2 * k, (u64)16 * len, (u64)16 * plane + 64 * N);
-    if (rc == SC_OK) {
+    SC_TRY(timer_begin(ctx, SC_KIND_MATMUL, 0, k, 2 * k, (u64)16 * len, (u64)16 * plane + 64 * N));
+    {
       const size_t a_threads = N * (KP / 16), b_threads = N * (KP / std::min<size_t>(KP, sc::kMatmulBRun));
       const unsigned a_grid = (unsigned)std::min<size_t>((a_threads + sc::kBlock - 1) / sc::kBlock, (size_t)8 * ctx->num_cus);
       const unsigned b_grid = (unsigned)std::min<size_t>((b_threads + sc::kBlock - 1) / sc::kBlock, (size_t)8 * ctx->num_cus);
@@ -41,13 +40,13 @@ int matmul_impl(sc_ctx* ctx, const u64* A, const u64* B, size_t n, u64* C) {
       });
       if (hipGetLastError() != hipSuccess) {
         poison(ctx);
-        rc = fail(ctx, SC_ERR_HIP, "matmul_bytes kernel launch failed");
+        return fail(ctx, SC_ERR_HIP, "matmul_bytes kernel launch failed");
       }
-      if (rc == SC_OK) rc = timer_end(ctx);
+      SC_TRY(timer_end(ctx));
     }
     // product: every plane byte once, C once
-    if (rc == SC_OK) rc = timer_begin(ctx, SC_KIND_MATMUL, 1, k, 2 * k, (u64)16 * plane + 64 * N, (u64)8 * len);
-    if (rc == SC_OK) {
+    SC_TRY(timer_begin(ctx, SC_KIND_MATMUL, 1, k, 2 * k, (u64)16 * plane + 64 * N, (u64)8 * len));
+    {
       const size_t waves = (N / 16) * (N / 16);
       const unsigned grid = (unsigned)std::min<size_t>((waves + 3) / 4, (size_t)8 * ctx->num_cus);
       SC_DISPATCH_FIELD(ctx, F, f,
@@ -55,12 +54,10 @@ int matmul_impl(sc_ctx* ctx, const u64* A, const u64* B, size_t n, u64* C) {
                                            (const unsigned char*)a8, (const unsigned char*)b8t, (const unsigned*)sa, (const unsigned*)sb, k, KP, C));
       if (hipGetLastError() != hipSuccess) {
         poison(ctx);
-        rc = fail(ctx, SC_ERR_HIP, "matmul_mfma_kernel launch failed");
+        return fail(ctx, SC_ERR_HIP, "matmul_mfma_kernel launch failed");
       }
-      if (rc == SC_OK) rc = timer_end(ctx);
     }
-    pool_release(ctx, scratch);   // stream-ordered reuse
-    return rc;
+    return timer_end(ctx);
   }
   SC_TRY(timer_begin(ctx, SC_KIND_MATMUL, which, k, 2 * k, (u64)16 * len, (u64)8 * len));
   SC_DISPATCH_FIELD(ctx, F, f, {
@@ -89,13 +86,9 @@ extern "C" int sc_matmul(sc_ctx* ctx, const sc_table* A, const sc_table* B, size
   if (n > 14) return fail(ctx, SC_ERR_ARG, "sc_matmul: 2^%zu x 2^%zu matrices (at most 2^14 x 2^14)", n, n);
   if (A->len != ((size_t)1 << (2 * n))) return fail(ctx, SC_ERR_ARG, "sc_matmul: tables must have 2^(2n) = 2^%zu entries, not %zu", 2 * n, A->len);
   SC_TRY(set_device(ctx));
-  sc_table* out = nullptr;
-  SC_TRY(new_table(ctx, A->len, &out));
-  const int rc = matmul_impl(ctx, A->d, B->d, n, out->d);
-  if (rc != SC_OK) {
-    (void)sc_table_free(ctx, out);
-    return rc;
-  }
-  *C = out;
+  TableBuf out;
+  SC_TRY(out.alloc(ctx, A->len));
+  SC_TRY(matmul_impl(ctx, A->d, B->d, n, out->d));
+  *C = out.release();
   return SC_OK;
 }

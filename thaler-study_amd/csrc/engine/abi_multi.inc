@@ -104,11 +104,11 @@ namespace {
 
 struct FirstView {
   sc_table view;        // an ordinary table of subs[0] holding the whole of a handle's table (borrowed or `owned`)
-  u64* owned = nullptr;
+  PoolBuf owned;
 };
 int to_first(sc_ctx* m, const sc_table* t, FirstView* v) {
   sc_ctx* first = m->subs[0];
-  v->owned = nullptr;
+  v->owned.reset();
   v->view.len = t->len;
   if (t->parts.size() == 1) {   // single, or a handle over one device
     v->view.d = t->parts[0]->d;
@@ -118,47 +118,46 @@ int to_first(sc_ctx* m, const sc_table* t, FirstView* v) {
   v->view.d = v->owned;
   return SC_OK;
 }
-void drop_first(sc_ctx* m, FirstView* v) {
-  pool_release(m->subs[0], v->owned);
-  v->owned = nullptr;
-}
+void drop_first(FirstView* v) { v->owned.reset(); }
 // an ordinary table of subs[0] (consumed) -> a table of the handle
-int from_first(sc_ctx* m, sc_table* w, sc_table** out) {
+int from_first(sc_ctx* m, TableBuf&& w_in, sc_table** out) {
   sc_ctx* first = m->subs[0];
   const size_t N = m->subs.size();
-  if (N == 1 || w->len < N) {
+  if (N == 1 || w_in->len < N) {
+    TableBuf w(std::move(w_in));
     sc_table* t = new_multi_table(1, w->len);
-    if (!t) {
-      sc_table_free(first, w);
-      return fail(m, SC_ERR_OOM, "host allocation failed");
-    }
-    t->parts[0] = w;
+    if (!t) return fail(m, SC_ERR_OOM, "host allocation failed");
+    t->parts[0] = w.release();
     *out = t;
     return SC_OK;
   }
-  const size_t part = w->len / N;
-  sc_table* t = new_multi_table(N, w->len);
-  int rc = t ? SC_OK : fail(m, SC_ERR_OOM, "host allocation failed");
+  const size_t part = w_in->len / N;
+  TableBuf t(m, new_multi_table(N, w_in->len), /*multi=*/true);
+  TableBuf w(std::move(w_in));   // (goes back first)
+  if (!t.get()) return fail(m, SC_ERR_OOM, "host allocation failed");
   // every device allocates its part and drains its stream (the first device's stream writes into the recycled block)
-  if (rc == SC_OK)
-    rc = multi_run(m, [&](int d, sc_ctx* sub) -> int {
-      SC_TRY(set_device(sub));
-      SC_TRY(new_table(sub, part, &t->parts[d]));
-      SC_HIP(sub, hipStreamSynchronize(sub->stream));
-      return SC_OK;
-    }, /*recoverable=*/true);
-  if (rc == SC_OK) rc = set_device(first);
-  for (size_t q = 0; q < N && rc == SC_OK; ++q) {
+  SC_TRY(multi_run(m, [&](int d, sc_ctx* sub) -> int {
+    SC_TRY(set_device(sub));
+    SC_TRY(new_table(sub, part, &t->parts[d]));
+    SC_HIP(sub, hipStreamSynchronize(sub->stream));
+    return SC_OK;
+  }, /*recoverable=*/true));
+  SC_TRY(set_device(first));
+  for (size_t q = 0; q < N; ++q) {
     const hipError_t e = hipMemcpyPeerAsync(t->parts[q]->d, m->subs[q]->device, w->d + q * part, first->device, part * sizeof(u64), first->stream);
-    if (e != hipSuccess) rc = fail(m, SC_ERR_HIP, "scattering a table over the handle's devices: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(m, SC_ERR_HIP, "scattering a table over the handle's devices: %s", hipGetErrorString(e));
   }
-  if (rc == SC_OK && hipStreamSynchronize(first->stream) != hipSuccess) rc = fail(m, SC_ERR_HIP, "scattering a table over the handle's devices: synchronize failed");
-  sc_table_free(first, w);
-  if (rc != SC_OK) {
-    drop_multi_table(m, t);
-    return rc;
-  }
-  *out = t;
+  if (hipStreamSynchronize(first->stream) != hipSuccess) return fail(m, SC_ERR_HIP, "scattering a table over the handle's devices: synchronize failed");
+  w.reset();
+  *out = t.release();
+  return SC_OK;
+}
+// the two results of one call on the first device -> two tables of the handle (or none)
+int from_first_pair(sc_ctx* m, TableBuf&& wa, TableBuf&& wb, sc_table** a_out, sc_table** b_out) {
+  TableBuf ta;   // (adopted as a table the handle hands out: should the second fail, it is freed the way a caller would, sc_table_free on the handle)
+  SC_TRY(from_first(m, std::move(wa), ta.out(m)));
+  SC_TRY(from_first(m, std::move(wb), b_out));
+  *a_out = ta.release();
   return SC_OK;
 }
 // rc of a call made on the first device -> the handle's error
@@ -198,11 +197,11 @@ int via_first_table(sc_ctx* m, std::initializer_list<const sc_table*> ins, const
     if (rc != SC_OK) break;
     ++n;
   }
-  sc_table* w = nullptr;
-  if (rc == SC_OK) rc = on_first(m, [&](sc_ctx* first) { return op(first, v, &w); });
-  for (int i = 0; i < n; ++i) drop_first(m, &v[i]);
+  TableBuf w;
+  if (rc == SC_OK) rc = on_first(m, [&](sc_ctx* first) { return op(first, v, w.out(first)); });
+  for (int i = 0; i < n; ++i) drop_first(&v[i]);
   if (rc != SC_OK) return rc;
-  return from_first(m, w, out);
+  return from_first(m, std::move(w), out);
 }
 // op(first, views) -> words on the host
 int via_first_value(sc_ctx* m, std::initializer_list<const sc_table*> ins, const std::function<int(sc_ctx*, FirstView*)>& op) {
@@ -214,7 +213,7 @@ int via_first_value(sc_ctx* m, std::initializer_list<const sc_table*> ins, const
     ++n;
   }
   if (rc == SC_OK) rc = on_first(m, [&](sc_ctx* first) { return op(first, v); });
-  for (int i = 0; i < n; ++i) drop_first(m, &v[i]);
+  for (int i = 0; i < n; ++i) drop_first(&v[i]);
   return rc;
 }
 
@@ -225,9 +224,9 @@ int via_first_value(sc_ctx* m, std::initializer_list<const sc_table*> ins, const
 static int multi_table_upload(sc_ctx* m, const uint64_t* host, size_t len, sc_table** out) {
   SC_TRY(multi_enter(m));
   if (is_pow2(len) && len < m->subs.size()) {   // fewer entries than devices: whole on the first device
-    sc_table* w = nullptr;
-    SC_TRY(on_first(m, [&](sc_ctx* first) { return sc_table_upload(first, host, len, &w); }));
-    return from_first(m, w, out);
+    TableBuf w;
+    SC_TRY(on_first(m, [&](sc_ctx* first) { return sc_table_upload(first, host, len, w.out(first)); }));
+    return from_first(m, std::move(w), out);
   }
   SC_TRY(check_multi_len(m, len, "sc_table_upload"));
   const size_t part = len / m->subs.size();
@@ -237,9 +236,9 @@ static int multi_table_upload(sc_ctx* m, const uint64_t* host, size_t len, sc_ta
 static int multi_table_generate(sc_ctx* m, uint64_t seed, uint64_t start, size_t len, sc_table** out) {
   SC_TRY(multi_enter(m));
   if (is_pow2(len) && len < m->subs.size()) {
-    sc_table* w = nullptr;
-    SC_TRY(on_first(m, [&](sc_ctx* first) { return sc_table_generate(first, seed, start, len, &w); }));
-    return from_first(m, w, out);
+    TableBuf w;
+    SC_TRY(on_first(m, [&](sc_ctx* first) { return sc_table_generate(first, seed, start, len, w.out(first)); }));
+    return from_first(m, std::move(w), out);
   }
   SC_TRY(check_multi_len(m, len, "sc_table_generate"));
   const size_t part = len / m->subs.size();
@@ -251,9 +250,9 @@ static int multi_table_clone(sc_ctx* m, const sc_table* t, sc_table** out) {
   SC_TRY(multi_enter(m));
   SC_TRY(check_table(m, t, "sc_table_clone"));
   if (is_single(m, t)) {
-    sc_table* w = nullptr;
-    SC_TRY(on_first(m, [&](sc_ctx* first) { return sc_table_clone(first, t->parts[0], &w); }));
-    return from_first(m, w, out);
+    TableBuf w;
+    SC_TRY(on_first(m, [&](sc_ctx* first) { return sc_table_clone(first, t->parts[0], w.out(first)); }));
+    return from_first(m, std::move(w), out);
   }
   return make_multi_table(m, t->len, [&](int d, sc_ctx* sub, sc_table** p) { return sc_table_clone(sub, t->parts[d], p); }, out);
 }
@@ -336,13 +335,13 @@ static int multi_prod2_sum(sc_ctx* m, const sc_table* a, const sc_table* b, uint
     // one entry per shard: the partial sum is the single product
     return multi_sums(m, 1, [&](int d, sc_ctx* sub, bool* mb) -> int {
       SC_TRY(set_device(sub));
-      u64* prod = nullptr;
-      SC_TRY(pool_alloc(sub, 1, &prod));
+      PoolBuf prod;
+      SC_TRY(prod.alloc(sub, 1));
       SC_DISPATCH_FIELD(sub, F, f, hipLaunchKernelGGL((sc::mul_kernel<F>), dim3(1), dim3(sc::kBlock), 0, sub->stream, f,
-                                                      (const u64*)a->parts[d]->d, (const u64*)b->parts[d]->d, prod, (size_t)1));
+                                                      (const u64*)a->parts[d]->d, (const u64*)b->parts[d]->d, prod.get(), (size_t)1));
       SC_DISPATCH_FIELD(sub, F, f, hipLaunchKernelGGL((sc::scale_split_kernel<F>), dim3(1), dim3(64), 0, sub->stream, f,
                                                       (const u64*)prod, hf.one(), sub->d_sums));
-      pool_release(sub, prod);
+      prod.reset();
       SC_HIP(sub, hipGetLastError());
       *mb = false;
       return SC_OK;
@@ -366,42 +365,26 @@ static int multi_prod2_fold_and_sums(sc_ctx* m, const sc_table* a, const sc_tabl
     FirstView va, vb;
     SC_TRY(to_first(m, a, &va));
     int rc = to_first(m, b, &vb);
-    sc_table *wa = nullptr, *wb = nullptr;
-    if (rc == SC_OK) rc = on_first(m, [&](sc_ctx* first) { return sc_prod2_fold_and_sums(first, &va.view, &vb.view, r, &wa, &wb, out_e); });
-    drop_first(m, &va);
-    drop_first(m, &vb);
+    TableBuf wb, wa;
+    if (rc == SC_OK) rc = on_first(m, [&](sc_ctx* first) { return sc_prod2_fold_and_sums(first, &va.view, &vb.view, r, wa.out(first), wb.out(first), out_e); });
+    drop_first(&va);
+    drop_first(&vb);
     if (rc != SC_OK) return rc;
-    rc = from_first(m, wa, a_out);
-    if (rc != SC_OK) {
-      sc_table_free(m->subs[0], wb);
-      return rc;
-    }
-    rc = from_first(m, wb, b_out);
-    if (rc != SC_OK) {
-      drop_multi_table(m, *a_out);
-      *a_out = nullptr;
-    }
-    return rc;
+    return from_first_pair(m, std::move(wa), std::move(wb), a_out, b_out);
   }
-  sc_table *ta = new_multi_table(m->subs.size(), a->len / 2), *tb = new_multi_table(m->subs.size(), a->len / 2);
-  int rc = (ta && tb) ? SC_OK : fail(m, SC_ERR_OOM, "host allocation failed");
+  TableBuf tb(m, new_multi_table(m->subs.size(), a->len / 2), /*multi=*/true), ta(m, new_multi_table(m->subs.size(), a->len / 2), /*multi=*/true);
+  if (!ta.get() || !tb.get()) return fail(m, SC_ERR_OOM, "host allocation failed");
   const bool across = m->subs.size() > 1;
-  if (rc == SC_OK)
-    rc = multi_sums(m, 3, [&](int d, sc_ctx* sub, bool* mb) -> int {
-      SC_TRY(set_device(sub));
-      SC_TRY(new_table(sub, part / 2, &ta->parts[d]));
-      SC_TRY(new_table(sub, part / 2, &tb->parts[d]));
-      return launch_pass(sub, 1, 1, a->parts[d]->d, b->parts[d]->d, ta->parts[d]->d, tb->parts[d]->d, r, nv, across, mb);
-    }, out_e);
-  if (rc != SC_OK) {
-    drop_multi_table(m, ta);
-    drop_multi_table(m, tb);
-    return rc;
-  }
+  SC_TRY(multi_sums(m, 3, [&](int d, sc_ctx* sub, bool* mb) -> int {
+    SC_TRY(set_device(sub));
+    SC_TRY(new_table(sub, part / 2, &ta->parts[d]));
+    SC_TRY(new_table(sub, part / 2, &tb->parts[d]));
+    return launch_pass(sub, 1, 1, a->parts[d]->d, b->parts[d]->d, ta->parts[d]->d, tb->parts[d]->d, r, nv, across, mb);
+  }, out_e));
   HostField hf(m->fp);
   out_e[2] = eval2_from_inf(hf, out_e[0], out_e[1], out_e[2]);
-  *a_out = ta;
-  *b_out = tb;
+  *a_out = ta.release();
+  *b_out = tb.release();
   return SC_OK;
 }
 
@@ -422,65 +405,46 @@ static int multi_matmul_g_new(sc_ctx* m, const sc_table* A, const sc_table* B, s
     FirstView va, vb;
     SC_TRY(to_first(m, A, &va));
     int rc = to_first(m, B, &vb);
-    sc_table *wa = nullptr, *wb = nullptr;
-    if (rc == SC_OK) rc = on_first(m, [&](sc_ctx* first) { return sc_matmul_g_new(first, &va.view, &vb.view, n, point, &wa, &wb); });
-    drop_first(m, &va);
-    drop_first(m, &vb);
+    TableBuf wb, wa;
+    if (rc == SC_OK) rc = on_first(m, [&](sc_ctx* first) { return sc_matmul_g_new(first, &va.view, &vb.view, n, point, wa.out(first), wb.out(first)); });
+    drop_first(&va);
+    drop_first(&vb);
     if (rc != SC_OK) return rc;
-    rc = from_first(m, wa, a_out);
-    if (rc != SC_OK) {
-      sc_table_free(m->subs[0], wb);
-      return rc;
-    }
-    rc = from_first(m, wb, b_out);
-    if (rc != SC_OK) {
-      drop_multi_table(m, *a_out);
-      *a_out = nullptr;
-    }
-    return rc;
+    return from_first_pair(m, std::move(wa), std::move(wb), a_out, b_out);
   }
   if (n < (size_t)g || n == 0) return fail(m, n == 0 && N == 1 ? SC_ERR_UNSUPPORTED : SC_ERR_ARG, "sc_matmul_g_new: 2^%zu rows cannot be split over %zu devices", n, N);
   const size_t side = (size_t)1 << n, rows_local = side >> g, cols_local = side >> g;
   if (N == 1) {
-    sc_table *ta = new_multi_table(1, side), *tb = new_multi_table(1, side);
-    int rc = (ta && tb) ? sc_matmul_g_new(m->subs[0], A->parts[0], B->parts[0], n, point, &ta->parts[0], &tb->parts[0])
-                        : fail(m, SC_ERR_OOM, "host allocation failed");
-    if (rc != SC_OK) {
-      if (ta && tb) rc = fail(m, rc, "%s", m->subs[0]->err.c_str());
-      drop_multi_table(m, ta);
-      drop_multi_table(m, tb);
-      return rc;
-    }
-    *a_out = ta;
-    *b_out = tb;
+    TableBuf tb(m, new_multi_table(1, side), /*multi=*/true), ta(m, new_multi_table(1, side), /*multi=*/true);
+    if (!ta.get() || !tb.get()) return fail(m, SC_ERR_OOM, "host allocation failed");
+    const int rc = sc_matmul_g_new(m->subs[0], A->parts[0], B->parts[0], n, point, &ta->parts[0], &tb->parts[0]);
+    if (rc != SC_OK) return fail(m, rc, "%s", m->subs[0]->err.c_str());
+    *a_out = ta.release();
+    *b_out = tb.release();
     return SC_OK;
   }
   if (cols_local < 2) return fail(m, SC_ERR_UNSUPPORTED, "sc_matmul_g_new: fewer than two columns per device");
-  sc_table *ta = new_multi_table(N, side), *tb = new_multi_table(N, side);
-  if (!ta || !tb) {
-    drop_multi_table(m, ta);
-    drop_multi_table(m, tb);
-    return fail(m, SC_ERR_OOM, "host allocation failed");
-  }
-  u64* stage[kMaxSubs] = {};   // stage[q]: N partial blocks of device q's columns, [source][cols_local]
-  u64* partial[kMaxSubs] = {};
+  TableBuf tb(m, new_multi_table(N, side), /*multi=*/true), ta(m, new_multi_table(N, side), /*multi=*/true);
+  if (!ta.get() || !tb.get()) return fail(m, SC_ERR_OOM, "host allocation failed");
+  PoolBuf stage[kMaxSubs];   // stage[q]: N partial blocks of device q's columns, [source][cols_local]
+  PoolBuf partial[kMaxSubs];
   // phase 1: partial vectors, scattered by column block
   // (stage[d] is written by the OTHER devices' streams: a pool block is stream-ordered on its own context's stream only, so its
   // owner drains that stream before anyone else may touch the block - ADVICE r04; multi_run returns when every device has)
   int rc = multi_run(m, [&](int d, sc_ctx* sub) -> int {
     SC_TRY(set_device(sub));
-    SC_TRY(pool_alloc(sub, N * cols_local, &stage[d]));
-    SC_TRY(pool_alloc(sub, side, &partial[d]));
+    SC_TRY(stage[d].alloc(sub, N * cols_local));
+    SC_TRY(partial[d].alloc(sub, side));
     SC_HIP(sub, hipStreamSynchronize(sub->stream));
     return SC_OK;
   });
   if (rc == SC_OK)
     rc = multi_run(m, [&](int d, sc_ctx* sub) -> int {
       SC_TRY(set_device(sub));
-      u64* eq = nullptr;
+      PoolBuf eq;
       SC_TRY(build_eq_table(sub, point, (int)n, &eq));
-      int r2 = coldot(sub, A->parts[d]->d, eq + (size_t)d * rows_local, rows_local, side, partial[d]);
-      pool_release(sub, eq);
+      const int r2 = coldot(sub, A->parts[d]->d, eq + (size_t)d * rows_local, rows_local, side, partial[d]);
+      eq.reset();
       SC_TRY(r2);
       for (size_t q = 0; q < N; ++q)
         SC_HIP(sub, hipMemcpyPeerAsync(stage[q] + (size_t)d * cols_local, m->subs[q]->device, partial[d] + q * cols_local, sub->device,
@@ -497,28 +461,22 @@ static int multi_matmul_g_new(sc_ctx* m, const sc_table* A, const sc_table* B, s
                                                       sub->stream, f, (const u64*)stage[d], (const u64*)stage[d], N, cols_local,
                                                       ta->parts[d]->d, ta->parts[d]->d));
       SC_HIP(sub, hipGetLastError());
-      sc_table* fb = new (std::nothrow) sc_table;
-      if (!fb) return fail(sub, SC_ERR_OOM, "host allocation failed");
-      const int r2 = fold_chain(sub, B->parts[d]->d, B->parts[d]->len, point + n, n, SC_ORDER_LE, &fb->d, &fb->len);
-      if (r2 != SC_OK) {
-        delete fb;
-        return r2;
-      }
-      tb->parts[d] = fb;
+      PoolBuf folded;
+      size_t folded_len = 0;
+      SC_TRY(fold_chain(sub, B->parts[d]->d, B->parts[d]->len, point + n, n, SC_ORDER_LE, &folded, &folded_len));
+      TableBuf fb;
+      SC_TRY(fb.wrap(sub, std::move(folded), folded_len));
+      tb->parts[d] = fb.release();
       SC_HIP(sub, hipStreamSynchronize(sub->stream));
       return SC_OK;
     });
   for (size_t d = 0; d < N; ++d) {
-    pool_release(m->subs[d], stage[d]);
-    pool_release(m->subs[d], partial[d]);
+    stage[d].reset();
+    partial[d].reset();
   }
-  if (rc != SC_OK) {
-    drop_multi_table(m, ta);
-    drop_multi_table(m, tb);
-    return rc;
-  }
-  *a_out = ta;
-  *b_out = tb;
+  SC_TRY(rc);
+  *a_out = ta.release();
+  *b_out = tb.release();
   return SC_OK;
 }
 

@@ -9,7 +9,7 @@ struct sc_merkle_tree {
   const sc_ctx* ctx = nullptr;
   const sc_table* t = nullptr;   // borrowed: must outlive the tree
   int n = 0, lb = 0;
-  u64* d_levels = nullptr;
+  PoolBuf d_levels;
   uint32_t root[8] = {};
 };
 
@@ -64,7 +64,7 @@ int grid_extend_impl(sc_ctx* ctx, const u64* in, size_t m, u64* out, u64* scratc
 // tree in one block; the root comes back to the host.
 int merkle_build(sc_ctx* ctx, sc_merkle_tree* tr) {
   const int n = tr->n, lb = tr->lb;
-  u32* in = reinterpret_cast<u32*>(tr->d_levels);
+  u32* in = reinterpret_cast<u32*>(tr->d_levels.get());
   u64 in_nodes = (u64)1 << (n - lb);
   SC_TRY(timer_begin(ctx, SC_KIND_MERKLE, 0, lb, n, (u64)8 << n, 32 * in_nodes));
   SC_DISPATCH_FIELD(ctx, F, f,
@@ -91,7 +91,7 @@ int merkle_build(sc_ctx* ctx, sc_merkle_tree* tr) {
     SC_TRY(timer_end(ctx));
   }
   const u64 total = ((u64)2 << (n - lb)) - 1;
-  SC_HIP(ctx, hipMemcpyAsync(tr->root, reinterpret_cast<const u32*>(tr->d_levels) + 8 * (total - 1), 32, hipMemcpyDeviceToHost,
+  SC_HIP(ctx, hipMemcpyAsync(tr->root, reinterpret_cast<const u32*>(tr->d_levels.get()) + 8 * (total - 1), 32, hipMemcpyDeviceToHost,
                              ctx->stream));
   SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SC_OK;
@@ -143,13 +143,12 @@ extern "C" int sc_table_extend_grid(sc_ctx* ctx, const sc_table* t, size_t m, sc
   size_t N = 1;
   while (N < pm) N <<= 1;
   SC_TRY(set_device(ctx));
-  sc_table* o = nullptr;
-  SC_TRY(new_table(ctx, N, &o));
-  int rc = SC_OK;
+  TableBuf o;
+  SC_TRY(o.alloc(ctx, N));
   if (m == 0) {
     if (hipMemcpyAsync(o->d, t->d, sizeof(u64), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) {
       poison(ctx);
-      rc = fail(ctx, SC_ERR_HIP, "sc_table_extend_grid: copy failed");
+      return fail(ctx, SC_ERR_HIP, "sc_table_extend_grid: copy failed");
     }
   } else {
     // the stages that do not write `out` write scratch: the largest of them, p^(s+1) 2^(m-s-1) for m-1-s odd
@@ -158,20 +157,15 @@ extern "C" int sc_table_extend_grid(sc_ctx* ctx, const sc_table* t, size_t m, sc
       if ((m - 1 - s) % 2 == 1) scratch_words = std::max(scratch_words, (E * p) << (m - 1 - s));
       E *= p;
     }
-    u64* scratch = nullptr;
-    if (scratch_words) rc = pool_alloc(ctx, scratch_words, &scratch);
-    if (rc == SC_OK) rc = grid_extend_impl(ctx, t->d, m, o->d, scratch);
-    pool_release(ctx, scratch);   // stream-ordered reuse
+    PoolBuf scratch;   // (given back at the end of this block: stream-ordered reuse)
+    if (scratch_words) SC_TRY(scratch.alloc(ctx, scratch_words));
+    SC_TRY(grid_extend_impl(ctx, t->d, m, o->d, scratch));
   }
-  if (rc == SC_OK && N > pm && hipMemsetAsync(o->d + pm, 0, (N - pm) * sizeof(u64), ctx->stream) != hipSuccess) {
+  if (N > pm && hipMemsetAsync(o->d + pm, 0, (N - pm) * sizeof(u64), ctx->stream) != hipSuccess) {
     poison(ctx);
-    rc = fail(ctx, SC_ERR_HIP, "sc_table_extend_grid: memset failed");
+    return fail(ctx, SC_ERR_HIP, "sc_table_extend_grid: memset failed");
   }
-  if (rc != SC_OK) {
-    (void)sc_table_free(ctx, o);
-    return rc;
-  }
-  *out = o;
+  *out = o.release();
   return SC_OK;
 }
 
@@ -190,10 +184,9 @@ extern "C" int sc_merkle_commit(sc_ctx* ctx, const sc_table* t, sc_merkle_tree**
   tr->t = t;
   tr->n = n;
   tr->lb = std::min(n, sc::kMerkleBase);
-  int rc = pool_alloc(ctx, 4 * (((size_t)2 << (n - tr->lb)) - 1), &tr->d_levels);
+  int rc = tr->d_levels.alloc(ctx, 4 * (((size_t)2 << (n - tr->lb)) - 1));
   if (rc == SC_OK) rc = merkle_build(ctx, tr);
   if (rc != SC_OK) {
-    pool_release(ctx, tr->d_levels);
     delete tr;
     return rc;
   }
@@ -228,8 +221,8 @@ extern "C" int sc_merkle_open(sc_ctx* ctx, const sc_merkle_tree* tr, const uint6
       return fail(ctx, SC_ERR_ARG, "sc_merkle_open: index %llu of opening %zu is not below N = 2^%d", (unsigned long long)index[q], q, n);
   SC_TRY(set_device(ctx));
   const size_t chunk = std::min(count, kOpenChunk);
-  u64* buf = nullptr;
-  SC_TRY(pool_alloc(ctx, chunk * (1 + per + 4 * (size_t)ns), &buf));
+  PoolBuf buf;
+  SC_TRY(buf.alloc(ctx, chunk * (1 + per + 4 * (size_t)ns)));
   u64* d_idx = buf;
   u64* d_vals = d_idx + chunk;
   u32* d_sib = reinterpret_cast<u32*>(d_vals + chunk * per);
@@ -248,7 +241,7 @@ extern "C" int sc_merkle_open(sc_ctx* ctx, const sc_merkle_tree* tr, const uint6
     if (rc != SC_OK) break;
     SC_DISPATCH_FIELD(ctx, F, f,
                       hipLaunchKernelGGL((sc::merkle_open_kernel<F>), dim3(pcs_grid(ctx, c)), dim3(sc::kBlock), 0, ctx->stream, f,
-                                         (const u64*)tr->t->d, reinterpret_cast<const u32*>(tr->d_levels), (const u64*)d_idx, (u32)c, n,
+                                         (const u64*)tr->t->d, reinterpret_cast<const u32*>(tr->d_levels.get()), (const u64*)d_idx, (u32)c, n,
                                          lb, d_vals, d_sib));
     rc = pcs_launched(ctx, "merkle_open_kernel");
     if (rc == SC_OK) rc = timer_end(ctx);
@@ -263,14 +256,12 @@ extern "C" int sc_merkle_open(sc_ctx* ctx, const sc_merkle_tree* tr, const uint6
     for (size_t q = 0; q < c; ++q)
       merkle_path_host(n, lb, index[q0 + q], &hv[q * per], &hs[q * ns * 8], &leaves[q0 + q], paths ? paths + (q0 + q) * 32 * n : nullptr);
   }
-  pool_release(ctx, buf);
   return rc;
 }
 
 extern "C" int sc_merkle_tree_destroy(sc_ctx* ctx, sc_merkle_tree* tr) {
   if (!tr) return SC_OK;
   if (!ctx || tr->ctx != ctx) return SC_ERR_ARG;
-  pool_release(ctx, tr->d_levels);
   delete tr;
   return SC_OK;
 }

@@ -15,8 +15,7 @@ struct ProverShard {
   sc_ctx* ctx = nullptr;
   const u64* cur_a = nullptr;   // the caller's tables (borrowed, never written) until the first folding pass
   const u64* cur_b = nullptr;
-  u64* own_a = nullptr;  // pool buffers backing cur_* when they are not the caller's (or the context's pinned tail buffer)
-  u64* own_b = nullptr;
+  PoolBuf own_a, own_b;  // what backs cur_* when they are not the caller's: pool buffers (or the prover's slot of the context's pinned tail buffer)
 };
 struct sc_prover {
   sc_ctx* ctx = nullptr;
@@ -340,33 +339,24 @@ int launches_left(const PlanOpts& o, size_t num_vars, size_t j, int kf, int cur_
 }
 
 // all-gather both tables of a sharded prover into pool buffers (any transport)
-int gather_pair(sc_ctx* ctx, const u64* a, const u64* b, size_t len, u64** fa, u64** fb) {
+int gather_pair(sc_ctx* ctx, const u64* a, const u64* b, size_t len, PoolBuf* fa, PoolBuf* fb) {
+  PoolBuf ga, gb;
   if (ctx->transport == Transport::kPeer) {
-    u64 *ga = nullptr, *gb = nullptr;
-    SC_TRY(pool_alloc(ctx, len * ctx->world, &ga));
-    int rc = pool_alloc(ctx, len * ctx->world, &gb);
-    if (rc == SC_OK) rc = peer_gather(ctx, a, b, len, ga, gb);
-    if (rc != SC_OK) {
-      pool_release(ctx, ga);
-      pool_release(ctx, gb);
-      return rc;
-    }
-    *fa = ga;
-    *fb = gb;
-    return SC_OK;
+    SC_TRY(ga.alloc(ctx, len * ctx->world));
+    SC_TRY(gb.alloc(ctx, len * ctx->world));
+    SC_TRY(peer_gather(ctx, a, b, len, ga, gb));
+  } else {
+    SC_TRY(gather_table(ctx, a, len, &ga));
+    SC_TRY(gather_table(ctx, b, len, &gb));
   }
-  SC_TRY(gather_table(ctx, a, len, fa));
-  const int rc = gather_table(ctx, b, len, fb);
-  if (rc != SC_OK) {
-    pool_release(ctx, *fa);
-    *fa = nullptr;
-  }
-  return rc;
+  *fa = std::move(ga);
+  *fb = std::move(gb);
+  return SC_OK;
 }
 
 // One shard's half of a pass: output buffers (pool memory, or the prover's slot of the context's pinned tail buffer when the
 // plan hands the folded tables to the host), the launch.  *mb as launch_pass.
-int shard_launch(sc_prover* pr, ProverShard& s, const PassPlan& plan, int kf, u64** na_out, u64** nb_out, bool* mb) {
+int shard_launch(sc_prover* pr, ProverShard& s, const PassPlan& plan, int kf, PoolBuf* na_out, PoolBuf* nb_out, bool* mb) {
   sc_ctx* ctx = s.ctx;
   struct Stat {
     sc_ctx* c;
@@ -374,46 +364,36 @@ int shard_launch(sc_prover* pr, ProverShard& s, const PassPlan& plan, int kf, u6
     ~Stat() { c->stat_launch_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t).count(); }
   } stat{ctx, std::chrono::steady_clock::now()};
   SC_TRY(set_device(ctx));
-  u64 *na = nullptr, *nb = nullptr;
+  PoolBuf na, nb;
   if (kf > 0) {
     const size_t out_len = (size_t)1 << (pr->cur_log - kf);
-    if (plan.to_host) {   // (the planner has checked: a slot is held, the outputs fit)
-      na = ctx->d_tail + (size_t)pr->tail_slot * kTailSlotWords;
-      nb = na + kTailEntries;
+    if (plan.to_host) {   // (the planner has checked: a slot is held, the outputs fit.  Not pool memory: the owners ignore it)
+      na.reset(ctx, ctx->d_tail + (size_t)pr->tail_slot * kTailSlotWords);
+      nb.reset(ctx, na + kTailEntries);
     } else {
-      SC_TRY(pool_alloc(ctx, out_len, &na));
-      const int rc = pool_alloc(ctx, out_len, &nb);
-      if (rc != SC_OK) {
-        pool_release(ctx, na);
-        return rc;
-      }
+      SC_TRY(na.alloc(ctx, out_len));
+      SC_TRY(nb.alloc(ctx, out_len));
     }
   }
-  const int rc = plan.kind == PassPlan::kGramPass
-                     ? launch_gram_pass(ctx, s.cur_a, s.cur_b, pr->cur_log, pr->sharded)
-                 : plan.kind == PassPlan::kWfoldPass
-                     ? launch_wfold_pass(ctx, kf, plan.ks, s.cur_a, s.cur_b, na, nb, pr->pending.data(), pr->cur_log, pr->sharded)
-                 : plan.kind == PassPlan::kGridPass
-                     ? launch_grid_pass(ctx, kf, plan.ks, s.cur_a, s.cur_b, na, nb, pr->pending.data(), pr->cur_log, pr->sharded)
-                     : launch_pass(ctx, kf, plan.ks, s.cur_a, s.cur_b, na, nb, pr->pending.data(), pr->cur_log, pr->sharded, mb);
-  if (rc != SC_OK) {
-    pool_release(ctx, na);   // (not pool memory: ignored)
-    pool_release(ctx, nb);
-    return rc;
-  }
-  *na_out = na;
-  *nb_out = nb;
+  SC_TRY(plan.kind == PassPlan::kGramPass
+             ? launch_gram_pass(ctx, s.cur_a, s.cur_b, pr->cur_log, pr->sharded)
+         : plan.kind == PassPlan::kWfoldPass
+             ? launch_wfold_pass(ctx, kf, plan.ks, s.cur_a, s.cur_b, na, nb, pr->pending.data(), pr->cur_log, pr->sharded)
+         : plan.kind == PassPlan::kGridPass
+             ? launch_grid_pass(ctx, kf, plan.ks, s.cur_a, s.cur_b, na, nb, pr->pending.data(), pr->cur_log, pr->sharded)
+             : launch_pass(ctx, kf, plan.ks, s.cur_a, s.cur_b, na, nb, pr->pending.data(), pr->cur_log, pr->sharded, mb));
+  *na_out = std::move(na);
+  *nb_out = std::move(nb);
   return SC_OK;
 }
-// the launch went through and its sums are in: the folded tables become the shard's current ones
-void shard_commit(ProverShard& s, u64* na, u64* nb) {
+// the launch went through and its sums are in: the folded tables become the shard's current ones (and what backed the
+// old ones goes back to the pool)
+void shard_commit(ProverShard& s, PoolBuf&& na, PoolBuf&& nb) {
   if (!na) return;
-  pool_release(s.ctx, s.own_a);
-  pool_release(s.ctx, s.own_b);
-  s.own_a = na;
-  s.own_b = nb;
-  s.cur_a = na;
-  s.cur_b = nb;
+  s.own_a = std::move(na);
+  s.own_b = std::move(nb);
+  s.cur_a = s.own_a;
+  s.cur_b = s.own_b;
 }
 
 // out[i] = sum_c w[c] h[2^kf i + c], i < out_len (kf = 0: a copy)
@@ -530,16 +510,11 @@ int prover_pass(sc_prover* pr, size_t j) {
     return SC_OK;
   }
   if (plan.kind == PassPlan::kRankPass) {
-    u64 *na = nullptr, *nb = nullptr;
-    SC_TRY(pool_alloc(ctx, (size_t)ctx->world, &na));
-    int rc = pool_alloc(ctx, (size_t)ctx->world, &nb);
-    if (rc == SC_OK) rc = rank_pass(ctx, kf, s0.cur_a, s0.cur_b, na, nb, pr->pending.data(), pr->S);
-    if (rc != SC_OK) {
-      pool_release(ctx, na);
-      pool_release(ctx, nb);
-      return rc;
-    }
-    shard_commit(s0, na, nb);
+    PoolBuf na, nb;
+    SC_TRY(na.alloc(ctx, (size_t)ctx->world));
+    SC_TRY(nb.alloc(ctx, (size_t)ctx->world));
+    SC_TRY(rank_pass(ctx, kf, s0.cur_a, s0.cur_b, na, nb, pr->pending.data(), pr->S));
+    shard_commit(s0, std::move(na), std::move(nb));
     pr->cur_log = ctx->log_world;
     pr->pending.clear();
     pr->sharded = false;
@@ -549,9 +524,9 @@ int prover_pass(sc_prover* pr, size_t j) {
     return SC_OK;
   }
   if (plan.gather_first) {
-    u64 *fa = nullptr, *fb = nullptr;
+    PoolBuf fa, fb;
     SC_TRY(gather_pair(ctx, s0.cur_a, s0.cur_b, (size_t)1 << pr->cur_log, &fa, &fb));
-    shard_commit(s0, fa, fb);
+    shard_commit(s0, std::move(fa), std::move(fb));
     pr->cur_log += ctx->log_world;
     pr->sharded = false;
   }
@@ -564,24 +539,18 @@ int prover_pass(sc_prover* pr, size_t j) {
     u64 loc[kMaxSubs][2 * sc::kGridMaxCells];
     SC_TRY(multi_run(ctx, [&](int d, sc_ctx* sub) -> int {
       ProverShard& s = pr->sh[d];
-      u64 *na = nullptr, *nb = nullptr;
+      PoolBuf na, nb;
       bool mb = false;
       SC_TRY(shard_launch(pr, s, plan, kf, &na, &nb, &mb));
-      int rc;
       if (by_grid) {
-        rc = wait_mailbox(sub, sub->mailbox_seq);
-        if (rc == SC_OK) memcpy(loc[d], sub->h_mailbox + sc::kMailboxWide, (size_t)cells * sizeof(u64));   // whole residues
+        SC_TRY(wait_mailbox(sub, sub->mailbox_seq));
+        memcpy(loc[d], sub->h_mailbox + sc::kMailboxWide, (size_t)cells * sizeof(u64));   // whole residues
       } else {
         u64* src = nullptr;
-        rc = fetch_limbs(sub, cells, pr->sharded, mb, &src);
-        if (rc == SC_OK) memcpy(loc[d], src, 2 * (size_t)cells * sizeof(u64));                              // split limbs
+        SC_TRY(fetch_limbs(sub, cells, pr->sharded, mb, &src));
+        memcpy(loc[d], src, 2 * (size_t)cells * sizeof(u64));                              // split limbs
       }
-      if (rc != SC_OK) {
-        pool_release(sub, na);
-        pool_release(sub, nb);
-        return rc;
-      }
-      shard_commit(s, na, nb);
+      shard_commit(s, std::move(na), std::move(nb));
       return SC_OK;
     }));
     HostField hf(ctx->fp);
@@ -602,16 +571,11 @@ int prover_pass(sc_prover* pr, size_t j) {
       }
     }
   } else {
-    u64 *na = nullptr, *nb = nullptr;
+    PoolBuf na, nb;
     bool mb = false;
     SC_TRY(shard_launch(pr, s0, plan, kf, &na, &nb, &mb));
-    const int rc = by_grid ? collect_grid(ctx, ks, pr->sharded, pr->S) : collect_sums(ctx, cells, pr->sharded, mb, pr->S);
-    if (rc != SC_OK) {
-      pool_release(ctx, na);
-      pool_release(ctx, nb);
-      return rc;
-    }
-    shard_commit(s0, na, nb);
+    SC_TRY(by_grid ? collect_grid(ctx, ks, pr->sharded, pr->S) : collect_sums(ctx, cells, pr->sharded, mb, pr->S));
+    shard_commit(s0, std::move(na), std::move(nb));
   }
   if (kf > 0) {
     pr->cur_log -= kf;
@@ -864,7 +828,7 @@ static int prewarm(sc_ctx* ctx, size_t num_vars) {
   const PlanOpts o = plan_opts_of(ctx, true);
   int cur_log = (int)num_vars - g, kf = 0;
   bool sharded = is_sharded(ctx) && ctx->world > 1, on_host = false;
-  std::vector<u64*> held;
+  std::vector<PoolBuf> held;
   int rc = SC_OK;
   for (size_t j = 0; j < num_vars && rc == SC_OK;) {
     const PassPlan p = plan_pass(o, num_vars, j, kf, cur_log, sharded, on_host);
@@ -875,9 +839,9 @@ static int prewarm(sc_ctx* ctx, size_t num_vars) {
     else if (p.kind == PassPlan::kWfoldPass) (void)wfold_resident_blocks(ctx);
     if (kf > 0 && !p.to_host && rc == SC_OK) {
       for (int t = 0; t < 2 && rc == SC_OK; ++t) {
-        u64* blk = nullptr;
-        rc = pool_alloc(ctx, (size_t)1 << (cur_log - kf), &blk);
-        if (rc == SC_OK) held.push_back(blk);
+        PoolBuf blk;
+        rc = blk.alloc(ctx, (size_t)1 << (cur_log - kf));
+        if (rc == SC_OK) held.push_back(std::move(blk));
       }
     }
     cur_log -= kf;
@@ -885,7 +849,7 @@ static int prewarm(sc_ctx* ctx, size_t num_vars) {
     kf = p.ks;
     j += (size_t)p.ks;
   }
-  for (u64* blk : held) pool_release(ctx, blk);
+  for (PoolBuf& blk : held) blk.reset();   // (in the order they were taken)
   SC_TRY(rc);
   SC_HIP(ctx, sync_stream(ctx));
   return SC_OK;
@@ -932,10 +896,6 @@ extern "C" int sc_prover_round(sc_prover* pr, uint64_t r_prev, size_t j, uint64_
 
 extern "C" int sc_prover_destroy(sc_prover* pr) {
   if (!pr) return SC_OK;
-  for (ProverShard& s : pr->sh) {   // (a pinned tail buffer is not pool memory: ignored)
-    pool_release(s.ctx, s.own_a);
-    pool_release(s.ctx, s.own_b);
-  }
   if (pr->tail_slot >= 0) pr->ctx->tail_free.push_back(pr->tail_slot);
   delete pr;
   return SC_OK;

@@ -164,9 +164,9 @@ static int peer_finish_connect(sc_ctx* ctx) {
   // self-test 2: gather (two chunk-sized rounds, so both arenas are exercised)
   {
     const size_t len = 64;
-    u64 *src = nullptr, *dst = nullptr;
-    int rc = pool_alloc(ctx, len, &src);
-    if (rc == SC_OK) rc = pool_alloc(ctx, len * ctx->world, &dst);
+    PoolBuf dst, src;
+    int rc = src.alloc(ctx, len);
+    if (rc == SC_OK) rc = dst.alloc(ctx, len * ctx->world);
     std::vector<u64> host(len * ctx->world);
     for (int round = 0; round < 2 && rc == SC_OK; ++round) {
       for (size_t i = 0; i < len; ++i) host[i] = ((u64)(ctx->rank + 1) << 32) | ((u64)round << 16) | i;
@@ -182,8 +182,8 @@ static int peer_finish_connect(sc_ctx* ctx) {
             break;
           }
     }
-    pool_release(ctx, src);
-    pool_release(ctx, dst);
+    src.reset();
+    dst.reset();
     if (rc != SC_OK) return unusable(rc);
   }
   return SC_OK;

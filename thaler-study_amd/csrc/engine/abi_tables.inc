@@ -9,8 +9,8 @@ extern "C" int sc_table_upload(sc_ctx* ctx, const uint64_t* host, size_t len, sc
   if (is_multi(ctx)) return multi_table_upload(ctx, host, len, out);
   if (!is_pow2(len)) return fail(ctx, SC_ERR_ARG, "sc_table_upload: len %zu is not a power of two", len);
   SC_TRY(set_device(ctx));
-  sc_table* t = nullptr;
-  SC_TRY(new_table(ctx, len, &t));
+  TableBuf t;
+  SC_TRY(t.alloc(ctx, len));
   return table_done(ctx, t, hipMemcpyAsync(t->d, host, len * sizeof(u64), hipMemcpyHostToDevice, ctx->stream), "upload", out);
 }
 
@@ -41,8 +41,8 @@ extern "C" int sc_table_generate(sc_ctx* ctx, uint64_t seed, uint64_t start, siz
   if (is_multi(ctx)) return multi_table_generate(ctx, seed, start, len, out);
   if (!is_pow2(len)) return fail(ctx, SC_ERR_ARG, "sc_table_generate: len %zu is not a power of two", len);
   SC_TRY(set_device(ctx));
-  sc_table* t = nullptr;
-  SC_TRY(new_table(ctx, len, &t));
+  TableBuf t;
+  SC_TRY(t.alloc(ctx, len));
   int grid = grid_for_wide(ctx, len);
   SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::generate_kernel<F>), dim3(grid), dim3(sc::kBlock), 0, ctx->stream,
                                                   f, (u64)seed, (u64)start, len, t->d));
@@ -54,16 +54,9 @@ extern "C" int sc_table_clone(sc_ctx* ctx, const sc_table* t, sc_table** out) {
   if (is_multi(ctx)) return multi_table_clone(ctx, t, out);
   SC_TRY(check_table(ctx, t, "sc_table_clone"));
   SC_TRY(set_device(ctx));
-  sc_table* c = nullptr;
-  SC_TRY(new_table(ctx, t->len, &c));
-  hipError_t e = hipMemcpyAsync(c->d, t->d, t->len * sizeof(u64), hipMemcpyDeviceToDevice, ctx->stream);
-  if (e == hipSuccess) e = sync_stream(ctx);
-  if (e != hipSuccess) {
-    sc_table_free(ctx, c);
-    return fail(ctx, SC_ERR_HIP, "clone: %s", hipGetErrorString(e));
-  }
-  *out = c;
-  return SC_OK;
+  TableBuf c;
+  SC_TRY(c.alloc(ctx, t->len));
+  return table_done(ctx, c, hipMemcpyAsync(c->d, t->d, t->len * sizeof(u64), hipMemcpyDeviceToDevice, ctx->stream), "clone", out);
 }
 
 extern "C" int sc_table_download(sc_ctx* ctx, const sc_table* t, uint64_t* host, size_t len) {
@@ -84,7 +77,7 @@ extern "C" int sc_table_free(sc_ctx* ctx, sc_table* t) {
   if (!t) return SC_OK;
   if (!ctx) return SC_ERR_ARG;
   if (is_multi(ctx) || !t->parts.empty()) return multi_table_free(ctx, t);
-  pool_release(ctx, t->d);
+  PoolBuf(ctx, t->d).reset();   // the block goes back through its owner, like every other (a borrowed one, sc_table_from_device: ignored)
   delete t;
   return SC_OK;
 }
@@ -104,16 +97,14 @@ extern "C" int sc_table_fix_variables(sc_ctx* ctx, const sc_table* in, const uin
   if (ctx->world > 1 && order == SC_ORDER_BE && k > 0)
     return fail(ctx, SC_ERR_UNSUPPORTED, "BE fix_variables pairs entries of different shards");
   SC_TRY(set_device(ctx));
-  sc_table* t = new (std::nothrow) sc_table;
-  if (!t) return fail(ctx, SC_ERR_OOM, "host allocation failed");
-  int rc = fold_chain(ctx, in->d, in->len, r, k, order, &t->d, &t->len);
-  if (rc != SC_OK) {
-    delete t;
-    return rc;
-  }
+  PoolBuf folded;
+  size_t folded_len = 0;
+  SC_TRY(fold_chain(ctx, in->d, in->len, r, k, order, &folded, &folded_len));
+  TableBuf t;
+  SC_TRY(t.wrap(ctx, std::move(folded), folded_len));
   // no synchronisation: every consumer of the new table (and every release of the old one) is work on the
   // context's stream, behind these launches; a fault of theirs surfaces at the next call that waits
-  *out = t;
+  *out = t.release();
   return SC_OK;
 }
 
@@ -125,12 +116,12 @@ static int evaluate_local(sc_ctx* ctx, const u64* d, size_t len, const u64* pt_l
   *from_mailbox = false;
   if (nv < 8) {
     // tiny table: fold chain, then scale into d_sums
-    u64* v1 = nullptr;
+    PoolBuf v1;
     size_t out_len = 0;
     SC_TRY(fold_chain(ctx, d, len, pt_le, (size_t)nv, SC_ORDER_LE, &v1, &out_len));
     SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::scale_split_kernel<F>), dim3(1), dim3(64), 0, ctx->stream, f,
                                                     (const u64*)v1, w_extra, ctx->d_sums));
-    pool_release(ctx, v1);
+    v1.reset();
     SC_HIP(ctx, hipGetLastError());
     return SC_OK;
   }
@@ -326,8 +317,8 @@ extern "C" int sc_table_relabel(sc_ctx* ctx, const sc_table* in, size_t a, size_
   if (a > b) std::swap(a, b);
   if (a + k > b || b + k > (size_t)nv) return fail(ctx, SC_ERR_ARG, "relabel(%zu,%zu,%zu) on %d variables", a, b, k, nv);
   SC_TRY(set_device(ctx));
-  sc_table* t = nullptr;
-  SC_TRY(new_table(ctx, in->len, &t));
+  TableBuf t;
+  SC_TRY(t.alloc(ctx, in->len));
   int grid = grid_for_wide(ctx, in->len);
   hipLaunchKernelGGL(sc::relabel_kernel, dim3(grid), dim3(sc::kBlock), 0, ctx->stream, (const u64*)in->d, t->d, in->len,
                      (unsigned)a, (unsigned)b, (unsigned)k);
@@ -362,40 +353,26 @@ extern "C" int sc_matmul_g_new(sc_ctx* ctx, const sc_table* A, const sc_table* B
     const size_t side = (size_t)1 << n, rows_local = side >> g;
     if (A->len != rows_local * side) return fail(ctx, SC_ERR_ARG, "sc_matmul_g_new: shard must hold 2^(2n)/world entries");
     if (side < 2) return fail(ctx, SC_ERR_UNSUPPORTED, "sc_matmul_g_new: sharded 1x1 matrices");
-    u64 *eq = nullptr, *partial = nullptr, *limbs = nullptr;
-    sc_table *ta = nullptr, *tb = nullptr;
-    int rc = build_eq_table(ctx, point, (int)n, &eq);
-    if (rc == SC_OK) rc = pool_alloc(ctx, side, &partial);
-    if (rc == SC_OK) rc = pool_alloc(ctx, 2 * side, &limbs);
-    if (rc == SC_OK) rc = coldot(ctx, A->d, eq + (size_t)ctx->rank * rows_local, rows_local, side, partial);
-    if (rc == SC_OK) {
-      hipLaunchKernelGGL(sc::split_limbs_kernel, dim3(grid_for(ctx, side)), dim3(sc::kBlock), 0, ctx->stream,
-                         (const u64*)partial, side, limbs);
-      rc = allreduce_device(ctx, limbs, 2 * side);
-    }
-    if (rc == SC_OK) rc = new_table(ctx, rows_local, &ta);
-    if (rc == SC_OK) {
-      const u64* mine = limbs + 2 * (size_t)ctx->rank * rows_local;
-      SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::recombine_limbs_kernel<F>), dim3(grid_for(ctx, rows_local)),
-                                                      dim3(sc::kBlock), 0, ctx->stream, f, mine, rows_local, ta->d));
-      if (hipGetLastError() != hipSuccess) rc = fail(ctx, SC_ERR_HIP, "recombine_limbs_kernel launch failed");
-    }
-    if (rc == SC_OK) {
-      tb = new (std::nothrow) sc_table;
-      if (!tb) rc = fail(ctx, SC_ERR_OOM, "host allocation failed");
-      else rc = fold_chain(ctx, B->d, B->len, point + n, n, SC_ORDER_LE, &tb->d, &tb->len);
-    }
-    if (rc == SC_OK && sync_stream(ctx) != hipSuccess) rc = fail(ctx, SC_ERR_HIP, "g_new: sync failed");
-    pool_release(ctx, eq);
-    pool_release(ctx, partial);
-    pool_release(ctx, limbs);
-    if (rc != SC_OK) {
-      sc_table_free(ctx, ta);
-      if (tb) { pool_release(ctx, tb->d); delete tb; }
-      return rc;
-    }
-    *a_out = ta;
-    *b_out = tb;
+    TableBuf tb, ta;               // (given back in the order of the declarations read upwards: eq, partial, limbs, then the tables)
+    PoolBuf fb, limbs, partial, eq;
+    size_t fb_len = 0;
+    SC_TRY(build_eq_table(ctx, point, (int)n, &eq));
+    SC_TRY(partial.alloc(ctx, side));
+    SC_TRY(limbs.alloc(ctx, 2 * side));
+    SC_TRY(coldot(ctx, A->d, eq + (size_t)ctx->rank * rows_local, rows_local, side, partial));
+    hipLaunchKernelGGL(sc::split_limbs_kernel, dim3(grid_for(ctx, side)), dim3(sc::kBlock), 0, ctx->stream,
+                       (const u64*)partial, side, limbs.get());
+    SC_TRY(allreduce_device(ctx, limbs, 2 * side));
+    SC_TRY(ta.alloc(ctx, rows_local));
+    const u64* mine = limbs + 2 * (size_t)ctx->rank * rows_local;
+    SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::recombine_limbs_kernel<F>), dim3(grid_for(ctx, rows_local)),
+                                                    dim3(sc::kBlock), 0, ctx->stream, f, mine, rows_local, ta->d));
+    if (hipGetLastError() != hipSuccess) return fail(ctx, SC_ERR_HIP, "recombine_limbs_kernel launch failed");
+    SC_TRY(fold_chain(ctx, B->d, B->len, point + n, n, SC_ORDER_LE, &fb, &fb_len));
+    SC_TRY(tb.wrap(ctx, std::move(fb), fb_len));
+    if (sync_stream(ctx) != hipSuccess) return fail(ctx, SC_ERR_HIP, "g_new: sync failed");
+    *a_out = ta.release();
+    *b_out = tb.release();
     return SC_OK;
   }
   if (A->len != ((size_t)1 << (2 * n))) return fail(ctx, SC_ERR_ARG, "sc_matmul_g_new: tables must have 2^(2n) entries");
@@ -405,30 +382,23 @@ extern "C" int sc_matmul_g_new(sc_ctx* ctx, const sc_table* A, const sc_table* B
   SC_TRY(set_device(ctx));
   const size_t side = (size_t)1 << n;
   if (n == 0) {
-    SC_TRY(sc_table_clone(ctx, A, a_out));
-    int rc0 = sc_table_clone(ctx, B, b_out);
-    if (rc0 != SC_OK) { sc_table_free(ctx, *a_out); *a_out = nullptr; }
-    return rc0;
+    sc_table* ca = nullptr;
+    SC_TRY(sc_table_clone(ctx, A, &ca));
+    TableBuf ta(ctx, ca);
+    SC_TRY(sc_table_clone(ctx, B, b_out));
+    *a_out = ta.release();
+    return SC_OK;
   }
-  sc_table* ta = nullptr;
+  TableBuf ta;
   if (side >= 2) {
-    u64* eq = nullptr;
+    PoolBuf eq;
     SC_TRY(build_eq_table(ctx, point, (int)n, &eq));
-    int rc1 = new_table(ctx, side, &ta);
-    if (rc1 == SC_OK) rc1 = coldot(ctx, A->d, eq, side, side, ta->d);
-    pool_release(ctx, eq);
-    if (rc1 != SC_OK) {
-      sc_table_free(ctx, ta);
-      return rc1;
-    }
+    SC_TRY(ta.alloc(ctx, side));
+    SC_TRY(coldot(ctx, A->d, eq, side, side, ta->d));
   }
-  int rc = sc_table_fix_variables(ctx, B, point + n, n, SC_ORDER_LE, b_out);
-  if (rc != SC_OK) {
-    sc_table_free(ctx, ta);
-    return rc;
-  }
+  SC_TRY(sc_table_fix_variables(ctx, B, point + n, n, SC_ORDER_LE, b_out));
   SC_HIP(ctx, sync_stream(ctx));
-  *a_out = ta;
+  *a_out = ta.release();
   return SC_OK;
 }
 
@@ -437,8 +407,8 @@ extern "C" int sc_prod2_to_evaluations(sc_ctx* ctx, const sc_table* a, const sc_
   if (is_multi(ctx)) return multi_prod2_to_evaluations(ctx, a, b, out);
   SC_TRY(check_pair(ctx, a, b, "sc_prod2_to_evaluations"));
   SC_TRY(set_device(ctx));
-  sc_table* t = nullptr;
-  SC_TRY(new_table(ctx, a->len, &t));
+  TableBuf t;
+  SC_TRY(t.alloc(ctx, a->len));
   int grid = grid_for(ctx, a->len);
   SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::mul_kernel<F>), dim3(grid), dim3(sc::kBlock), 0, ctx->stream, f,
                                                   (const u64*)a->d, (const u64*)b->d, t->d, a->len));
@@ -473,13 +443,13 @@ extern "C" int sc_prod2_sum(sc_ctx* ctx, const sc_table* a, const sc_table* b, u
   HostField hf(ctx->fp);
   if (a->len == 1) {
     // zero variables on this rank: the (partial) sum is the single product
-    u64* prod = nullptr;
-    SC_TRY(pool_alloc(ctx, 1, &prod));
+    PoolBuf prod;
+    SC_TRY(prod.alloc(ctx, 1));
     SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::mul_kernel<F>), dim3(1), dim3(sc::kBlock), 0, ctx->stream, f,
-                                                    (const u64*)a->d, (const u64*)b->d, prod, (size_t)1));
+                                                    (const u64*)a->d, (const u64*)b->d, prod.get(), (size_t)1));
     SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::scale_split_kernel<F>), dim3(1), dim3(64), 0, ctx->stream, f,
                                                     (const u64*)prod, hf.one(), ctx->d_sums));
-    pool_release(ctx, prod);
+    prod.reset();
     SC_HIP(ctx, hipGetLastError());
     return collect_sums(ctx, 1, is_sharded(ctx), false, out_c1);
   }
@@ -497,23 +467,16 @@ extern "C" int sc_prod2_fold_and_sums(sc_ctx* ctx, const sc_table* a, const sc_t
   SC_TRY(set_device(ctx));
   int nv = log2_of(a->len);
   if (nv < 2) return fail(ctx, SC_ERR_ARG, "sc_prod2_fold_and_sums: need >= 2 variables (fold one, sum over one)");
-  sc_table *ta = nullptr, *tb = nullptr;
-  SC_TRY(new_table(ctx, a->len / 2, &ta));
-  int rc = new_table(ctx, a->len / 2, &tb);
+  TableBuf tb, ta;
+  SC_TRY(ta.alloc(ctx, a->len / 2));
+  SC_TRY(tb.alloc(ctx, a->len / 2));
   bool mb = false;
-  if (rc == SC_OK) rc = launch_pass(ctx, 1, 1, a->d, b->d, ta->d, tb->d, r, nv, is_sharded(ctx), &mb);
-  if (rc == SC_OK) rc = collect_sums(ctx, 3, is_sharded(ctx), mb, out_e);
-  if (rc == SC_OK) {
-    HostField hf(ctx->fp);
-    out_e[2] = eval2_from_inf(hf, out_e[0], out_e[1], out_e[2]);
-  }
-  if (rc != SC_OK) {
-    sc_table_free(ctx, ta);
-    sc_table_free(ctx, tb);
-    return rc;
-  }
-  *a_out = ta;
-  *b_out = tb;
+  SC_TRY(launch_pass(ctx, 1, 1, a->d, b->d, ta->d, tb->d, r, nv, is_sharded(ctx), &mb));
+  SC_TRY(collect_sums(ctx, 3, is_sharded(ctx), mb, out_e));
+  HostField hf(ctx->fp);
+  out_e[2] = eval2_from_inf(hf, out_e[0], out_e[1], out_e[2]);
+  *a_out = ta.release();
+  *b_out = tb.release();
   return SC_OK;
 }
 

@@ -42,8 +42,8 @@ extern "C" int sc_tri_to_evaluations(sc_ctx* ctx, const sc_table* f1, const sc_t
   SC_TRY(set_device(ctx));
   if (v.xv + v.yv + v.zv > 34) return fail(ctx, SC_ERR_ARG, "triangle to_evaluations: 2^%d entries", v.xv + v.yv + v.zv);
   const size_t total = (size_t)1 << (v.xv + v.yv + v.zv);
-  sc_table* t = nullptr;
-  SC_TRY(new_table(ctx, total, &t));
+  TableBuf t;
+  SC_TRY(t.alloc(ctx, total));
   SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::tri_to_evaluations_kernel<F>), dim3(grid_for_wide(ctx, total)),
                                                   dim3(sc::kBlock), 0, ctx->stream, f, v.f1, v.f2, v.f3, v.xv, v.yv, v.zv, t->d));
   return table_done(ctx, t, hipGetLastError(), "triangle to_evaluations", out);
@@ -83,19 +83,13 @@ extern "C" int sc_tri_fix_variables(sc_ctx* ctx, const sc_table* f1, const sc_ta
   const size_t n_yz = k > xv ? k - xv : 0;
   std::vector<u64> xz(r, r + std::min(xv, k));
   if (k > xv + yv) xz.insert(xz.end(), r + xv + yv, r + k);
-  sc_table *o1 = nullptr, *o2 = nullptr, *o3 = nullptr;
-  int rc = sc_table_fix_variables(ctx, f1, r, n_xy, SC_ORDER_LE, &o1);
-  if (rc == SC_OK) rc = sc_table_fix_variables(ctx, f2, r + std::min(xv, k), n_yz, SC_ORDER_LE, &o2);
-  if (rc == SC_OK) rc = sc_table_fix_variables(ctx, f3, xz.data(), xz.size(), SC_ORDER_LE, &o3);
-  if (rc != SC_OK) {
-    sc_table_free(ctx, o1);
-    sc_table_free(ctx, o2);
-    sc_table_free(ctx, o3);
-    return rc;
-  }
-  *f1_out = o1;
-  *f2_out = o2;
-  *f3_out = o3;
+  TableBuf o3, o2, o1;
+  SC_TRY(sc_table_fix_variables(ctx, f1, r, n_xy, SC_ORDER_LE, o1.out(ctx)));
+  SC_TRY(sc_table_fix_variables(ctx, f2, r + std::min(xv, k), n_yz, SC_ORDER_LE, o2.out(ctx)));
+  SC_TRY(sc_table_fix_variables(ctx, f3, xz.data(), xz.size(), SC_ORDER_LE, o3.out(ctx)));
+  *f1_out = o1.release();
+  *f2_out = o2.release();
+  *f3_out = o3.release();
   return SC_OK;
 }
 
@@ -127,8 +121,8 @@ struct sc_tri_prover {
   std::vector<u64> r;        // every challenge received
   sc_prover* sub = nullptr;  // current phase's engine
   sc_table ta, tb;           // views handed to sc_prover_create
-  u64 *P = nullptr, *f3r = nullptr, *f1y = nullptr, *Q = nullptr, *f2r = nullptr;  // pool buffers
-  u64* adj_full = nullptr;   // sharded contexts: the gathered adjacency table
+  PoolBuf P, f3r, f1y, Q, f2r;
+  PoolBuf adj_full;          // sharded contexts: the gathered adjacency table
   u64 scale = 0;             // f1(r_x, r_y) in the z phase
   u64 c1 = 0;
 };
@@ -137,19 +131,18 @@ namespace {
 
 // Fold the challenges the sub-prover has not applied yet plus `r_last`; hand back the table(s) asked for (a null
 // a_out / b_out: that table is not needed, its folds are not launched).
-int prover_finish(sc_prover* pr, u64 r_last, u64** a_out, u64** b_out, size_t* len_out) {
+int prover_finish(sc_prover* pr, u64 r_last, PoolBuf* a_out, PoolBuf* b_out, size_t* len_out) {
   sc_ctx* ctx = pr->ctx;
   std::vector<u64> rs(pr->pending);   // the sub-prover's own state is left untouched
   rs.push_back(r_last);
-  u64 *na = nullptr, *nb = nullptr;
+  PoolBuf na, nb;
   size_t la = 0, lb = 0;
   if (pr->host_mode) {
     // the host has taken the sub-prover's tables over (engine/abi_prover.inc: host_tail; only option mixes with one-round passes
     // get here before a phase ends): fold copies of them on the host and hand device copies back
     HostField hf(ctx->fp);
     for (int t = 0; t < 2; ++t) {
-      u64** dst = t ? b_out : a_out;
-      if (!dst) continue;
+      if (!(t ? b_out : a_out)) continue;
       std::vector<u64> v(t ? pr->hb : pr->ha);
       for (const u64 r : rs) {
         const size_t half = v.size() / 2;
@@ -157,35 +150,20 @@ int prover_finish(sc_prover* pr, u64 r_last, u64** a_out, u64** b_out, size_t* l
         for (size_t i = 0; i < half; ++i) v[i] = hf.add(v[2 * i], hf.mul(r, hf.sub(v[2 * i + 1], v[2 * i])));
         v.resize(half);
       }
-      u64* d = nullptr;
-      int rc = pool_alloc(ctx, v.size(), &d);
-      if (rc == SC_OK && hipMemcpyAsync(d, v.data(), v.size() * sizeof(u64), hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-        rc = fail(ctx, SC_ERR_HIP, "prover_finish: upload failed");
-      if (rc == SC_OK && sync_stream(ctx) != hipSuccess) rc = fail(ctx, SC_ERR_HIP, "prover_finish: upload failed");
-      if (rc != SC_OK) {
-        pool_release(ctx, d);
-        pool_release(ctx, na);
-        return rc;
-      }
-      (t ? nb : na) = d;
+      PoolBuf d;
+      SC_TRY(d.alloc(ctx, v.size()));
+      if (hipMemcpyAsync(d, v.data(), v.size() * sizeof(u64), hipMemcpyHostToDevice, ctx->stream) != hipSuccess || sync_stream(ctx) != hipSuccess)
+        return fail(ctx, SC_ERR_HIP, "prover_finish: upload failed");
+      (t ? nb : na) = std::move(d);
       (t ? lb : la) = v.size();
     }
-    if (a_out) *a_out = na;
-    if (b_out) *b_out = nb;
-    *len_out = a_out ? la : lb;
-    return SC_OK;
+  } else {
+    const size_t len = (size_t)1 << pr->cur_log;
+    if (a_out) SC_TRY(fold_chain(ctx, pr->sh[0].cur_a, len, rs.data(), rs.size(), SC_ORDER_LE, &na, &la));
+    if (b_out) SC_TRY(fold_chain(ctx, pr->sh[0].cur_b, len, rs.data(), rs.size(), SC_ORDER_LE, &nb, &lb));
   }
-  const size_t len = (size_t)1 << pr->cur_log;
-  if (a_out) SC_TRY(fold_chain(ctx, pr->sh[0].cur_a, len, rs.data(), rs.size(), SC_ORDER_LE, &na, &la));
-  if (b_out) {
-    const int rc = fold_chain(ctx, pr->sh[0].cur_b, len, rs.data(), rs.size(), SC_ORDER_LE, &nb, &lb);
-    if (rc != SC_OK) {
-      pool_release(ctx, na);
-      return rc;
-    }
-  }
-  if (a_out) *a_out = na;
-  if (b_out) *b_out = nb;
+  if (a_out) *a_out = std::move(na);
+  if (b_out) *b_out = std::move(nb);
   *len_out = a_out ? la : lb;
   return SC_OK;
 }
@@ -221,44 +199,36 @@ int tri_start_phase(sc_tri_prover* tp, const u64* a, const u64* b, size_t len) {
 // table on this device: the n^3 work of the proof, the part that splits over ranks / devices.
 int tri_square_rows(sc_ctx* ctx, const u64* adj, int k, u64* P, size_t z_begin, size_t z_rows) {
   const size_t n = (size_t)1 << k, full_len = n * n;
-  int rc = SC_OK;
-  if (rc == SC_OK) {
-    rc = timer_begin(ctx, SC_KIND_MATSQ, k, 0, 2 * k, (u64)8 * full_len, (u64)8 * z_rows * n);
-    if (rc == SC_OK) {
-      if (k >= 6 && z_rows >= 64) {
-        // adjacency tables are 0/1 (G::new_adj_matrix): their square is a count, computed exactly by the int8 matrix
-        // cores.  Bytes + flag, the MFMA kernel, and behind it the generic kernel, which runs only if the flag says
-        // the table held something else - no host round trip decides.
-        u64* bytes = nullptr;   // T8 | T8t | flag
-        rc = pool_alloc(ctx, 2 * (full_len / 8) + 8, &bytes);
-        if (rc == SC_OK) {
-          unsigned char* t8 = reinterpret_cast<unsigned char*>(bytes);
-          unsigned char* t8t = t8 + full_len;
-          unsigned* flag = reinterpret_cast<unsigned*>(bytes + 2 * (full_len / 8));
-          const size_t tiles = (z_rows / 64) * (n / 64);   // 64 x 64 output tiles of this rank's rows
-          const int grid = (int)std::min<size_t>(tiles, (size_t)4 * ctx->num_cus);
-          const size_t tiles32 = (z_rows / 32) * (n / 32);
-          if (hipMemsetAsync(flag, 0, sizeof(unsigned), ctx->stream) != hipSuccess) rc = fail(ctx, SC_ERR_HIP, "matsq: memset failed");
-          SC_DISPATCH_FIELD(ctx, F, f, {
-            hipLaunchKernelGGL((sc::matsq_bytes_kernel<F>), dim3((unsigned)std::min<size_t>((n / 64) * (n / 64), (size_t)8 * ctx->num_cus)),
-                               dim3(sc::kBlock), 0, ctx->stream, f, adj, k, t8, t8t, flag);
-            hipLaunchKernelGGL((sc::matsq_mfma_kernel<F>), dim3((unsigned)std::min<size_t>((tiles32 + 3) / 4, (size_t)8 * ctx->num_cus)),
-                               dim3(sc::kBlock), 0, ctx->stream, f, (const unsigned char*)t8, (const unsigned char*)t8t, k, P, z_begin,
-                               z_rows, (const unsigned*)flag);
-            hipLaunchKernelGGL((sc::matsq_tiled_kernel<F>), dim3(grid), dim3(sc::kBlock), 0, ctx->stream, f, adj, k, P, z_begin,
-                               z_rows, (const unsigned*)flag);
-          });
-          pool_release(ctx, bytes);   // stream-ordered reuse
-        }
-      } else {
-        SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::matsq_kernel<F>), dim3(grid_for_wide(ctx, z_rows * n)), dim3(sc::kBlock),
-                                                        0, ctx->stream, f, adj, k, P, z_begin, z_rows));
-      }
-      if (hipGetLastError() != hipSuccess) rc = fail(ctx, SC_ERR_HIP, "matsq kernel launch failed");
-    }
-    if (rc == SC_OK) rc = timer_end(ctx);
+  SC_TRY(timer_begin(ctx, SC_KIND_MATSQ, k, 0, 2 * k, (u64)8 * full_len, (u64)8 * z_rows * n));
+  if (k >= 6 && z_rows >= 64) {
+    // adjacency tables are 0/1 (G::new_adj_matrix): their square is a count, computed exactly by the int8 matrix
+    // cores.  Bytes + flag, the MFMA kernel, and behind it the generic kernel, which runs only if the flag says
+    // the table held something else - no host round trip decides.
+    PoolBuf bytes;   // T8 | T8t | flag
+    SC_TRY(bytes.alloc(ctx, 2 * (full_len / 8) + 8));
+    unsigned char* t8 = reinterpret_cast<unsigned char*>(bytes.get());
+    unsigned char* t8t = t8 + full_len;
+    unsigned* flag = reinterpret_cast<unsigned*>(bytes.get() + 2 * (full_len / 8));
+    const size_t tiles = (z_rows / 64) * (n / 64);   // 64 x 64 output tiles of this rank's rows
+    const int grid = (int)std::min<size_t>(tiles, (size_t)4 * ctx->num_cus);
+    const size_t tiles32 = (z_rows / 32) * (n / 32);
+    if (hipMemsetAsync(flag, 0, sizeof(unsigned), ctx->stream) != hipSuccess) return fail(ctx, SC_ERR_HIP, "matsq: memset failed");
+    SC_DISPATCH_FIELD(ctx, F, f, {
+      hipLaunchKernelGGL((sc::matsq_bytes_kernel<F>), dim3((unsigned)std::min<size_t>((n / 64) * (n / 64), (size_t)8 * ctx->num_cus)),
+                         dim3(sc::kBlock), 0, ctx->stream, f, adj, k, t8, t8t, flag);
+      hipLaunchKernelGGL((sc::matsq_mfma_kernel<F>), dim3((unsigned)std::min<size_t>((tiles32 + 3) / 4, (size_t)8 * ctx->num_cus)),
+                         dim3(sc::kBlock), 0, ctx->stream, f, (const unsigned char*)t8, (const unsigned char*)t8t, k, P, z_begin,
+                         z_rows, (const unsigned*)flag);
+      hipLaunchKernelGGL((sc::matsq_tiled_kernel<F>), dim3(grid), dim3(sc::kBlock), 0, ctx->stream, f, adj, k, P, z_begin,
+                         z_rows, (const unsigned*)flag);
+    });
+    bytes.reset();   // stream-ordered reuse
+  } else {
+    SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::matsq_kernel<F>), dim3(grid_for_wide(ctx, z_rows * n)), dim3(sc::kBlock),
+                                                    0, ctx->stream, f, adj, k, P, z_begin, z_rows));
   }
-  return rc;
+  if (hipGetLastError() != hipSuccess) return fail(ctx, SC_ERR_HIP, "matsq kernel launch failed");
+  return timer_end(ctx);
 }
 
 }  // namespace
@@ -291,16 +261,13 @@ extern "C" int sc_tri_prover_create(sc_ctx* ctx, const sc_table* adj, size_t var
   }
   const size_t n = (size_t)1 << var_len;
   const size_t z_rows = sharded ? n / ctx->world : n, z_begin = sharded ? (size_t)ctx->rank * z_rows : 0;
-  if (rc == SC_OK) rc = pool_alloc(ctx, full_len, &tp->P);
+  if (rc == SC_OK) rc = tp->P.alloc(ctx, full_len);
   if (rc == SC_OK) rc = tri_square_rows(ctx, tp->adj, tp->k, tp->P, z_begin, z_rows);
   if (rc == SC_OK && sharded) {
     // every rank computed its rows of P: gather the whole square
-    u64* full = nullptr;
+    PoolBuf full;
     rc = gather_table(ctx, tp->P + z_begin * n, z_rows * n, &full);
-    if (rc == SC_OK) {
-      pool_release(ctx, tp->P);
-      tp->P = full;
-    }
+    if (rc == SC_OK) tp->P = std::move(full);   // (the rows go back)
   }
   // x phase: sum_{x,z} P(x,z) f3(x,z), both indexed (z << k) | x
   if (rc == SC_OK) rc = tri_start_phase(tp, tp->P, tp->adj, full_len);
@@ -347,29 +314,25 @@ static int tri_prover_round_impl(sc_tri_prover* tp, uint64_t r_prev, size_t j, u
   const size_t n = (size_t)1 << k;
   if (j == k) {
     // x fully fixed at r_x = r[0..k): P(r_x, .) is not needed any more, f3(r_x, .) is
-    // every buffer lands in a member of tp at once, so an error return leaks nothing (destroy frees them)
-    u64* pb = nullptr;
+    PoolBuf pb;
     size_t len = 0;
     SC_TRY_POP(prover_finish(tp->sub, r_prev, nullptr, &pb, &len));   // P(r_x, .) is not needed
-    pool_release(ctx, tp->f3r);
-    tp->f3r = pb;  // f3(r_x, z), 2^k entries
+    tp->f3r = std::move(pb);  // f3(r_x, z), 2^k entries (an earlier one goes back)
     size_t l1 = 0;
-    pool_release(ctx, tp->f1y);
-    tp->f1y = nullptr;
+    tp->f1y.reset();
     SC_TRY_POP(fold_chain(ctx, tp->adj, n * n, tp->r.data(), k, SC_ORDER_LE, &tp->f1y, &l1));  // f1(r_x, y)
-    if (!tp->Q) SC_TRY_POP(pool_alloc(ctx, n, &tp->Q));
+    if (!tp->Q) SC_TRY_POP(tp->Q.alloc(ctx, n));
     SC_TRY_POP(coldot(ctx, tp->adj, tp->f3r, n, n, tp->Q));  // Q[y] = sum_z f2[(z<<k)|y] f3r[z]
     SC_TRY_POP(tri_start_phase(tp, tp->f1y, tp->Q, n));
   } else if (j == 2 * k) {
-    u64* pa = nullptr;
+    PoolBuf pa;
     size_t len = 0;
     SC_TRY_POP(prover_finish(tp->sub, r_prev, &pa, nullptr, &len));   // Q(r_y) is not needed
     const int fr = fetch_word(ctx, pa, &tp->scale);                    // f1(r_x, r_y)
-    pool_release(ctx, pa);
+    pa.reset();
     SC_TRY_POP(fr);
     size_t l2 = 0;
-    pool_release(ctx, tp->f2r);
-    tp->f2r = nullptr;
+    tp->f2r.reset();
     SC_TRY_POP(fold_chain(ctx, tp->adj, n * n, tp->r.data() + k, k, SC_ORDER_LE, &tp->f2r, &l2));  // f2(r_y, z)
     SC_TRY_POP(tri_start_phase(tp, tp->f2r, tp->f3r, n));
   }
@@ -400,12 +363,6 @@ extern "C" int sc_tri_prove(sc_ctx* ctx, const sc_table* adj, size_t var_len, sc
 extern "C" int sc_tri_prover_destroy(sc_tri_prover* tp) {
   if (!tp) return SC_OK;
   if (tp->sub) sc_prover_destroy(tp->sub);
-  pool_release(tp->ctx, tp->P);
-  pool_release(tp->ctx, tp->f3r);
-  pool_release(tp->ctx, tp->f1y);
-  pool_release(tp->ctx, tp->Q);
-  pool_release(tp->ctx, tp->f2r);
-  pool_release(tp->ctx, tp->adj_full);
   delete tp;
   return SC_OK;
 }
@@ -427,34 +384,31 @@ static int multi_tri_prover_create(sc_ctx* m, const sc_table* adj, size_t var_le
   tp->handle = m;
   tp->k = (int)var_len;
   const size_t z_rows = n / N;
-  u64* whole[kMaxSubs] = {};
+  PoolBuf whole[kMaxSubs];   // the adjacency table, whole on every device
   int rc = set_device(first);
-  if (rc == SC_OK) rc = pool_alloc(first, full_len, &tp->P);
+  if (rc == SC_OK) rc = tp->P.alloc(first, full_len);
   // (every device's stream writes its rows into P: the first device's stream must be done with the recycled block - ADVICE r04)
   if (rc == SC_OK && hipStreamSynchronize(first->stream) != hipSuccess) rc = fail(first, SC_ERR_HIP, "triangle: draining the first device's stream failed");
   if (rc == SC_OK)
     rc = multi_run(m, [&](int d, sc_ctx* sub) -> int {
       SC_TRY(multi_gather_to(m, adj, sub, &whole[d]));
-      u64* rows = nullptr;   // this device's rows of P, addressed like the whole matrix
-      SC_TRY(pool_alloc(sub, z_rows * n, &rows));
-      int r2 = tri_square_rows(sub, whole[d], tp->k, rows - (size_t)d * z_rows * n, (size_t)d * z_rows, z_rows);
-      if (r2 == SC_OK) {
-        hipError_t e = hipMemcpyPeerAsync(tp->P + (size_t)d * z_rows * n, first->device, rows, sub->device, z_rows * n * sizeof(u64), sub->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(sub->stream);
-        if (e != hipSuccess) r2 = fail(sub, SC_ERR_HIP, "triangle: sending a device's rows of the square to the first device: %s", hipGetErrorString(e));
-      }
-      pool_release(sub, rows);
-      return r2;
+      PoolBuf rows;   // this device's rows of P, addressed like the whole matrix (given back on return: the copy is drained)
+      SC_TRY(rows.alloc(sub, z_rows * n));
+      SC_TRY(tri_square_rows(sub, whole[d], tp->k, rows - (size_t)d * z_rows * n, (size_t)d * z_rows, z_rows));
+      hipError_t e = hipMemcpyPeerAsync(tp->P + (size_t)d * z_rows * n, first->device, rows, sub->device, z_rows * n * sizeof(u64), sub->stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(sub->stream);
+      if (e != hipSuccess) return fail(sub, SC_ERR_HIP, "triangle: sending a device's rows of the square to the first device: %s", hipGetErrorString(e));
+      return SC_OK;
     });
-  for (size_t d = 1; d < N; ++d) pool_release(m->subs[d], whole[d]);
+  for (size_t d = 1; d < N; ++d) whole[d].reset();
   if (rc == SC_OK) {
-    tp->adj_full = whole[0];   // (released with the prover)
+    tp->adj_full = std::move(whole[0]);   // (released with the prover)
     tp->adj = tp->adj_full;
     rc = set_device(first);
     if (rc == SC_OK) rc = tri_start_phase(tp, tp->P, tp->adj, full_len);   // x phase: sum_{x,z} P(x,z) f3(x,z)
     if (rc != SC_OK) (void)fail(m, rc, "%s", first->err.c_str());
   } else {
-    pool_release(first, whole[0]);
+    whole[0].reset();
   }
   if (rc != SC_OK) {
     sc_tri_prover_destroy(tp);

@@ -200,37 +200,25 @@ int peer_gather(sc_ctx* ctx, const u64* a, const u64* b, size_t len, u64* dst_a,
 }
 
 // All-gather `len` words per rank of a device buffer into a new pool buffer of len*world.
-int gather_table(sc_ctx* ctx, const u64* local, size_t len, u64** out_full) {
-  u64* full = nullptr;
-  SC_TRY(pool_alloc(ctx, len * ctx->world, &full));
+int gather_table(sc_ctx* ctx, const u64* local, size_t len, PoolBuf* out_full) {
+  PoolBuf full;
+  SC_TRY(full.alloc(ctx, len * ctx->world));
   if (ctx->transport == Transport::kPeer) {
-    const int rc = peer_gather(ctx, local, nullptr, len, full, nullptr);
-    if (rc != SC_OK) {
-      pool_release(ctx, full);
-      return rc;
-    }
+    SC_TRY(peer_gather(ctx, local, nullptr, len, full, nullptr));
   } else if (ctx->transport == Transport::kRccl) {
     ncclResult_t r = g_rccl.AllGather(local, full, len, ncclUint64, ctx->comm, ctx->stream);
-    if (r != ncclSuccess) {
-      pool_release(ctx, full);
-      return fail(ctx, SC_ERR_RCCL, "ncclAllGather: %s", g_rccl.GetErrorString ? g_rccl.GetErrorString(r) : "?");
-    }
+    if (r != ncclSuccess) return fail(ctx, SC_ERR_RCCL, "ncclAllGather: %s", g_rccl.GetErrorString ? g_rccl.GetErrorString(r) : "?");
   } else {
-    if (!ctx->host_allgather) {
-      pool_release(ctx, full);
-      return fail(ctx, SC_ERR_STATE, "gather_table: no host collectives installed on this context");
-    }
+    if (!ctx->host_allgather) return fail(ctx, SC_ERR_STATE, "gather_table: no host collectives installed on this context");
     std::vector<u64> send(len), recv(len * ctx->world);
     SC_HIP(ctx, hipMemcpyAsync(send.data(), local, len * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
     SC_HIP(ctx, sync_stream(ctx));
-    if (ctx->host_allgather(ctx->host_user, send.data(), recv.data(), len) != 0) {
-      pool_release(ctx, full);
+    if (ctx->host_allgather(ctx->host_user, send.data(), recv.data(), len) != 0)
       return fail(ctx, SC_ERR_RCCL, "host all-gather callback failed");
-    }
     SC_HIP(ctx, hipMemcpyAsync(full, recv.data(), recv.size() * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
     SC_HIP(ctx, sync_stream(ctx));
   }
-  *out_full = full;
+  *out_full = std::move(full);
   return SC_OK;
 }
 
@@ -238,16 +226,13 @@ int gather_table(sc_ctx* ctx, const u64* local, size_t len, u64** out_full) {
 int allreduce_device(sc_ctx* ctx, u64* buf, size_t count) {
   if (ctx->transport == Transport::kPeer) {
     // gather every rank's vector, then sum the rows locally (plain u64 adds of limbs)
-    u64* all = nullptr;
-    SC_TRY(pool_alloc(ctx, count * ctx->world, &all));
-    int rc = peer_gather(ctx, buf, nullptr, count, all, nullptr);
-    if (rc == SC_OK) {
-      hipLaunchKernelGGL(sc::sum_limb_rows_kernel, dim3(grid_for(ctx, count)), dim3(sc::kBlock), 0, ctx->stream, (const u64*)all, ctx->world,
-                         count, buf);
-      if (hipGetLastError() != hipSuccess) rc = fail(ctx, SC_ERR_HIP, "sum_limb_rows_kernel launch failed");
-    }
-    pool_release(ctx, all);   // stream-ordered reuse
-    return rc;
+    PoolBuf all;   // (given back on return: stream-ordered reuse)
+    SC_TRY(all.alloc(ctx, count * ctx->world));
+    SC_TRY(peer_gather(ctx, buf, nullptr, count, all, nullptr));
+    hipLaunchKernelGGL(sc::sum_limb_rows_kernel, dim3(grid_for(ctx, count)), dim3(sc::kBlock), 0, ctx->stream, (const u64*)all, ctx->world,
+                       count, buf);
+    if (hipGetLastError() != hipSuccess) return fail(ctx, SC_ERR_HIP, "sum_limb_rows_kernel launch failed");
+    return SC_OK;
   }
   if (ctx->transport == Transport::kRccl) {
     ncclResult_t r = g_rccl.AllReduce(buf, buf, count, ncclUint64, ncclSum, ctx->comm, ctx->stream);

@@ -191,19 +191,15 @@ sc_table* new_multi_table(size_t n_parts, size_t len) {
 }
 void drop_multi_table(sc_ctx* m, sc_table* t) {
   if (!t) return;
-  for (size_t d = 0; d < t->parts.size() && d < m->subs.size(); ++d) sc_table_free(m->subs[d], t->parts[d]);
+  for (size_t d = 0; d < t->parts.size() && d < m->subs.size(); ++d) TableBuf(m->subs[d], t->parts[d]).reset();   // (each part is an ordinary table of its device: freed through its owner)
   delete t;
 }
 // build a table of the handle part by part: make(d, sub, &part) on every shard in parallel
 int make_multi_table(sc_ctx* m, size_t len, const std::function<int(int, sc_ctx*, sc_table**)>& make, sc_table** out) {
-  sc_table* t = new_multi_table(m->subs.size(), len);
-  if (!t) return fail(m, SC_ERR_OOM, "host allocation failed");
-  const int rc = multi_run(m, [&](int d, sc_ctx* sub) { return make(d, sub, &t->parts[d]); }, /*recoverable=*/true);
-  if (rc != SC_OK) {
-    drop_multi_table(m, t);
-    return rc;
-  }
-  *out = t;
+  TableBuf t(m, new_multi_table(m->subs.size(), len), /*multi=*/true);
+  if (!t.get()) return fail(m, SC_ERR_OOM, "host allocation failed");
+  SC_TRY(multi_run(m, [&](int d, sc_ctx* sub) { return make(d, sub, &t->parts[d]); }, /*recoverable=*/true));
+  *out = t.release();
   return SC_OK;
 }
 int check_multi_len(sc_ctx* m, size_t len, const char* what) {

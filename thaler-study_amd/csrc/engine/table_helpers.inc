@@ -8,13 +8,13 @@ namespace {
 
 // The end of a call that launched a kernel (or queued a copy: e) into the fresh table t: the stream drained, t handed out - or
 // freed and `what` reported
-int table_done(sc_ctx* ctx, sc_table* t, hipError_t e, const char* what, sc_table** out) {
+int table_done(sc_ctx* ctx, TableBuf& t, hipError_t e, const char* what, sc_table** out) {
   if (e == hipSuccess) e = sync_stream(ctx);
   if (e != hipSuccess) {
-    sc_table_free(ctx, t);
+    t.reset();
     return fail(ctx, SC_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
   }
-  *out = t;
+  *out = t.release();
   return SC_OK;
 }
 
@@ -26,20 +26,17 @@ sc::RVec make_rvec(const u64* r, size_t n) {
 }
 
 // eq table over `nbits` index bits: out[i] = prod_j (bit_j(i) ? r[j] : 1 - r[j]).
-int build_eq_table(sc_ctx* ctx, const u64* r, int nbits, u64** out) {
+int build_eq_table(sc_ctx* ctx, const u64* r, int nbits, PoolBuf* out) {
   if (nbits > 40) return fail(ctx, SC_ERR_ARG, "eq table of 2^%d entries", nbits);
-  u64* t = nullptr;
-  SC_TRY(pool_alloc(ctx, (size_t)1 << nbits, &t));
+  PoolBuf t;
+  SC_TRY(t.alloc(ctx, (size_t)1 << nbits));
   sc::RVec rv = make_rvec(r, (size_t)nbits);
   int grid = grid_for_wide(ctx, (size_t)1 << nbits);
   SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::eq_table_kernel<F>), dim3(grid), dim3(sc::kBlock), 0, ctx->stream, f,
-                                                  rv, 0, nbits, t));
+                                                  rv, 0, nbits, t.get()));
   hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    pool_release(ctx, t);
-    return fail(ctx, SC_ERR_HIP, "eq_table_kernel: %s", hipGetErrorString(e));
-  }
-  *out = t;
+  if (e != hipSuccess) return fail(ctx, SC_ERR_HIP, "eq_table_kernel: %s", hipGetErrorString(e));
+  *out = std::move(t);
   return SC_OK;
 }
 
@@ -74,8 +71,9 @@ int coldot(sc_ctx* ctx, const u64* in, const u64* w, size_t rows, size_t M, u64*
   const size_t gx = rw.gx, chunks = rw.chunks, rows_per_chunk = rw.rows_per_chunk;
   if (rows_per_chunk > sc::GoldilocksMont::kAccMaxTerms)   // one lazy accumulator sums rows_per_chunk products
     return fail(ctx, SC_ERR_UNSUPPORTED, "coldot: %zu rows per chunk exceed the lazy accumulator's capacity", rows_per_chunk);
-  u64* partial = out;
-  if (chunks > 1) SC_TRY(pool_alloc(ctx, chunks * M, &partial));
+  PoolBuf rows_buf;   // the chunks' partial rows
+  if (chunks > 1) SC_TRY(rows_buf.alloc(ctx, chunks * M));
+  u64* const partial = chunks > 1 ? rows_buf.get() : out;
   const int nt = (rows * M) >= ((size_t)1 << ctx->nt_load_log) ? 1 : 0;
   SC_TRY(timer_begin(ctx, SC_KIND_COLDOT, log2_of(rows), 0, log2_of(rows * M), (u64)8 * rows * M + 8 * rows, (u64)8 * M));
 #define SC_COLDOT(NT, PW)                                                                                                  \
@@ -95,7 +93,7 @@ int coldot(sc_ctx* ctx, const u64* in, const u64* w, size_t rows, size_t M, u64*
     int grid = grid_for_wide(ctx, M);
     SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::sum_rows_kernel<F>), dim3(grid, 1), dim3(sc::kBlock), 0, ctx->stream, f,
                                                     (const u64*)partial, (const u64*)partial, chunks, M, out, out));
-    pool_release(ctx, partial);
+    rows_buf.reset();
   }
   SC_HIP(ctx, hipGetLastError());
   SC_TRY(timer_end(ctx));
@@ -106,13 +104,13 @@ int coldot(sc_ctx* ctx, const u64* in, const u64* w, size_t rows, size_t M, u64*
 // written.  LE: eight or more variables in one streaming segment-dot pass, fewer at up to three
 // per pass (read N, write N/8).  BE: one "column dot" pass against the eq table of the k
 // leading variables.
-int fold_chain(sc_ctx* ctx, const u64* in, size_t len, const u64* r, size_t k, int order, u64** out,
+int fold_chain(sc_ctx* ctx, const u64* in, size_t len, const u64* r, size_t k, int order, PoolBuf* out,
                size_t* out_len) {
   if (k == 0) {
-    u64* cp = nullptr;
-    SC_TRY(pool_alloc(ctx, len, &cp));
+    PoolBuf cp;
+    SC_TRY(cp.alloc(ctx, len));
     SC_HIP(ctx, hipMemcpyAsync(cp, in, len * sizeof(u64), hipMemcpyDeviceToDevice, ctx->stream));
-    *out = cp;
+    *out = std::move(cp);
     *out_len = len;
     return SC_OK;
   }
@@ -120,42 +118,28 @@ int fold_chain(sc_ctx* ctx, const u64* in, size_t len, const u64* r, size_t k, i
     // eq index i has variable 0 (r[0]) as its MSB: reverse r for the LE-bit table builder
     std::vector<u64> rr(r, r + k);
     std::reverse(rr.begin(), rr.end());
-    u64* eq = nullptr;
+    PoolBuf res, eq;   // (eq is given back first)
     SC_TRY(build_eq_table(ctx, rr.data(), (int)k, &eq));
-    u64* res = nullptr;
-    int rc = pool_alloc(ctx, len >> k, &res);
-    if (rc == SC_OK) rc = coldot(ctx, in, eq, (size_t)1 << k, len >> k, res);
-    pool_release(ctx, eq);
-    if (rc != SC_OK) {
-      pool_release(ctx, res);
-      return rc;
-    }
-    *out = res;
+    SC_TRY(res.alloc(ctx, len >> k));
+    SC_TRY(coldot(ctx, in, eq, (size_t)1 << k, len >> k, res));
+    *out = std::move(res);   // (eq goes back behind it: the launches that read it are queued)
     *out_len = len >> k;
     return SC_OK;
   }
   const u64* cur = in;
-  u64* owned = nullptr;  // intermediate we own (never `in`)
+  PoolBuf owned;  // intermediate we own (never `in`)
   size_t cur_len = len;
   size_t done = 0;
-  // a failing step gives back the intermediate of the previous one (and its own output)
-#define SC_CHAIN(expr)                \
-  do {                                \
-    int rc_ = (expr);                 \
-    if (rc_ != SC_OK) {               \
-      pool_release(ctx, nxt);         \
-      pool_release(ctx, owned);       \
-      return rc_;                     \
-    }                                 \
-  } while (0)
   while (done < k) {
     int step;
-    u64* nxt = nullptr;
+    PoolBuf nxt_buf;
+    u64* nxt = nullptr;   // = nxt_buf, once allocated (what the launches below capture)
     if (order == SC_ORDER_LE && k - done >= 8) {
       // many variables left: one streaming pass over contiguous segments (kernels.hpp, fix_low_kernel)
       step = (int)std::min<size_t>(17, k - done);
       const size_t nlen = cur_len >> step;
-      SC_CHAIN(pool_alloc(ctx, nlen, &nxt));
+      SC_TRY(nxt_buf.alloc(ctx, nlen));
+      nxt = nxt_buf;
       const sc::RVec rv = make_rvec(r + done, (size_t)step);
       // one segment per wave: four-wave blocks while there is at most one segment per wave of one block per CU, beyond that
       // one block per CU with all sixteen waves, which draw their segments from a counter in LDS (kernels.hpp, evaluate_kernel)
@@ -165,31 +149,33 @@ int fold_chain(sc_ctx* ctx, const u64* in, size_t len, const u64* r, size_t k, i
         grid = std::min(ctx->num_cus, ctx->max_blocks);
       }
       const int nt = cur_len >= ((size_t)1 << ctx->nt_load_log) ? 1 : 0;
-      SC_CHAIN(timer_begin(ctx, SC_KIND_FIX_LOW, step, 0, log2_of(cur_len), (u64)8 * cur_len, (u64)8 * nlen));
+      SC_TRY(timer_begin(ctx, SC_KIND_FIX_LOW, step, 0, log2_of(cur_len), (u64)8 * cur_len, (u64)8 * nlen));
       SC_DISPATCH_FIELD(ctx, F, f, with_bool(nt, [&](auto NT) {
         hipLaunchKernelGGL((sc::fix_low_kernel<F, NT>), dim3(grid), dim3(threads), 0, ctx->stream, f, cur, nxt, step, rv, nlen);
       }));
-      SC_CHAIN(timer_end(ctx));
+      SC_TRY(timer_end(ctx));
       cur_len = nlen;
     } else if (order == SC_ORDER_LE && k - done >= 4 && cur_len <= ((size_t)1 << 20) && (cur_len >> std::min<size_t>(5, k - done)) >= 1) {
       // a small table: four or five variables in one launch (kernels.hpp, fold_wide_kernel)
       step = (int)std::min<size_t>(5, k - done);
       const size_t nlen = cur_len >> step;
-      SC_CHAIN(pool_alloc(ctx, nlen, &nxt));
+      SC_TRY(nxt_buf.alloc(ctx, nlen));
+      nxt = nxt_buf;
       const sc::GridW gw = make_weights<sc::GridW>(ctx, r + done, step);
-      SC_CHAIN(timer_begin(ctx, SC_KIND_FOLD, step, 0, log2_of(cur_len), (u64)8 * cur_len, (u64)8 * nlen));
+      SC_TRY(timer_begin(ctx, SC_KIND_FOLD, step, 0, log2_of(cur_len), (u64)8 * cur_len, (u64)8 * nlen));
       const int grid = grid_for(ctx, nlen);
       SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::fold_wide_kernel<F>), dim3(grid), dim3(sc::kBlock), 0, ctx->stream, f, cur, nxt,
                                                       gw, step, nlen));
-      SC_CHAIN(timer_end(ctx));
+      SC_TRY(timer_end(ctx));
       cur_len = nlen;
     } else if (order == SC_ORDER_LE) {
       step = (int)std::min<size_t>(3, k - done);
       while (step > 1 && (cur_len >> step) < 2) --step;
       size_t nlen = cur_len >> step;
-      SC_CHAIN(pool_alloc(ctx, nlen, &nxt));
+      SC_TRY(nxt_buf.alloc(ctx, nlen));
+      nxt = nxt_buf;
       const sc::FoldW fw = make_weights<sc::FoldW>(ctx, r + done, step);
-      SC_CHAIN(timer_begin(ctx, SC_KIND_FOLD, step, 0, log2_of(cur_len), (u64)8 * cur_len, (u64)8 * nlen));
+      SC_TRY(timer_begin(ctx, SC_KIND_FOLD, step, 0, log2_of(cur_len), (u64)8 * cur_len, (u64)8 * nlen));
       if (nlen >= 2) {
         size_t n_units = nlen / 2;
         int grid = grid_for(ctx, n_units), threads = sc::kBlock, grab = ctx->dbg_fold_grab > 0 ? ctx->dbg_fold_grab : 1;   // four-wave blocks: one tile per draw
@@ -213,40 +199,37 @@ int fold_chain(sc_ctx* ctx, const u64* in, size_t len, const u64* r, size_t k, i
                                cur, nxt, fw, n_units, grab);
           });
         }));
-        if (ea != hipSuccess) SC_CHAIN(fail(ctx, SC_ERR_HIP, "fold_kernel: %s", hipGetErrorString(ea)));
+        if (ea != hipSuccess) SC_TRY(fail(ctx, SC_ERR_HIP, "fold_kernel: %s", hipGetErrorString(ea)));
       } else {
         SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::fold_le_small_kernel<F>), dim3(1), dim3(64), 0,
                                                         ctx->stream, f, cur, nxt, r[done], nlen));
       }
-      SC_CHAIN(timer_end(ctx));
+      SC_TRY(timer_end(ctx));
       cur_len = nlen;
     } else {
       step = 1;
       size_t half = cur_len / 2;
-      SC_CHAIN(pool_alloc(ctx, half, &nxt));
+      SC_TRY(nxt_buf.alloc(ctx, half));
+      nxt = nxt_buf;
       int grid = grid_for(ctx, (half + 1) / 2);
-      SC_CHAIN(timer_begin(ctx, SC_KIND_FOLD_BE, 1, 0, log2_of(cur_len), (u64)8 * cur_len, (u64)8 * half));
+      SC_TRY(timer_begin(ctx, SC_KIND_FOLD_BE, 1, 0, log2_of(cur_len), (u64)8 * cur_len, (u64)8 * half));
       SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::fold_be_kernel<F>), dim3(grid), dim3(sc::kBlock), 0,
                                                       ctx->stream, f, cur, nxt, r[done], half));
-      SC_CHAIN(timer_end(ctx));
+      SC_TRY(timer_end(ctx));
       cur_len = half;
     }
     {
       hipError_t le = hipGetLastError();
       if (le != hipSuccess) {
         poison(ctx);
-        pool_release(ctx, nxt);
-        pool_release(ctx, owned);
         return fail(ctx, SC_ERR_HIP, "fold launch: %s", hipGetErrorString(le));
       }
     }
-    if (owned) pool_release(ctx, owned);  // stream-ordered reuse: single stream per context
-    owned = nxt;
+    owned = std::move(nxt_buf);  // the previous intermediate goes back here (stream-ordered reuse: single stream per context)
     cur = nxt;
     done += step;
   }
-#undef SC_CHAIN
-  *out = owned;
+  *out = std::move(owned);
   *out_len = cur_len;
   return SC_OK;
 }

@@ -188,6 +188,8 @@ struct sc_ctx {
   // device-buffer pool (free blocks by capacity in words; live blocks by pointer)
   std::multimap<size_t, u64*> pool_free;
   std::map<u64*, size_t> pool_live;
+  // words out of the pool now, and their high-water mark since "stat_reset" (options "stat_pool_live_words" / "stat_pool_peak_words")
+  size_t pool_live_words = 0, pool_peak_words = 0;
 
   // sharding
   Transport transport = Transport::kNone;
@@ -352,12 +354,18 @@ struct HostField {
 
 // ---- pool ---------------------------------------------------------------------------
 
+inline void pool_count_live(sc_ctx* ctx, size_t words) {
+  ctx->pool_live_words += words;
+  ctx->pool_peak_words = std::max(ctx->pool_peak_words, ctx->pool_live_words);
+}
+
 int pool_alloc(sc_ctx* ctx, size_t words, u64** out) {
   if (words < 32) words = 32;
   auto it = ctx->pool_free.lower_bound(words);
   if (it != ctx->pool_free.end() && it->first <= 2 * words) {
     *out = it->second;
     ctx->pool_live[it->second] = it->first;
+    pool_count_live(ctx, it->first);
     ctx->pool_free.erase(it);
     return SC_OK;
   }
@@ -377,6 +385,7 @@ int pool_alloc(sc_ctx* ctx, size_t words, u64** out) {
       return fail(ctx, SC_ERR_OOM, "hipMalloc(%zu bytes): %s", words * sizeof(u64), hipGetErrorString(e));
   }
   ctx->pool_live[p] = words;
+  pool_count_live(ctx, words);
   *out = p;
   return SC_OK;
 }
@@ -386,6 +395,7 @@ void pool_release(sc_ctx* ctx, u64* p) {
   auto it = ctx->pool_live.find(p);
   if (it == ctx->pool_live.end()) return;
   ctx->pool_free.emplace(it->second, p);
+  ctx->pool_live_words -= it->second;
   ctx->pool_live.erase(it);
 }
 
@@ -401,6 +411,105 @@ int new_table(sc_ctx* ctx, size_t len, sc_table** out) {
   *out = t;
   return SC_OK;
 }
+
+// ---- owners -------------------------------------------------------------------------
+//
+// Every pool block and every table the engine makes is held by one of these two from the moment it exists: whatever way a
+// function is left, the block goes back to its context's pool.  A release is pool bookkeeping only and stream-ordered (one
+// stream per context: the kernels that use the block are already queued), so a buffer that is no longer needed is given back
+// with reset() - or by moving its successor in - right there, not at the end of the scope: the next pool_alloc reuses it.
+
+// A pool block of one context.  Like pool_release it ignores null and pointers the pool did not hand out (a prover's slot of
+// the pinned tail buffer, the pinned batch memory).
+class PoolBuf {
+ public:
+  PoolBuf() = default;
+  PoolBuf(sc_ctx* ctx, u64* p) : ctx_(ctx), p_(p) {}
+  PoolBuf(PoolBuf&& o) noexcept : ctx_(o.ctx_), p_(o.release()) {}
+  PoolBuf& operator=(PoolBuf&& o) noexcept {
+    if (this != &o) reset(o.ctx_, o.release());
+    return *this;
+  }
+  ~PoolBuf() { reset(); }
+  // a fresh block (what was held is released after the new one is allocated)
+  int alloc(sc_ctx* ctx, size_t words) {
+    u64* p = nullptr;
+    SC_TRY(pool_alloc(ctx, words, &p));
+    reset(ctx, p);
+    return SC_OK;
+  }
+  u64* get() const { return p_; }
+  operator u64*() const { return p_; }
+  u64* release() {
+    u64* p = p_;
+    p_ = nullptr;
+    return p;
+  }
+  void reset(sc_ctx* ctx = nullptr, u64* p = nullptr) {
+    if (p_) pool_release(ctx_, p_);
+    ctx_ = ctx;
+    p_ = p;
+  }
+
+ private:
+  sc_ctx* ctx_ = nullptr;
+  u64* p_ = nullptr;
+};
+
+void drop_multi_table(sc_ctx* m, sc_table* t);   // engine/multi.inc
+
+// A table: one of a context (new_table, the public table calls: freed by sc_table_free), or, `multi`, one of a multi-device
+// handle under construction (new_multi_table: freed part by part by drop_multi_table).
+class TableBuf {
+ public:
+  TableBuf() = default;
+  TableBuf(sc_ctx* ctx, sc_table* t, bool multi = false) : ctx_(ctx), t_(t), multi_(multi) {}
+  TableBuf(TableBuf&& o) noexcept : ctx_(o.ctx_), t_(o.release()), multi_(o.multi_) {}
+  TableBuf& operator=(TableBuf&& o) noexcept {
+    if (this != &o) reset(o.ctx_, o.release(), o.multi_);
+    return *this;
+  }
+  ~TableBuf() { reset(); }
+  int alloc(sc_ctx* ctx, size_t len) {
+    sc_table* t = nullptr;
+    SC_TRY(new_table(ctx, len, &t));
+    reset(ctx, t);
+    return SC_OK;
+  }
+  // a table over a block that is already there (a fold chain's result)
+  int wrap(sc_ctx* ctx, PoolBuf&& block, size_t len) {
+    sc_table* t = new (std::nothrow) sc_table;
+    if (!t) return fail(ctx, SC_ERR_OOM, "host allocation failed");
+    t->d = block.release();
+    t->len = len;
+    reset(ctx, t);
+    return SC_OK;
+  }
+  // where a call that hands a fresh table out through an sc_table** writes it: adopted as a table of ctx
+  sc_table** out(sc_ctx* ctx) {
+    reset(ctx);
+    return &t_;
+  }
+  sc_table* get() const { return t_; }
+  sc_table* operator->() const { return t_; }
+  sc_table* release() {
+    sc_table* t = t_;
+    t_ = nullptr;
+    return t;
+  }
+  void reset(sc_ctx* ctx = nullptr, sc_table* t = nullptr, bool multi = false) {
+    if (t_ && multi_) drop_multi_table(ctx_, t_);
+    else if (t_) sc_table_free(ctx_, t_);
+    ctx_ = ctx;
+    t_ = t;
+    multi_ = multi;
+  }
+
+ private:
+  sc_ctx* ctx_ = nullptr;
+  sc_table* t_ = nullptr;
+  bool multi_ = false;
+};
 
 // connecting: the call is the peer connect itself (the only thing an exported, not yet connected context may do)
 int set_device(sc_ctx* ctx, bool connecting = false) {
