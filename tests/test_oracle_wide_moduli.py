@@ -10,7 +10,8 @@ import pytest
 
 from test_host_protocols import gkr_draw_count
 from util import GOLD, oracle, pyref
-from wide_words import WIDE, edge_table, edge_words, wid
+from wide_words import (DIFF_CLASSES, WIDE, classes_of, classes_present, degenerate_challenges, diff_classes, edge_table, edge_words, octet_table,
+                        select_challenges, stride_classes, wid)
 
 
 def is_prime(n):
@@ -175,3 +176,57 @@ def test_gkr_transcript_layers_match_the_oracle(p):
             assert res["status"] == 0 and can1(p, res["c_1"]) == lr["c_1"], (ks, i)
             assert [can(p, r) for r in res["evals"]] == [list(e) for e in lr["evals"]], (ks, i)
             r_i = lr["r_next"]
+
+
+# ---- the inputs of tests/test_gpu_pass_edge_words.py ----------------------------------------------------------------------
+
+# which corners of wide_words.classes_of exist below each modulus, by reasoning: two words below p sum to 2^64 or more only
+# where p > 2^63; a borrow leaves a low limb of 0 only where two words below p differ by a multiple of 2^32, i.e. p > 2^32
+_ABSENT = {2**64 - 59: set(), 2**63 + 29: set(), GOLD: set(), 2**61 - 1: {"sum_2_64", "sum_carry"}, 2**32 + 15: {"sum_2_64", "sum_carry"},
+           2**32 - 5: {"sum_2_64", "sum_carry", "borrow_low_zero"}}
+
+
+@pytest.mark.parametrize("p", WIDE + [GOLD], ids=wid)
+def test_octet_tables_and_degenerate_challenges(p):
+    """octet tables with degenerate challenges are legal inputs on which the C oracle and pyref agree word for word (the GPU
+    tests compare the passes with the oracle on them), every transcript word is below p, and the tables really hold every
+    difference / sum class that exists for p at the strides 1, 2 and 4"""
+    o = oracle(p)
+    pairs = diff_classes(p)
+    assert all(0 <= lo < p and 0 <= hi < p for lo, hi in pairs) and len(set(pairs)) == len(pairs) <= 20
+    assert classes_present(p) == set(DIFF_CLASSES) - _ABSENT[p]
+    # the pairs the classes are named after
+    assert "borrow_low_ones" in classes_of(p, 1, 0) and "diff_minus_one" in classes_of(p, 1, 0)
+    assert "sum_p" in classes_of(p, 1, p - 1) and "sum_p" in classes_of(p, 2**64 % p, p - 2**64 % p)
+    assert classes_of(p, 0, 0) == {"diff_zero"}
+    if p > 2**63:
+        assert {"sum_2_64", "diff_zero"} <= classes_of(p, 2**63, 2**63)
+    if p > 0xFFFFFFFF00000000:
+        assert "sum_p_to_2_64" in classes_of(p, 0xFFFFFFFF00000000, 2**32 - 1)
+    one = 2**64 % p
+    assert degenerate_challenges(p, 8) == [0, one, p - 1, 1, p - 2, (p + 1) // 2, 0, one]
+    rng = np.random.default_rng(p % 1033)
+    for n in (8, 13):
+        for _ in range(2):
+            t = octet_table(p, 1 << n, rng)
+            assert t.dtype == np.uint64 and t.size == 1 << n and int(t.max()) < p
+            for s in (1, 2, 4):
+                assert stride_classes(p, t, s) >= classes_present(p), (n, s, classes_present(p) - stride_classes(p, t, s))
+    # shifted octets: a fold by select_challenges leaves a table of octets with every class again (checked with the oracle's fold)
+    for n, k in ((13, 3), (14, 4)):
+        t = octet_table(p, 1 << n, rng, shift=k)
+        sel = np.array(select_challenges(p, k), dtype=np.uint64)
+        folded = o.fix_variables(t, sel)
+        assert np.array_equal(folded, t[sum(1 << j for j in range(k) if sel[j]):: 1 << k]) and int(t.max()) < p, (n, k)
+        for s in (1, 2, 4):
+            assert stride_classes(p, folded, s) >= classes_present(p), (n, k, s)
+    for n, k in ((3, 0), (6, 0), (8, 0), (6, 2), (8, 4)):
+        a, b = octet_table(p, 1 << n, rng, shift=k), octet_table(p, 1 << n, rng, shift=k)
+        ch = np.array((select_challenges(p, k) + degenerate_challenges(p, n))[:n], dtype=np.uint64)
+        t = pyref.transcript(can(p, a), can(p, b), can(p, ch), p)
+        res = o.prove(a, b, ch)
+        assert res["status"] == 0 and can1(p, res["c_1"]) == t["c_1"], n
+        assert [can(p, r) for r in res["evals"]] == t["evals"], n
+        assert [can(p, r) for r in res["coeffs"]] == t["coeffs"], n
+        assert can1(p, res["final_eval"]) == t["final_eval"], n
+        assert res["c_1"] < p and res["final_eval"] < p and int(np.max(res["evals"])) < p and int(np.max(res["coeffs"])) < p, n
