@@ -228,6 +228,11 @@ int sc_ctx_kernel_time(sc_ctx* ctx, double out[2], int reset);
                                 * per variable (not fused): bytes = what that launch reads and writes, about p/(p-2) times the output in all */
 #define SC_KIND_MERKLE 18      /* sc_merkle_*: kf = 0 merkle_leaf_kernel (leaves up to level ks = min(n, 4)), 1 merkle_level_kernel (level ks),
                                 * 2 merkle_top_kernel (levels ks .. n in one block), 3 merkle_open_kernel (an opening's gather); log_in = n */
+#define SC_KIND_RS_ENCODE 19   /* rs_encode_rows_kernel: the row transform of sc_rs_encode_rows / sc_ligero_commit, one launch; kf = log_cols, ks = log_blowup,
+                                * log_in = n; it reads the table once (8 * 2^n bytes) and writes the codewords once (8 * 2^(n + log_blowup)) */
+#define SC_KIND_LIGERO 20      /* sc_ligero_*: kf = 0 column_leaf_kernel (ks = log2 rows; reads E, writes L digests), 1 row_combine_kernel (ks = the
+                                * number of weight vectors; ks = 0: the launch that adds the row ranges' partial sums), 2 column_open_kernel
+                                * (ks = openings of the launch); log_in = n.  The tree levels above the leaves are SC_KIND_MERKLE records */
 typedef struct sc_launch_record {
   int32_t kind;           /* SC_KIND_* */
   int32_t kf, ks;         /* variables folded / rounds served (meaning per kind above) */
@@ -522,6 +527,33 @@ int sc_merkle_depth(const sc_merkle_tree* tr, size_t* depth);
  * index is 0, else H(s_l || h); then h must equal the root.  SC_ERR_ARG: an index >= N. */
 int sc_merkle_open(sc_ctx* ctx, const sc_merkle_tree* tr, const uint64_t* index, size_t count, uint64_t* leaves, uint8_t* paths);
 int sc_merkle_tree_destroy(sc_ctx* ctx, sc_merkle_tree* tr);
+
+/* ---- Ligero-style polynomial commitment: row Reed-Solomon encoding, column Merkle tree ----------------------------------
+ * (Thaler's book, section 10.5; kernels/ligero.hpp states the contract.)  A table of 2^n entries is 2^(n - log_cols) rows of
+ * 2^log_cols columns (row i = entries i 2^log_cols ..); every row, as the coefficients of a polynomial, is evaluated at the
+ * L = 2^(log_cols + log_blowup) powers of w_L in natural order; leaf j of the tree is SHA-256 over column j of that matrix
+ * (canonical values, 8 little-endian bytes each), nodes as sc_merkle_*.  w_L = w_max^(2^(s - log_cols - log_blowup)) with s the
+ * 2-adicity of p - 1, w_max = g^((p-1)/2^s), g the smallest integer >= 2 with g^((p-1)/2) = -1: derived by the library.
+ * SC_ERR_ARG: a null pointer, a table that is not 2^n long, log_cols > n, log_blowup not 1 or 2, more than 4 weight vectors, a
+ * column index >= L, a commitment of another context.  SC_ERR_UNSUPPORTED: log_cols + log_blowup > 14 (one codeword has to fit the
+ * LDS of a CU), n + log_blowup > 29, log_cols + log_blowup > s (the message names p and s), a sharded context or a multi-device
+ * handle. */
+
+/* the codeword matrix alone: *out has 2^(n + log_blowup) entries, E[i][j] at i L + j, Montgomery like every table */
+int sc_rs_encode_rows(sc_ctx* ctx, const sc_table* t, size_t log_cols, size_t log_blowup, sc_table** out);
+/* encode and hash.  t is borrowed: it must outlive the commitment, unchanged (sc_ligero_combine_rows reads it).  The commitment
+ * owns the codeword matrix and every level of the tree (at most 1 MiB). */
+typedef struct sc_ligero sc_ligero;
+int sc_ligero_commit(sc_ctx* ctx, const sc_table* t, size_t log_cols, size_t log_blowup, sc_ligero** out);
+int sc_ligero_root(const sc_ligero* lg, uint8_t root[32]);
+int sc_ligero_shape(const sc_ligero* lg, size_t* log_rows, size_t* log_cols, size_t* log_blowup);
+/* out[m][k] = sum_i weights[m][i] * t[i 2^log_cols + k] for count <= 4 vectors of 2^log_rows Montgomery words, in one read of the
+ * table; out is count x 2^log_cols words.  count = 0 does nothing. */
+int sc_ligero_combine_rows(sc_ctx* ctx, const sc_ligero* lg, const uint64_t* weights, size_t count, uint64_t* out);
+/* values[q][2^log_rows] = column cols[q] of the codeword matrix (Montgomery words), paths[q][log_cols + log_blowup][32] = the
+ * sibling digests of leaf cols[q] bottom up (verified as sc_merkle_open's, from the column's leaf digest).  Indices may repeat. */
+int sc_ligero_open_columns(sc_ctx* ctx, const sc_ligero* lg, const uint64_t* cols, size_t count, uint64_t* values, uint8_t* paths);
+int sc_ligero_destroy(sc_ctx* ctx, sc_ligero* lg);
 
 /* ---- gkr_protocol::circuit::Circuit on the device, and the whole GKR prover over it ----------------------------------
  * A circuit lives on ONE context of one device and one rank: sharded contexts (world > 1) and multi-device handles get

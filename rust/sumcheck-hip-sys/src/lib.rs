@@ -95,6 +95,10 @@ pub struct sc_circuit {
 pub struct sc_merkle_tree {
     _private: [u8; 0],
 }
+#[repr(C)]
+pub struct sc_ligero {
+    _private: [u8; 0],
+}
 
 pub type sc_allreduce_fn = Option<unsafe extern "C" fn(user: *mut c_void, buf: *mut u64, count: usize) -> c_int>;
 pub type sc_allgather_fn =
@@ -470,4 +474,23 @@ extern "C" {
         paths: *mut u8,
     ) -> c_int;
     pub fn sc_merkle_tree_destroy(ctx: *mut sc_ctx, tr: *mut sc_merkle_tree) -> c_int;
+
+    /// Ligero-style commitment: every row of `t` (2^log_cols coefficients) evaluated at the 2^(log_cols + log_blowup) powers of w_L
+    pub fn sc_rs_encode_rows(ctx: *mut sc_ctx, t: *const sc_table, log_cols: usize, log_blowup: usize, out: *mut *mut sc_table) -> c_int;
+    /// encode the rows and Merkle-hash the columns of the codeword matrix; `t` is borrowed and must outlive the commitment
+    pub fn sc_ligero_commit(ctx: *mut sc_ctx, t: *const sc_table, log_cols: usize, log_blowup: usize, out: *mut *mut sc_ligero) -> c_int;
+    pub fn sc_ligero_root(lg: *const sc_ligero, root: *mut u8) -> c_int;
+    pub fn sc_ligero_shape(lg: *const sc_ligero, log_rows: *mut usize, log_cols: *mut usize, log_blowup: *mut usize) -> c_int;
+    /// out[count][2^log_cols] = the combinations of the rows by `count` <= 4 weight vectors of 2^log_rows words
+    pub fn sc_ligero_combine_rows(ctx: *mut sc_ctx, lg: *const sc_ligero, weights: *const u64, count: usize, out: *mut u64) -> c_int;
+    /// values[count][2^log_rows] Montgomery, paths[count][log_cols + log_blowup][32] bottom up
+    pub fn sc_ligero_open_columns(
+        ctx: *mut sc_ctx,
+        lg: *const sc_ligero,
+        cols: *const u64,
+        count: usize,
+        values: *mut u64,
+        paths: *mut u8,
+    ) -> c_int;
+    pub fn sc_ligero_destroy(ctx: *mut sc_ctx, lg: *mut sc_ligero) -> c_int;
 }

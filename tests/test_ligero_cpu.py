@@ -1,0 +1,123 @@
+"""CPU-only: the Ligero-style commitment's reference (tests/ligero_ref.py) against the defining sums and the contract's constants,
+and the package's host Verifier (thaler-study_amd/ligero_pcs.py) against the reference prover: honest transcripts are accepted
+with the right value, every tampered message is refused with its own error."""
+import random
+
+import pytest
+
+import ligero_ref as ref
+from conftest import load_package
+
+GOLD = ref.GOLD
+
+
+@pytest.fixture(scope="module")
+def lp():
+    return load_package().ligero_pcs
+
+
+@pytest.mark.parametrize("p", ref.FIELDS)
+def test_reference_ntt_equals_the_direct_sum(p):
+    rng = random.Random(p)
+    for log_len in range(0, 7):
+        L = 1 << log_len
+        w = ref.omega(p, log_len)
+        for row in ([rng.randrange(p) for _ in range(L)], [p - 1] * L, [rng.randrange(p) for _ in range(L // 2)] + [0] * (L - L // 2)):
+            want = [ref.direct(row, w, p, j) for j in range(L)]
+            assert ref.ntt(row, w, p) == want, (p, log_len)
+            assert [int(x) for x in ref.ntt_rows_np([row, row], w, p)[1]] == want, (p, log_len)
+
+
+@pytest.mark.parametrize("p", ref.FIELDS)
+def test_derived_roots_are_the_contracts(p, lp):
+    assert ref.two_adic(p) == ref.ROOTS[p]
+    assert lp.two_adic_root(p) == ref.ROOTS[p]
+    s = ref.ROOTS[p][0]
+    F = load_package().Field(p)
+    for log_len in range(0, min(s, 16) + 1):
+        w = ref.omega(p, log_len)
+        assert pow(w, 1 << log_len, p) == 1 and (log_len == 0 or pow(w, 1 << (log_len - 1), p) == p - 1), (p, log_len)   # order exactly L
+        assert lp.root_of_unity(F, log_len) == F.from_int(w)
+    with pytest.raises(ValueError):
+        lp.root_of_unity(F, s + 1)
+
+
+def test_encode_is_the_contracts_sum():
+    """E[i][j] = sum_k w[i C + k] w_L^(j k): both transforms, through encode(), on a 4 x 8 table with rho = 1 and 2"""
+    for p in (GOLD, 65537):
+        rng = random.Random(7)
+        table = [rng.randrange(p) for _ in range(32)]
+        for rho in (1, 2):
+            E = ref.encode(table, 3, rho, p)
+            w = ref.omega(p, 3 + rho)
+            assert len(E) == 4 and all(len(row) == 8 << rho for row in E)
+            for i in range(4):
+                assert E[i] == [ref.direct(table[8 * i:8 * i + 8], w, p, j) for j in range(8 << rho)]
+
+
+def run_protocol(pkg, p, n, c, rho, queries, seed, tamper=None):
+    """the reference prover against the package's Verifier; `tamper` names the message to corrupt.  Returns (value, expected)"""
+    lp = pkg.ligero_pcs
+    F = pkg.Field(p)
+    rng = random.Random(seed)
+    table = [rng.randrange(p) for _ in range(1 << n)]
+    prover = ref.RefProver(table, c, rho, p)
+    root = prover.root()
+    if tamper == "root":
+        root = bytes([root[0] ^ 1]) + root[1:]
+    v = lp.Verifier(F, n, c, rho, root, queries)
+    gamma = v.draw_gamma(rng)
+    point = [F.rand(rng) for _ in range(n)]
+    u_gamma, u_z = prover.combine(ref.canon(p, point), ref.canon(p, gamma))
+    u_gamma, u_z = ref.mont(p, u_gamma), ref.mont(p, u_z)
+    if tamper == "u_z":
+        u_z[len(u_z) // 2] = F.add(u_z[len(u_z) // 2], F.one)
+    if tamper == "u_gamma":
+        u_gamma[0] = F.add(u_gamma[0], F.one)
+    v.receive(u_gamma, u_z)
+    cols = v.draw_columns(rng)
+    openings = [(j, ref.mont(p, vals), lp.ColumnPath(j, sib, F)) for j, vals, sib in prover.open_columns(cols)]
+    if tamper == "column":
+        j, vals, path = openings[3]
+        openings[3] = (j, [F.add(vals[0], F.one)] + vals[1:], path)
+    if tamper == "path":
+        j, vals, path = openings[5]
+        sib = list(path.siblings)
+        sib[-1] = bytes(32)
+        openings[5] = (j, vals, lp.ColumnPath(j, sib, F))
+    value = v.verify(point, openings)
+    return value, F.from_int(ref.mle_eval(table, ref.canon(p, point), p))
+
+
+@pytest.mark.parametrize("p,n,c,rho", [(GOLD, 6, 3, 1), (GOLD, 6, 2, 2), (65537, 5, 3, 1), (65537, 5, 0, 2)])
+def test_verifier_accepts_the_reference_prover(pkg, p, n, c, rho):
+    value, want = run_protocol(pkg, p, n, c, rho, 16, 100 * n + c)
+    assert value == want
+
+
+@pytest.mark.parametrize("p,n,c", [(GOLD, 6, 3), (65537, 5, 3)])
+def test_tampering_is_caught(pkg, p, n, c):
+    lp = pkg.ligero_pcs
+    for tamper, err in (("u_z", lp.EvalMismatch), ("u_gamma", lp.ProximityMismatch), ("column", lp.MerkleMismatch),
+                        ("path", lp.MerkleMismatch), ("root", lp.MerkleMismatch)):
+        with pytest.raises(err):
+            run_protocol(pkg, p, n, c, 1, 16, 31, tamper=tamper)
+
+
+def test_draw_columns_before_receive_raises(pkg):
+    lp = pkg.ligero_pcs
+    v = lp.Verifier(pkg.Field(GOLD), 6, 3, 1, bytes(32), 16)
+    rng = random.Random(1)
+    with pytest.raises(lp.Error):
+        v.draw_columns(rng)
+    v.draw_gamma(rng)
+    with pytest.raises(lp.Error):
+        v.draw_columns(rng)
+    with pytest.raises(lp.Error):
+        v.verify([0] * 6, [])
+
+
+def test_errors_are_the_relaxed_pcs_family(pkg):
+    lp, rp = pkg.ligero_pcs, pkg.relaxed_pcs
+    assert lp.MerkleMismatch is rp.MerkleMismatch and lp.EvalMismatch is rp.EvalMismatch
+    assert issubclass(lp.ProximityMismatch, rp.Error) and issubclass(lp.ColumnPath, rp.Path)

@@ -140,6 +140,8 @@ extern "C" int sc_ctx_destroy(sc_ctx* ctx) {
   if (ctx->h_tail) (void)hipHostFree(ctx->h_tail);
   if (ctx->h_points) (void)hipHostFree(ctx->h_points);
   if (ctx->d_points) (void)hipFree(ctx->d_points);
+  for (u64* tw : ctx->d_rs_twiddles)
+    if (tw) (void)hipFree(tw);
   if (ctx->h_batch_desc) (void)hipHostFree(ctx->h_batch_desc);
   if (ctx->h_batch) (void)hipHostFree(ctx->h_batch);
   if (ctx->d_ticket) (void)hipFree(ctx->d_ticket);

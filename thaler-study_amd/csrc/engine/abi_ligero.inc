@@ -1,0 +1,295 @@
+// Part of sumcheck_hip.hip (included there, in order): C ABI: the Ligero-style commitment - Reed-Solomon encoding of the rows of a
+// table, the SHA-256 Merkle tree over the columns of the codeword matrix, and what an opening needs: linear combinations of
+// the rows and opened columns (kernels/ligero.hpp states the contract).
+
+// A commitment: the codeword matrix E (owned) and every level of the tree over its L columns, bottom up, 8 words per node.
+struct sc_ligero {
+  const sc_ctx* ctx = nullptr;
+  const sc_table* t = nullptr;   // borrowed: must outlive the commitment
+  int r = 0, c = 0, rho = 0;
+  TableBuf E;
+  PoolBuf d_levels;
+  uint32_t root[8] = {};
+};
+
+namespace {
+
+constexpr size_t kLigeroOpenWords = (size_t)1 << 22;   // column words gathered per launch of column_open_kernel
+
+// s, the 2-adicity of p - 1, and w_max = g^((p-1)/2^s) (Montgomery) for the smallest g >= 2 with g^((p-1)/2) = -1
+void two_adic_root(const HostField& hf, int* s_out, u64* w_max) {
+  const u64 p = hf.f.p;
+  int s = 0;
+  while ((((p - 1) >> s) & 1) == 0) ++s;
+  const u64 minus_one = hf.neg(hf.one());
+  u64 g = hf.add(hf.one(), hf.one());
+  while (hf.pow(g, (p - 1) / 2) != minus_one) g = hf.add(g, hf.one());
+  *s_out = s;
+  *w_max = hf.pow(g, (p - 1) >> s);
+}
+
+// the checks sc_rs_encode_rows and sc_ligero_commit share; *n = log2 of the table
+int ligero_shape(sc_ctx* ctx, const sc_table* t, size_t log_cols, size_t log_blowup, const char* what, int* n) {
+  SC_TRY(pcs_one_device(ctx, what));
+  SC_TRY(check_table(ctx, t, what));
+  *n = log2_of(t->len);
+  if (log_blowup < 1 || log_blowup > 2) return fail(ctx, SC_ERR_ARG, "%s: log_blowup is %zu, not 1 or 2", what, log_blowup);
+  if (log_cols > (size_t)*n) return fail(ctx, SC_ERR_ARG, "%s: log_cols = %zu exceeds the table's %d variables", what, log_cols, *n);
+  if (log_cols + log_blowup > (size_t)sc::kRsMaxLog)
+    return fail(ctx, SC_ERR_UNSUPPORTED, "%s: a codeword of 2^(%zu+%zu) words does not fit the LDS of a CU (at most 2^%d)", what, log_cols,
+                log_blowup, sc::kRsMaxLog);
+  if (*n + log_blowup > 29) return fail(ctx, SC_ERR_UNSUPPORTED, "%s: 2^(%d+%zu) codeword words (at most 2^29)", what, *n, log_blowup);
+  int s = 0;
+  while ((((ctx->fp.p - 1) >> s) & 1) == 0) ++s;
+  if (log_cols + log_blowup > (size_t)s)
+    return fail(ctx, SC_ERR_UNSUPPORTED, "%s: p = %llu has 2-adicity %d: no root of unity of order 2^(%zu+%zu)", what,
+                (unsigned long long)ctx->fp.p, s, log_cols, log_blowup);
+  return SC_OK;
+}
+
+// the powers w_L^i, i < L/2 (at least one word), of this context, built on the host at first use; and the powers of W16
+int rs_twiddles(sc_ctx* ctx, int log_len, const u64** tw, sc::RsRoots* roots) {
+  const HostField hf(ctx->fp);
+  if (!ctx->rs_root_known) {
+    two_adic_root(hf, &ctx->rs_two_adicity, &ctx->rs_w_max);
+    ctx->rs_root_known = true;
+  }
+  const int s = ctx->rs_two_adicity;
+  for (int k = 0; k < 8; ++k) {
+    // W16^k = w_max^(k 2^s / 16) where the field has that root
+    const int tz = k ? __builtin_ctz(k) : 4;
+    roots->w16[k] = s + tz >= 4 ? hf.pow(ctx->rs_w_max, s >= 4 ? (u64)k << (s - 4) : (u64)k >> (4 - s)) : 0;
+  }
+  if (!ctx->d_rs_twiddles[log_len]) {
+    u64 w = ctx->rs_w_max;
+    for (int k = s; k > log_len; --k) w = hf.mul(w, w);
+    const size_t half = std::max<size_t>(1, ((size_t)1 << log_len) / 2);
+    std::vector<u64> h(half);
+    h[0] = hf.one();
+    for (size_t i = 1; i < half; ++i) h[i] = hf.mul(h[i - 1], w);
+    u64* d = nullptr;
+    SC_HIP(ctx, hipMalloc(&d, half * sizeof(u64)));
+    if (hipMemcpy(d, h.data(), half * sizeof(u64), hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipFree(d);
+      poison(ctx);
+      return fail(ctx, SC_ERR_HIP, "twiddle upload failed");
+    }
+    ctx->d_rs_twiddles[log_len] = d;
+  }
+  *tw = ctx->d_rs_twiddles[log_len];
+  return SC_OK;
+}
+
+// E = the encoding of the 2^(n-c) rows of `in`: one launch, every word of `in` read once and every word of E written once
+int rs_encode_impl(sc_ctx* ctx, const u64* in, int n, int c, int rho, u64* E) {
+  const int log_len = c + rho, tile_log = sc::rs_tile_log(log_len, n + rho);
+  const u64* tw = nullptr;
+  sc::RsRoots roots;
+  SC_TRY(rs_twiddles(ctx, log_len, &tw, &roots));
+  const size_t lds = sc::rs_lds_words(tile_log) * sizeof(u64);
+  const unsigned blocks = 1u << (n + rho - tile_log);
+  const int vec = (tile_log - rho >= 1) && ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(E)) & 15) == 0;
+  hipError_t ea = hipSuccess;
+  SC_TRY(timer_begin(ctx, SC_KIND_RS_ENCODE, c, rho, n, (u64)8 << n, (u64)8 << (n + rho)));
+  SC_DISPATCH_FIELD(ctx, F, f, {
+    if (lds > 65536 && !ctx->rs_lds_allowed[ctx->gold ? 1 : 0]) {
+      ea = hipFuncSetAttribute(kernel_ptr(&sc::rs_encode_rows_kernel<F>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)(sc::rs_lds_words(sc::kRsMaxLog) * sizeof(u64)));
+      if (ea == hipSuccess) ctx->rs_lds_allowed[ctx->gold ? 1 : 0] = true;
+    }
+    if (ea == hipSuccess)
+      hipLaunchKernelGGL((sc::rs_encode_rows_kernel<F>), dim3(blocks), dim3(sc::rs_threads(tile_log, sc::rs_max_threads<F>())), lds, ctx->stream, f, in, E, tw, roots, c, rho, tile_log,
+                         vec);
+  });
+  SC_HIP(ctx, ea);
+  SC_TRY(pcs_launched(ctx, "rs_encode_rows_kernel"));
+  SC_TRY(timer_end(ctx));
+  return SC_OK;
+}
+
+// column_leaf_kernel over E, one merkle_level_kernel launch per level while a level has more than kMerkleTopNodes nodes, then the
+// rest of the tree in one block (the kernels of the Relaxed PCS, unchanged); the root comes back to the host.
+int ligero_tree_build(sc_ctx* ctx, sc_ligero* lg) {
+  const int depth = lg->c + lg->rho, n = lg->r + lg->c;
+  const u64 L = (u64)1 << depth, R = (u64)1 << lg->r;
+  u32* in = reinterpret_cast<u32*>(lg->d_levels.get());
+  SC_TRY(timer_begin(ctx, SC_KIND_LIGERO, 0, lg->r, n, 8 * R * L, 32 * L));
+  SC_DISPATCH_FIELD(ctx, F, f,
+                    hipLaunchKernelGGL((sc::column_leaf_kernel<F>), dim3(pcs_grid(ctx, L)), dim3(sc::kBlock), 0, ctx->stream, f,
+                                       (const u64*)lg->E->d, (u32)R, (u32)L, in));
+  SC_TRY(pcs_launched(ctx, "column_leaf_kernel"));
+  SC_TRY(timer_end(ctx));
+  u64 in_nodes = L;
+  int level = 0;
+  while (in_nodes > 2 * (u64)sc::kMerkleTopNodes) {
+    const u64 nodes = in_nodes / 2;
+    u32* out = in + 8 * in_nodes;
+    SC_TRY(timer_begin(ctx, SC_KIND_MERKLE, 1, level + 1, depth, 32 * in_nodes, 32 * nodes));
+    hipLaunchKernelGGL(sc::merkle_level_kernel, dim3(pcs_grid(ctx, nodes)), dim3(sc::kBlock), 0, ctx->stream, (const u32*)in, nodes, out);
+    SC_TRY(pcs_launched(ctx, "merkle_level_kernel"));
+    SC_TRY(timer_end(ctx));
+    in = out;
+    in_nodes = nodes;
+    ++level;
+  }
+  if (in_nodes > 1) {
+    SC_TRY(timer_begin(ctx, SC_KIND_MERKLE, 2, level + 1, depth, 32 * (2 * in_nodes - 2), 32 * (in_nodes - 1)));
+    hipLaunchKernelGGL(sc::merkle_top_kernel, dim3(1), dim3(sc::kBlock), 0, ctx->stream, in, (u32)in_nodes);
+    SC_TRY(pcs_launched(ctx, "merkle_top_kernel"));
+    SC_TRY(timer_end(ctx));
+  }
+  SC_HIP(ctx, hipMemcpyAsync(lg->root, reinterpret_cast<const u32*>(lg->d_levels.get()) + 8 * (2 * L - 2), 32, hipMemcpyDeviceToHost,
+                             ctx->stream));
+  SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SC_OK;
+}
+
+int ligero_check(sc_ctx* ctx, const sc_ligero* lg, const char* what) {
+  if (lg->ctx != ctx) return fail(ctx, SC_ERR_ARG, "%s: the commitment belongs to another context", what);
+  return SC_OK;
+}
+
+}  // namespace
+
+extern "C" int sc_rs_encode_rows(sc_ctx* ctx, const sc_table* t, size_t log_cols, size_t log_blowup, sc_table** out) {
+  if (!ctx || !out) return SC_ERR_ARG;
+  *out = nullptr;
+  int n = 0;
+  SC_TRY(ligero_shape(ctx, t, log_cols, log_blowup, "sc_rs_encode_rows", &n));
+  SC_TRY(set_device(ctx));
+  TableBuf E;
+  SC_TRY(E.alloc(ctx, (size_t)1 << (n + log_blowup)));
+  SC_TRY(rs_encode_impl(ctx, t->d, n, (int)log_cols, (int)log_blowup, E->d));
+  *out = E.release();
+  return SC_OK;
+}
+
+extern "C" int sc_ligero_commit(sc_ctx* ctx, const sc_table* t, size_t log_cols, size_t log_blowup, sc_ligero** out) {
+  if (!ctx || !out) return SC_ERR_ARG;
+  *out = nullptr;
+  int n = 0;
+  SC_TRY(ligero_shape(ctx, t, log_cols, log_blowup, "sc_ligero_commit", &n));
+  SC_TRY(set_device(ctx));
+  sc_ligero* lg = new (std::nothrow) sc_ligero;
+  if (!lg) return fail(ctx, SC_ERR_OOM, "host allocation failed");
+  lg->ctx = ctx;
+  lg->t = t;
+  lg->c = (int)log_cols;
+  lg->r = n - lg->c;
+  lg->rho = (int)log_blowup;
+  int rc = lg->E.alloc(ctx, (size_t)1 << (n + lg->rho));
+  if (rc == SC_OK) rc = lg->d_levels.alloc(ctx, 4 * (((size_t)2 << (lg->c + lg->rho)) - 1));
+  if (rc == SC_OK) rc = rs_encode_impl(ctx, t->d, n, lg->c, lg->rho, lg->E->d);
+  if (rc == SC_OK) rc = ligero_tree_build(ctx, lg);
+  if (rc != SC_OK) {
+    delete lg;
+    return rc;
+  }
+  *out = lg;
+  return SC_OK;
+}
+
+extern "C" int sc_ligero_root(const sc_ligero* lg, uint8_t root[32]) {
+  if (!lg || !root) return SC_ERR_ARG;
+  put_digest(root, lg->root);
+  return SC_OK;
+}
+
+extern "C" int sc_ligero_shape(const sc_ligero* lg, size_t* log_rows, size_t* log_cols, size_t* log_blowup) {
+  if (!lg || !log_rows || !log_cols || !log_blowup) return SC_ERR_ARG;
+  *log_rows = (size_t)lg->r;
+  *log_cols = (size_t)lg->c;
+  *log_blowup = (size_t)lg->rho;
+  return SC_OK;
+}
+
+// out[m][k] = sum_i weights[m][i] w[i C + k]: the weights go to a pool buffer, one launch reads the table once (row ranges per
+// block), a second adds the ranges' partial sums
+extern "C" int sc_ligero_combine_rows(sc_ctx* ctx, const sc_ligero* lg, const uint64_t* weights, size_t count, uint64_t* out) {
+  if (!ctx || !lg) return SC_ERR_ARG;
+  SC_TRY(ligero_check(ctx, lg, "sc_ligero_combine_rows"));
+  if (count > (size_t)sc::kLigeroMaxCombine)
+    return fail(ctx, SC_ERR_ARG, "sc_ligero_combine_rows: %zu weight vectors (at most %d per call)", count, sc::kLigeroMaxCombine);
+  if (count == 0) return SC_OK;
+  if (!weights || !out) return fail(ctx, SC_ERR_ARG, "sc_ligero_combine_rows: null array");
+  SC_TRY(set_device(ctx));
+  const u64 R = (u64)1 << lg->r, C = (u64)1 << lg->c;
+  const int V = (lg->c >= 1 && (reinterpret_cast<uintptr_t>(lg->t->d) & 15) == 0) ? 2 : 1;
+  const unsigned bx = (unsigned)((C / V + sc::kBlock - 1) / sc::kBlock);
+  // row ranges: enough blocks for four per CU, none shorter than 256 rows
+  u64 splits = 1;
+  while (splits * 2 * bx <= (u64)4 * ctx->num_cus && splits * 2 * 256 <= R && splits < 32768) splits *= 2;
+  const u64 rows_per = R / splits, words = count * C;
+  PoolBuf d_w, d_part, d_out;
+  SC_TRY(d_w.alloc(ctx, count * R));
+  SC_TRY(d_out.alloc(ctx, words));
+  if (splits > 1) SC_TRY(d_part.alloc(ctx, splits * words));
+  SC_HIP(ctx, hipMemcpyAsync(d_w, weights, count * R * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
+  u64* part = splits > 1 ? d_part.get() : d_out.get();
+  SC_TRY(timer_begin(ctx, SC_KIND_LIGERO, 1, (int)count, lg->r + lg->c, 8 * (R * C + count * R), 8 * splits * words));
+  SC_DISPATCH_FIELD(ctx, F, f, with_const<1, 2, 3, 4>((int)count, [&](auto M) {
+                      with_const<1, 2>(V, [&](auto VV) {
+                        hipLaunchKernelGGL((sc::row_combine_kernel<F, M, VV>), dim3(bx, (unsigned)splits), dim3(sc::kBlock), 0, ctx->stream, f,
+                                           (const u64*)lg->t->d, (const u64*)d_w.get(), R, rows_per, (sc::u32)C, part);
+                      });
+                    }));
+  SC_TRY(pcs_launched(ctx, "row_combine_kernel"));
+  SC_TRY(timer_end(ctx));
+  if (splits > 1) {
+    SC_TRY(timer_begin(ctx, SC_KIND_LIGERO, 1, 0, lg->r + lg->c, 8 * splits * words, 8 * words));
+    SC_DISPATCH_FIELD(ctx, F, f,
+                      hipLaunchKernelGGL((sc::row_combine_sum_kernel<F>), dim3(pcs_grid(ctx, words)), dim3(sc::kBlock), 0, ctx->stream, f,
+                                         (const u64*)d_part.get(), (sc::u32)splits, (sc::u32)words, d_out.get()));
+    SC_TRY(pcs_launched(ctx, "row_combine_sum_kernel"));
+    SC_TRY(timer_end(ctx));
+  }
+  SC_HIP(ctx, hipMemcpyAsync(out, d_out, words * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+  SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SC_OK;
+}
+
+// values[q][R] (Montgomery) and paths[q][c+rho][32] of the columns cols[q]
+extern "C" int sc_ligero_open_columns(sc_ctx* ctx, const sc_ligero* lg, const uint64_t* cols, size_t count, uint64_t* values,
+                                      uint8_t* paths) {
+  if (!ctx || !lg) return SC_ERR_ARG;
+  SC_TRY(ligero_check(ctx, lg, "sc_ligero_open_columns"));
+  if (count == 0) return SC_OK;
+  if (!cols || !values || !paths) return fail(ctx, SC_ERR_ARG, "sc_ligero_open_columns: null array");
+  const int depth = lg->c + lg->rho;
+  const u64 L = (u64)1 << depth, R = (u64)1 << lg->r;
+  for (size_t q = 0; q < count; ++q)
+    if (cols[q] >= L)
+      return fail(ctx, SC_ERR_ARG, "sc_ligero_open_columns: column %llu of opening %zu is not below L = 2^%d", (unsigned long long)cols[q], q,
+                  depth);
+  SC_TRY(set_device(ctx));
+  const size_t chunk = std::min<size_t>(count, std::max<size_t>(1, kLigeroOpenWords / R));
+  PoolBuf buf;
+  SC_TRY(buf.alloc(ctx, chunk * (1 + R + 4 * (size_t)depth)));
+  u64* d_idx = buf;
+  u64* d_vals = d_idx + chunk;
+  u32* d_sib = reinterpret_cast<u32*>(d_vals + chunk * R);
+  std::vector<u32> hs(chunk * depth * 8);
+  for (size_t q0 = 0; q0 < count; q0 += chunk) {
+    const size_t k = std::min(chunk, count - q0);
+    const u64 moved = (u64)k * (8 * R + 32 * depth);
+    SC_HIP(ctx, hipMemcpyAsync(d_idx, cols + q0, k * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
+    SC_TRY(timer_begin(ctx, SC_KIND_LIGERO, 2, (int)std::min<size_t>(k, 1u << 30), lg->r + lg->c, moved, moved));
+    hipLaunchKernelGGL(sc::column_open_kernel, dim3((unsigned)std::min<size_t>(k, (size_t)8 * ctx->num_cus)), dim3(sc::kBlock), 0, ctx->stream,
+                       (const u64*)lg->E->d, reinterpret_cast<const u32*>(lg->d_levels.get()), (const u64*)d_idx, (u32)k, R, (u32)L, depth,
+                       d_vals, d_sib);
+    SC_TRY(pcs_launched(ctx, "column_open_kernel"));
+    SC_TRY(timer_end(ctx));
+    SC_HIP(ctx, hipMemcpyAsync(values + q0 * R, d_vals, k * R * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+    SC_HIP(ctx, hipMemcpyAsync(hs.data(), d_sib, k * depth * 32, hipMemcpyDeviceToHost, ctx->stream));
+    SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t e = 0; e < k * depth; ++e) put_digest(paths + (q0 * depth + e) * 32, &hs[e * 8]);
+  }
+  return SC_OK;
+}
+
+extern "C" int sc_ligero_destroy(sc_ctx* ctx, sc_ligero* lg) {
+  if (!lg) return SC_OK;
+  if (!ctx || lg->ctx != ctx) return SC_ERR_ARG;
+  delete lg;
+  return SC_OK;
+}

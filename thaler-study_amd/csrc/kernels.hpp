@@ -258,4 +258,5 @@ __device__ __forceinline__ void transpose_to_pieces(ull2* __restrict__ lds, ull2
 #include "kernels/matmul.hpp"
 #include "kernels/batch.hpp"
 #include "kernels/pcs.hpp"
+#include "kernels/ligero.hpp"
 #include "kernels/peer.hpp"

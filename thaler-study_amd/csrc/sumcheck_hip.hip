@@ -249,6 +249,13 @@ struct sc_ctx {
   u64* h_batch = nullptr;
   u64* d_batch = nullptr;
   size_t batch_words = 0;
+  // sc_rs_encode_rows / sc_ligero_commit (engine/abi_ligero.inc): the field's two-adic root, found at first use, and the device
+  // tables of the powers of w_L, one per codeword length 2^k used so far (workspace like d_points: not pool blocks)
+  bool rs_root_known = false;
+  int rs_two_adicity = 0;
+  u64 rs_w_max = 0;
+  u64* d_rs_twiddles[15] = {};
+  bool rs_lds_allowed[2] = {};   // rs_encode_rows_kernel<generic / Goldilocks>: its dynamic LDS above 64 KiB has been requested
 
   // kernel timing
   // pass-kernel timing (option "time_kernels"): a ring of event pairs, read back only when the
@@ -583,4 +590,5 @@ static int multi_prod2_fold_and_sums(sc_ctx* m, const sc_table* a, const sc_tabl
 #include "engine/abi_batch.inc"
 #include "engine/abi_restrict.inc"
 #include "engine/abi_pcs.inc"
+#include "engine/abi_ligero.inc"
 #include "engine/abi_multi.inc"

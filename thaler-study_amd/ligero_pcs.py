@@ -1,0 +1,244 @@
+"""A Ligero-style polynomial commitment on the GPU (Thaler, "Proofs, Arguments, and Zero-Knowledge", section 10.5).
+
+The table of a multilinear polynomial in n variables is a matrix of R = 2^r rows by C = 2^c columns (n = r + c; variables
+0..c-1 select the column, c..n-1 the row).  The prover Reed-Solomon-encodes every row (sc_rs_encode_rows: the row as the
+coefficients of a polynomial, evaluated at the L = 2^(c + log_blowup) powers of w_L) and commits to the COLUMNS of the codeword
+matrix with a SHA-256 Merkle tree (sc_ligero_commit).  An evaluation at z is opened interactively:
+
+  1. the prover sends the root                                   4. the verifier draws `queries` columns in [0, L), with replacement
+  2. the verifier sends gamma in F^R                             5. the prover opens each: its R values and its path
+  3. the prover sends u_gamma = sum_i gamma_i row_i and          6. per column j the verifier checks the path against the root,
+     u_z = sum_i eq(z[c:], i) row_i (C words each)                  Enc(u_gamma)[j] = sum_i gamma_i col_j[i] and Enc(u_z)[j] = sum_i eq_i col_j[i]
+                                                                 7. the value is <u_z, eq(z[:c])>
+
+Enc(u)[j] is u, as coefficients, evaluated at w_L^j (Horner).  The verifier is host code (hashlib) and never touches the GPU.
+
+Contract (kernels/ligero.hpp):
+  root of unity  s = the 2-adicity of p - 1, g the smallest integer >= 2 with g^((p-1)/2) = -1, w_max = g^((p-1)/2^s),
+                 w_L = w_max^(2^(s - c - log_blowup))
+  leaf j         SHA-256(le64(canon E[0][j]) || .. || le64(canon E[R-1][j])); nodes SHA-256(left || right); paths bottom up
+  limits         c + log_blowup <= 14 and <= s, n + log_blowup <= 29, log_blowup in {1, 2}, one device and one rank
+
+Field elements are Montgomery words, as everywhere in this package; leaves hash canonical integers.  `queries` is the caller's
+parameter: DESIGN.md gives the book's soundness expression for it; no security level is claimed here."""
+import ctypes
+import hashlib
+
+import numpy as np
+
+from ._lib import size_t, voidp
+from .dense_mle import DenseMultilinearExtension, _u64p, _words
+from .relaxed_pcs import Error, EvalMismatch, MerkleMismatch, Path, _draw, node_digest
+
+MAX_LOG_LEN = 14
+
+
+class ProximityMismatch(Error):
+    """an opened column does not agree with the encoding of the claimed random combination of the rows"""
+
+    def __init__(self, column, encoded, combined):
+        super().__init__("Column %d: Enc(u_gamma) is %d, the combination of the opened column is %d" % (column, encoded, combined))
+        self.column, self.encoded, self.combined = column, encoded, combined
+
+
+# ---- the root of unity -----------------------------------------------------------------------------------------------
+
+def two_adic_root(p):
+    """(s, g, w_max) of the modulus p, canonical integers"""
+    s = ((p - 1) & -(p - 1)).bit_length() - 1
+    g = 2
+    while pow(g, (p - 1) // 2, p) != p - 1:
+        g += 1
+    return s, g, pow(g, (p - 1) >> s, p)
+
+
+def root_of_unity(field, log_len):
+    """w_L for L = 2^log_len, a Montgomery word"""
+    s, _, w_max = two_adic_root(field.p)
+    if log_len > s:
+        raise ValueError("p = %d has 2-adicity %d: no root of unity of order 2^%d" % (field.p, s, log_len))
+    return field.from_int(pow(w_max, 1 << (s - log_len), field.p))
+
+
+def eq_weights(field, point):
+    """eq(point, i) for every i < 2^len(point), LE: bit j of i goes with point[j]"""
+    w = [field.one]
+    for r in point:
+        w = [field.mul(x, field.sub(field.one, r)) for x in w] + [field.mul(x, r) for x in w]
+    return w
+
+
+def default_log_cols(num_vars, log_blowup):
+    return min((num_vars + 1) // 2, MAX_LOG_LEN - log_blowup)
+
+
+# ---- hashing (host) --------------------------------------------------------------------------------------------------
+
+def column_digest(field, values):
+    """the leaf of a column: SHA-256 over the 8 little-endian bytes of every canonical value, top row first"""
+    return hashlib.sha256(b"".join(field.to_int(v).to_bytes(8, "little") for v in values)).digest()
+
+
+class ColumnPath(Path):
+    """relaxed_pcs.Path over column leaves: the same sibling walk, started from a column's digest"""
+
+    def root_from_column(self, values):
+        h = column_digest(self.field, values)
+        for level, s in enumerate(self.siblings):
+            h = node_digest(h, s) if (self.index >> level) & 1 == 0 else node_digest(s, h)
+        return h
+
+    def verify_column(self, root, values):
+        return self.index < (1 << len(self.siblings)) and self.root_from_column(values) == bytes(root)
+
+
+# ---- the device side -------------------------------------------------------------------------------------------------
+
+def rs_encode_rows(ctx, poly, log_cols, log_blowup):
+    """sc_rs_encode_rows: the codeword matrix of `poly`'s table, row-major, a device table of 2^(n + log_blowup) words"""
+    h = voidp()
+    ctx.check(ctx.lib.sc_rs_encode_rows(ctx.h, poly.h, log_cols, log_blowup, ctypes.byref(h)))
+    return DenseMultilinearExtension(ctx, h)
+
+
+class Prover:
+    """sc_ligero_*: the commitment to a device table (borrowed: kept alive by the prover) and the replies of an opening"""
+
+    def __init__(self, ctx, poly, handle):
+        self.ctx, self.field, self.poly, self.h = ctx, ctx.field, poly, handle
+        r, c, b = size_t(), size_t(), size_t()
+        ctx.check(ctx.lib.sc_ligero_shape(handle, ctypes.byref(r), ctypes.byref(c), ctypes.byref(b)))
+        self.log_rows, self.log_cols, self.log_blowup = r.value, c.value, b.value
+        self.num_vars = self.log_rows + self.log_cols
+
+    @classmethod
+    def commit(cls, ctx, poly, log_cols=None, log_blowup=1):
+        if log_cols is None:
+            log_cols = default_log_cols(poly.num_vars(), log_blowup)
+        h = voidp()
+        ctx.check(ctx.lib.sc_ligero_commit(ctx.h, poly.h, log_cols, log_blowup, ctypes.byref(h)))
+        return cls(ctx, poly, h)
+
+    def root(self):
+        buf = (ctypes.c_uint8 * 32)()
+        self.ctx.check(self.ctx.lib.sc_ligero_root(self.h, buf))
+        return bytes(buf)
+
+    def combine_rows(self, weights):
+        """[sum_i w[i] row_i for w in weights]: up to four vectors of 2^log_rows words in one read of the table"""
+        count = len(weights)
+        w = np.ascontiguousarray(np.array([[int(x) for x in row] for row in weights], dtype=np.uint64).reshape(-1))
+        if count and w.size != count << self.log_rows:
+            raise ValueError("weight vectors must have 2^log_rows = %d words" % (1 << self.log_rows))
+        out = np.zeros(max(1, count << self.log_cols), dtype=np.uint64)
+        self.ctx.check(self.ctx.lib.sc_ligero_combine_rows(self.ctx.h, self.h, _u64p(w) if count else None, count, _u64p(out)))
+        return [[int(x) for x in out[m << self.log_cols:(m + 1) << self.log_cols]] for m in range(count)]
+
+    def combine(self, point, gamma):
+        """(u_gamma, u_z) for the evaluation point and the verifier's gamma; the eq weights of point[c:] are built on the host"""
+        if len(point) != self.num_vars:
+            raise ValueError("the point has %d coordinates, the polynomial %d variables" % (len(point), self.num_vars))
+        u_gamma, u_z = self.combine_rows([list(gamma), eq_weights(self.field, list(point)[self.log_cols:])])
+        return u_gamma, u_z
+
+    def open_columns(self, indices):
+        """[(index, values, ColumnPath)] for every index, in one call; values are the column's 2^log_rows Montgomery words"""
+        idx = _words(indices)
+        count, depth, R = idx.size, self.log_cols + self.log_blowup, 1 << self.log_rows
+        values = np.zeros(max(1, count * R), dtype=np.uint64)
+        paths = (ctypes.c_uint8 * max(1, count * depth * 32))()
+        self.ctx.check(self.ctx.lib.sc_ligero_open_columns(self.ctx.h, self.h, _u64p(idx) if count else None, count, _u64p(values), paths))
+        raw = bytes(paths)
+        out = []
+        for q in range(count):
+            sib = [raw[(q * depth + l) * 32:(q * depth + l + 1) * 32] for l in range(depth)]
+            out.append((int(idx[q]), [int(v) for v in values[q * R:(q + 1) * R]], ColumnPath(int(idx[q]), sib, self.field)))
+        return out
+
+    def close(self):
+        if self.h and self.ctx.h:
+            self.ctx.lib.sc_ligero_destroy(self.ctx.h, self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---- the verifier ----------------------------------------------------------------------------------------------------
+
+class Verifier:
+    """The verifier of one opening.  Pure host code: draw_gamma, receive, draw_columns, verify - in that order."""
+
+    def __init__(self, field, num_vars, log_cols, log_blowup, root, queries):
+        if not 0 <= log_cols <= num_vars or log_blowup not in (1, 2):
+            raise ValueError("log_cols must be in 0..num_vars and log_blowup 1 or 2")
+        self.field, self.num_vars, self.log_cols, self.log_blowup = field, num_vars, log_cols, log_blowup
+        self.log_rows = num_vars - log_cols
+        self.log_len = log_cols + log_blowup
+        self.root, self.queries = bytes(root), int(queries)
+        self.omega = root_of_unity(field, self.log_len)
+        self.gamma = None
+        self.u_gamma = self.u_z = None
+        self.columns = None
+
+    def draw_gamma(self, rng):
+        self.gamma = [_draw(self.field, rng) for _ in range(1 << self.log_rows)]
+        return list(self.gamma)
+
+    def receive(self, u_gamma, u_z):
+        if self.gamma is None:
+            raise Error("receive before draw_gamma")
+        if len(u_gamma) != 1 << self.log_cols or len(u_z) != 1 << self.log_cols:
+            raise Error("the combined rows must have 2^log_cols = %d words" % (1 << self.log_cols))
+        self.u_gamma, self.u_z = [int(x) for x in u_gamma], [int(x) for x in u_z]
+
+    def draw_columns(self, rng):
+        """`queries` column indices in [0, L), with replacement; only after the prover is bound to u_gamma and u_z"""
+        if self.u_gamma is None:
+            raise Error("draw_columns before receive: the columns must be drawn after the prover has sent u_gamma and u_z")
+        L = 1 << self.log_len
+        self.columns = [rng.randrange(L) if hasattr(rng, "randrange") else self.field.to_int(rng.draw()) % L for _ in range(self.queries)]
+        return list(self.columns)
+
+    def _encode_at(self, u, j):
+        """Enc(u)[j]: the polynomial with coefficients u at w_L^j (Horner)"""
+        F = self.field
+        x = F.from_int(pow(F.to_int(self.omega), j, F.p))
+        acc = 0
+        for coeff in reversed(u):
+            acc = F.add(F.mul(acc, x), coeff)
+        return acc
+
+    def verify(self, point, openings):
+        """check every opening; returns the value of the committed polynomial at `point`"""
+        F = self.field
+        if self.columns is None:
+            raise Error("verify before draw_columns")
+        if len(point) != self.num_vars:
+            raise Error("the point has %d coordinates, the polynomial %d variables" % (len(point), self.num_vars))
+        if len(openings) != len(self.columns):
+            raise MerkleMismatch("%d openings for %d drawn columns" % (len(openings), len(self.columns)))
+        eq_rows = eq_weights(F, list(point)[self.log_cols:])
+        for want, (index, values, path) in zip(self.columns, openings):
+            if index != want or path.index != want:
+                raise MerkleMismatch("the opening is of column %d, the drawn column is %d" % (index, want))
+            if len(values) != 1 << self.log_rows or len(path.siblings) != self.log_len:
+                raise MerkleMismatch("an opening of the wrong shape")
+            if not ColumnPath(path.index, path.siblings, F).verify_column(self.root, values):
+                raise MerkleMismatch("the opening of column %d does not lead to the committed root" % index)
+            for u, weights, err in ((self.u_gamma, self.gamma, ProximityMismatch), (self.u_z, eq_rows, EvalMismatch)):
+                combined = 0
+                for wt, v in zip(weights, values):
+                    combined = F.add(combined, F.mul(wt, int(v)))
+                encoded = self._encode_at(u, index)
+                if encoded != combined:
+                    if err is ProximityMismatch:
+                        raise ProximityMismatch(index, encoded, combined)
+                    raise EvalMismatch(combined, encoded)
+        value = 0
+        for a, b in zip(self.u_z, eq_weights(F, list(point)[:self.log_cols])):
+            value = F.add(value, F.mul(a, b))
+        return value

@@ -1,0 +1,211 @@
+"""Wall and device time of the Ligero-style commitment on one MI355X, Goldilocks tables (sc_table_generate):
+
+  encode   sc_rs_encode_rows alone at (n, c, rho) = (20, 10, 1), (24, 12, 1), (26, 13, 1), (26, 12, 2)
+  commit   sc_ligero_commit (encode + column hash + tree), sc_ligero_combine_rows with two weight vectors, 64 openings
+
+Per shape: two warm-up calls, then --reps calls timed on the host around a device synchronise (each call ends in one), and the
+launch log (option time_kernels) for every kernel's device time and bytes.  The encoder has to read the table once and write
+the codewords once, 8 * 2^n + 8 * 2^(n + rho) bytes: that over the time is the rate, reported against the 8 TB/s peak and the
+6.29 TB/s a plain copy reaches on this chip (the yardstick: a copy also reads and writes every word once).  The column hash
+costs ceil((8 R + 9) / 64) SHA-256 compressions per column (the data blocks and the padding), the levels above 2 per node.
+
+CPU row: the same sc_rs_encode_rows shape through tests/ligero_ref.py's numpy transform on one core (arrays of Python
+integers: Goldilocks products do not fit int64), at (20, 10, 1) only.
+
+  python tools/ligero_timing.py [--reps 10] [--limit 600] [--out profiles] [--trace]
+        every step in a child process under its own time limit; writes <out>/ligero_timing.json and <out>/ligero_summary.md;
+        --trace adds a rocprofv3 --kernel-trace --stats run of the encode step, stats to <out>/ligero_kernel_stats.csv
+  python tools/ligero_timing.py --step encode|commit [--reps 10]      one step, one JSON line
+  python tools/ligero_timing.py --skip-cpu ... ; python tools/ligero_timing.py --cpu-only    the GPU part and the CPU row apart
+"""
+import argparse
+import glob
+import json
+import os
+import shutil
+import statistics
+import subprocess
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SHAPES = ((20, 10, 1), (24, 12, 1), (26, 13, 1), (26, 12, 2))
+PEAK_BPS = 8.0e12
+COPY_BPS = 6.29e12          # the measured copy rate of the chip (read + write bytes per second)
+MERKLE_LEAF_CPS = 2.7e10    # merkle_leaf_kernel at n = 28, profiles/pcs_summary.md
+OPENINGS = 64
+
+
+def _timed(ctx, fn, reps):
+    for _ in range(2):   # warm-up (code objects, pool, the twiddle table)
+        fn()
+    ctx.synchronize()
+    walls = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        ctx.synchronize()
+        walls.append(time.perf_counter() - t0)
+    ctx.set_option("time_kernels", 1)
+    ctx.launch_log()
+    fn()
+    ctx.synchronize()
+    log = ctx.launch_log()
+    ctx.set_option("time_kernels", 0)
+    return walls, log
+
+
+def leaf_compressions(r, log_len):
+    return ((8 * (1 << r) + 9 + 63) // 64) << log_len
+
+
+def run_step(step, reps):
+    sys.path.insert(0, ROOT)
+    from __graft_entry__ import load_package
+    pkg = load_package()
+    lp = pkg.ligero_pcs
+    ctx = pkg.Context(pkg.Field(pkg.GOLDILOCKS), device=0)
+    F = ctx.field
+    out = {"step": step, "shapes": {}}
+    for n, c, rho in SHAPES:
+        key = "%d,%d,%d" % (n, c, rho)
+        t = pkg.DenseMultilinearExtension.generate(ctx, 0x11CE0000 + n, n)
+        if step == "encode":
+            walls, log = _timed(ctx, lambda: lp.rs_encode_rows(ctx, t, c, rho), reps)
+            [rec] = [r for r in log if r["kind"] == "rs_encode"]
+            wall = statistics.median(walls)
+            moved = rec["bytes_read"] + rec["bytes_written"]
+            out["shapes"][key] = {"wall_ms": wall * 1e3, "wall_all_ms": [w * 1e3 for w in walls], "device_ms": rec["ms"], "bytes": moved,
+                                  "wall_Bps": moved / wall, "device_Bps": moved / (rec["ms"] * 1e-3)}
+        else:
+            r = n - c
+            walls, log = _timed(ctx, lambda: lp.Prover.commit(ctx, t, c, rho).close(), reps)
+            kernels = {}
+            for rec in log:
+                name = {"rs_encode": "rs_encode_rows_kernel", "ligero": "column_leaf_kernel"}.get(rec["kind"]) or pkg._lib.MERKLE_KERNELS[rec["kf"]]
+                k = kernels.setdefault(name, {"launches": 0, "ms": 0.0})
+                k["launches"] += 1
+                k["ms"] += rec["ms"]
+            prover = lp.Prover.commit(ctx, t, c, rho)
+            import random
+            rng = random.Random(n)
+            weights = [[F.rand(rng) for _ in range(1 << r)] for _ in range(2)]
+            cw, clog = _timed(ctx, lambda: prover.combine_rows(weights), max(2, reps // 3))
+            cols = [rng.randrange(1 << (c + rho)) for _ in range(OPENINGS)]
+            ow, olog = _timed(ctx, lambda: prover.open_columns(cols), max(2, reps // 3))
+            comp = leaf_compressions(r, c + rho)
+            leaf_ms = kernels["column_leaf_kernel"]["ms"]
+            out["shapes"][key] = {"commit_wall_ms": statistics.median(walls) * 1e3, "commit_wall_all_ms": [w * 1e3 for w in walls], "kernels": kernels,
+                                  "leaf_compressions": comp, "leaf_compressions_per_s": comp / (leaf_ms * 1e-3), "root": prover.root().hex(),
+                                  "combine_wall_ms": statistics.median(cw) * 1e3,
+                                  "combine_device_ms": sum(x["ms"] for x in clog), "combine_bytes_read": clog[0]["bytes_read"],
+                                  "open_wall_ms": statistics.median(ow) * 1e3, "open_device_ms": sum(x["ms"] for x in olog)}
+            prover.close()
+        del t
+    return out
+
+
+def cpu_row(n=20, c=10, rho=1):
+    """the same encoding through the numpy reference of the tests, one core"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ligero_ref as ref
+    p = ref.GOLD
+    table = [(0x9E3779B97F4A7C15 * (i + 1)) % p for i in range(1 << n)]
+    t0 = time.perf_counter()
+    ref.encode(table, c, rho, p)
+    secs = time.perf_counter() - t0
+    return {"shape": "%d,%d,%d" % (n, c, rho), "ms": secs * 1e3, "Bps": (8 * (1 << n) + 8 * (1 << (n + rho))) / secs}
+
+
+def summary(res):
+    lines = ["# Ligero-style commitment on one MI355X: row encoding, column hash, openings", "",
+             "Measured by `python tools/ligero_timing.py --reps %d` (wall times: median of %d calls after two warm-up calls, host clock "
+             "around the call and a device synchronise; device times: HIP events of the launch log, option `time_kernels`).  Goldilocks, "
+             "tables from `sc_table_generate`." % (res["reps"], res["reps"]), "",
+             "## sc_rs_encode_rows (`rs_encode_rows_kernel`, one launch)", "",
+             "Bytes are the floor the kernel meets: 8·2^n read + 8·2^(n+rho) written.  The yardstick is the chip's measured copy rate, "
+             "6.29 TB/s: a copy also reads and writes each word once.", "",
+             "| (n, c, rho) | wall ms | device ms | bytes | wall TB/s | device TB/s | device / 8 TB/s peak | device / 6.29 TB/s copy |", "|---|---|---|---|---|---|---|---|"]
+    for key, r in res["steps"]["encode"]["shapes"].items():
+        lines.append("| (%s) | %.3f | %.3f | %d | %.2f | %.2f | %.0f %% | %.0f %% |" % (key.replace(",", ", "), r["wall_ms"], r["device_ms"], r["bytes"],
+                                                                                  r["wall_Bps"] / 1e12, r["device_Bps"] / 1e12,
+                                                                                  100 * r["device_Bps"] / PEAK_BPS, 100 * r["device_Bps"] / COPY_BPS))
+    cpu = res.get("cpu") or {"shape": "20,10,1", "ms": float("nan"), "Bps": float("nan")}
+    lines += ["", "**CPU row** (one core, the numpy reference of `tests/ligero_ref.py`, arrays of Python integers): shape (%s) in %.0f ms = "
+              "%.3g B/s." % (cpu["shape"].replace(",", ", "), cpu["ms"], cpu["Bps"]), "",
+              "## sc_ligero_commit, sc_ligero_combine_rows (M = 2), %d openings" % OPENINGS, "",
+              "| (n, c, rho) | commit wall ms | encode ms | column hash ms | tree ms | leaf compressions | compressions/s | vs merkle_leaf_kernel 2.7e10/s | "
+              "combine wall ms | combine device ms | open wall ms | open device ms |", "|---|---|---|---|---|---|---|---|---|---|---|---|"]
+    for key, r in res["steps"]["commit"]["shapes"].items():
+        k = r["kernels"]
+        tree = sum(v["ms"] for name, v in k.items() if name.startswith("merkle"))
+        lines.append("| (%s) | %.3f | %.3f | %.3f | %.3f | %d | %.3g | %.2f | %.3f | %.3f | %.3f | %.3f |" % (
+            key.replace(",", ", "), r["commit_wall_ms"], k["rs_encode_rows_kernel"]["ms"], k["column_leaf_kernel"]["ms"], tree, r["leaf_compressions"],
+            r["leaf_compressions_per_s"], r["leaf_compressions_per_s"] / MERKLE_LEAF_CPS, r["combine_wall_ms"], r["combine_device_ms"],
+            r["open_wall_ms"], r["open_device_ms"]))
+    lines += ["", "The column hash runs one lane per column: at L = 2^14 that is 2^14 lanes, one wave on each of the 256 CUs, against the "
+              "2^24 lanes `merkle_leaf_kernel` spreads over the chip at n = 28 - the same compression function on the same chip, so the "
+              "ratio column is what that occupancy costs.  The combine and open wall times include the host's copies of the weights, "
+              "the values and the paths.", ""]
+    if res.get("notes"):
+        lines += ["## What binds the encoder", ""] + res["notes"] + [""]
+    return "\n".join(lines)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--step", choices=("encode", "commit"))
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--limit", type=int, default=600, help="seconds each child step may take")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles"), help="directory of ligero_timing.json / ligero_summary.md")
+    ap.add_argument("--trace", action="store_true", help="also one rocprofv3 --kernel-trace --stats run of the encode step")
+    ap.add_argument("--skip-cpu", action="store_true", help="leave the CPU row out (add it later with --cpu-only)")
+    ap.add_argument("--cpu-only", action="store_true", help="measure the CPU row alone (no GPU needed), add it to ligero_timing.json, rewrite the summary")
+    ap.add_argument("--summary-only", action="store_true", help="rewrite ligero_summary.md from ligero_timing.json")
+    args = ap.parse_args()
+    os.makedirs(args.out, exist_ok=True)
+    path = os.path.join(args.out, "ligero_timing.json")
+    if args.summary_only or args.cpu_only:
+        with open(path) as fh:
+            res = json.load(fh)
+        if args.cpu_only:
+            res["cpu"] = cpu_row()
+            with open(path, "w") as fh:
+                json.dump(res, fh, indent=1)
+        with open(os.path.join(args.out, "ligero_summary.md"), "w") as fh:
+            fh.write(summary(res))
+        return
+    if args.step:
+        print(json.dumps(run_step(args.step, args.reps)))
+        return
+    res = {"reps": args.reps, "steps": {}}
+    for step in ("encode", "commit"):
+        cmd = [sys.executable, os.path.abspath(__file__), "--step", step, "--reps", str(args.reps)]
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=args.limit)
+        if p.returncode != 0:
+            print(json.dumps({"step": step, "error": "exit status %d" % p.returncode, "stderr": p.stderr[-2000:]}))
+            sys.exit(1)                                  # nothing more on the GPU after a failed step
+        res["steps"][step] = json.loads(p.stdout.strip().splitlines()[-1])
+    if args.trace:
+        d = tempfile.mkdtemp()
+        cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", d, "-o", "encode", "--output-format", "csv", "--",
+               sys.executable, os.path.abspath(__file__), "--step", "encode", "--reps", "1"]
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=args.limit)
+        if p.returncode != 0:
+            print(json.dumps({"trace": "encode", "error": "exit status %d" % p.returncode, "stderr": p.stderr[-2000:]}))
+            sys.exit(1)
+        for f in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
+            shutil.copy(f, os.path.join(args.out, "ligero_kernel_stats.csv"))
+        shutil.rmtree(d, ignore_errors=True)
+    if not args.skip_cpu:
+        res["cpu"] = cpu_row()
+    with open(path, "w") as fh:
+        json.dump(res, fh, indent=1)
+    with open(os.path.join(args.out, "ligero_summary.md"), "w") as fh:
+        fh.write(summary(res))
+    print(json.dumps({"encode_device_TBps": {k: round(v["device_Bps"] / 1e12, 3) for k, v in res["steps"]["encode"]["shapes"].items()}, "cpu": res.get("cpu")}))
+
+
+if __name__ == "__main__":
+    main()
