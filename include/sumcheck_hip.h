@@ -233,6 +233,9 @@ int sc_ctx_kernel_time(sc_ctx* ctx, double out[2], int reset);
 #define SC_KIND_LIGERO 20      /* sc_ligero_*: kf = 0 column_leaf_kernel (ks = log2 rows; reads E, writes L digests), 1 row_combine_kernel (ks = the
                                 * number of weight vectors; ks = 0: the launch that adds the row ranges' partial sums), 2 column_open_kernel
                                 * (ks = openings of the launch); log_in = n.  The tree levels above the leaves are SC_KIND_MERKLE records */
+#define SC_KIND_XC_ENCODE 21   /* xc_encode_rows_kernel: the row encoder of sc_xc_encode_rows / sc_ligero_commit_code(SC_CODE_EXPANDER), one launch;
+                                * kf = log_cols, ks = recursion levels, log_in = n; it reads the table once (8 * 2^n bytes) and writes the
+                                * codewords once (8 * 2^(n + 1)) */
 typedef struct sc_launch_record {
   int32_t kind;           /* SC_KIND_* */
   int32_t kf, ks;         /* variables folded / rounds served (meaning per kind above) */
@@ -554,6 +557,23 @@ int sc_ligero_combine_rows(sc_ctx* ctx, const sc_ligero* lg, const uint64_t* wei
  * sibling digests of leaf cols[q] bottom up (verified as sc_merkle_open's, from the column's leaf digest).  Indices may repeat. */
 int sc_ligero_open_columns(sc_ctx* ctx, const sc_ligero* lg, const uint64_t* cols, size_t count, uint64_t* values, uint8_t* paths);
 int sc_ligero_destroy(sc_ctx* ctx, sc_ligero* lg);
+
+/* ---- the same commitment over a linear-time expander code, for fields without two-adicity ------------------------------
+ * (Thaler's book, section 10.5: Ligero with a linear-time code, as in Brakedown; kernels/expander.hpp states the contract,
+ * "expander code 1".)  The code is systematic at rate 1/2: a row of 2^log_cols words encodes to itself followed by as many
+ * check words, L = 2^(log_cols + 1), log_blowup = 1.  It needs only additions and multiplications by constants, so any prime
+ * p > 63 is served, 2^64 - 59 included.  Its relative distance is NOT proved: no security level is claimed.
+ * SC_ERR_ARG: a null pointer, a table that is not 2^n long, log_cols > n, an unknown code, log_blowup != 1 with
+ * SC_CODE_EXPANDER.  SC_ERR_UNSUPPORTED: log_cols > 13 (one codeword has to fit the LDS of a CU), n + 1 > 29, p <= 63 (the
+ * message names p), a sharded context or a multi-device handle. */
+#define SC_CODE_RS 0
+#define SC_CODE_EXPANDER 1
+/* the codeword matrix alone: *out has 2^(n + 1) entries, E[i][j] at i L + j, Montgomery like every table */
+int sc_xc_encode_rows(sc_ctx* ctx, const sc_table* t, size_t log_cols, sc_table** out);
+/* sc_ligero_commit with the row code chosen: SC_CODE_RS is sc_ligero_commit itself.  The commitment is an ordinary sc_ligero:
+ * sc_ligero_root / shape / combine_rows / open_columns / destroy serve it unchanged. */
+int sc_ligero_commit_code(sc_ctx* ctx, const sc_table* t, size_t log_cols, size_t log_blowup, int code, sc_ligero** out);
+int sc_ligero_code(const sc_ligero* lg, int* code);
 
 /* ---- gkr_protocol::circuit::Circuit on the device, and the whole GKR prover over it ----------------------------------
  * A circuit lives on ONE context of one device and one rank: sharded contexts (world > 1) and multi-device handles get

@@ -493,4 +493,17 @@ extern "C" {
         paths: *mut u8,
     ) -> c_int;
     pub fn sc_ligero_destroy(ctx: *mut sc_ctx, lg: *mut sc_ligero) -> c_int;
+
+    /// the rows of `t` (2^log_cols words each) under the linear-time expander code: every row followed by as many check words
+    pub fn sc_xc_encode_rows(ctx: *mut sc_ctx, t: *const sc_table, log_cols: usize, out: *mut *mut sc_table) -> c_int;
+    /// sc_ligero_commit with the row code chosen (SC_CODE_RS or SC_CODE_EXPANDER; the latter needs log_blowup = 1)
+    pub fn sc_ligero_commit_code(
+        ctx: *mut sc_ctx,
+        t: *const sc_table,
+        log_cols: usize,
+        log_blowup: usize,
+        code: c_int,
+        out: *mut *mut sc_ligero,
+    ) -> c_int;
+    pub fn sc_ligero_code(lg: *const sc_ligero, code: *mut c_int) -> c_int;
 }

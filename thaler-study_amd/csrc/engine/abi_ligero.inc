@@ -7,6 +7,7 @@ struct sc_ligero {
   const sc_ctx* ctx = nullptr;
   const sc_table* t = nullptr;   // borrowed: must outlive the commitment
   int r = 0, c = 0, rho = 0;
+  int code = SC_CODE_RS;         // the row code of E: Reed-Solomon, or the expander code of engine/abi_expander.inc
   TableBuf E;
   PoolBuf d_levels;
   uint32_t root[8] = {};
@@ -164,22 +165,21 @@ extern "C" int sc_rs_encode_rows(sc_ctx* ctx, const sc_table* t, size_t log_cols
   return SC_OK;
 }
 
-extern "C" int sc_ligero_commit(sc_ctx* ctx, const sc_table* t, size_t log_cols, size_t log_blowup, sc_ligero** out) {
-  if (!ctx || !out) return SC_ERR_ARG;
-  *out = nullptr;
-  int n = 0;
-  SC_TRY(ligero_shape(ctx, t, log_cols, log_blowup, "sc_ligero_commit", &n));
+// the commitment to a table whose shape has been checked: E from `encode(E)`, then the tree over its columns
+template <class Encode>
+static int ligero_commit_with(sc_ctx* ctx, const sc_table* t, int n, int c, int rho, int code, Encode&& encode, sc_ligero** out) {
   SC_TRY(set_device(ctx));
   sc_ligero* lg = new (std::nothrow) sc_ligero;
   if (!lg) return fail(ctx, SC_ERR_OOM, "host allocation failed");
   lg->ctx = ctx;
   lg->t = t;
-  lg->c = (int)log_cols;
-  lg->r = n - lg->c;
-  lg->rho = (int)log_blowup;
-  int rc = lg->E.alloc(ctx, (size_t)1 << (n + lg->rho));
-  if (rc == SC_OK) rc = lg->d_levels.alloc(ctx, 4 * (((size_t)2 << (lg->c + lg->rho)) - 1));
-  if (rc == SC_OK) rc = rs_encode_impl(ctx, t->d, n, lg->c, lg->rho, lg->E->d);
+  lg->c = c;
+  lg->r = n - c;
+  lg->rho = rho;
+  lg->code = code;
+  int rc = lg->E.alloc(ctx, (size_t)1 << (n + rho));
+  if (rc == SC_OK) rc = lg->d_levels.alloc(ctx, 4 * (((size_t)2 << (c + rho)) - 1));
+  if (rc == SC_OK) rc = encode(lg->E->d);
   if (rc == SC_OK) rc = ligero_tree_build(ctx, lg);
   if (rc != SC_OK) {
     delete lg;
@@ -187,6 +187,15 @@ extern "C" int sc_ligero_commit(sc_ctx* ctx, const sc_table* t, size_t log_cols,
   }
   *out = lg;
   return SC_OK;
+}
+
+extern "C" int sc_ligero_commit(sc_ctx* ctx, const sc_table* t, size_t log_cols, size_t log_blowup, sc_ligero** out) {
+  if (!ctx || !out) return SC_ERR_ARG;
+  *out = nullptr;
+  int n = 0;
+  SC_TRY(ligero_shape(ctx, t, log_cols, log_blowup, "sc_ligero_commit", &n));
+  return ligero_commit_with(ctx, t, n, (int)log_cols, (int)log_blowup, SC_CODE_RS,
+                            [&](u64* E) { return rs_encode_impl(ctx, t->d, n, (int)log_cols, (int)log_blowup, E); }, out);
 }
 
 extern "C" int sc_ligero_root(const sc_ligero* lg, uint8_t root[32]) {

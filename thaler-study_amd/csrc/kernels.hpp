@@ -259,4 +259,5 @@ __device__ __forceinline__ void transpose_to_pieces(ull2* __restrict__ lds, ull2
 #include "kernels/batch.hpp"
 #include "kernels/pcs.hpp"
 #include "kernels/ligero.hpp"
+#include "kernels/expander.hpp"
 #include "kernels/peer.hpp"

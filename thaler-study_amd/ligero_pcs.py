@@ -20,17 +20,30 @@ Contract (kernels/ligero.hpp):
   limits         c + log_blowup <= 14 and <= s, n + log_blowup <= 29, log_blowup in {1, 2}, one device and one rank
 
 Field elements are Montgomery words, as everywhere in this package; leaves hash canonical integers.  `queries` is the caller's
-parameter: DESIGN.md gives the book's soundness expression for it; no security level is claimed here."""
+parameter: DESIGN.md gives the book's soundness expression for it; no security level is claimed here.
+
+code="expander" (sc_xc_encode_rows, sc_ligero_commit_code) replaces Reed-Solomon by the linear-time
+code of expander_code.py - systematic, rate 1/2 (log_blowup = 1), additions and multiplications by constants only - for fields
+without two-adicity such as 2^64 - 59: any p > 63, log_cols <= 13.  Everything above the encoder is the same; Enc(u)[j] is then
+entry j of expander_code.encode(u).  The distance of that code is not proved."""
 import ctypes
 import hashlib
 
 import numpy as np
 
+from . import expander_code
 from ._lib import size_t, voidp
 from .dense_mle import DenseMultilinearExtension, _u64p, _words
 from .relaxed_pcs import Error, EvalMismatch, MerkleMismatch, Path, _draw, node_digest
 
 MAX_LOG_LEN = 14
+CODES = {"rs": 0, "expander": 1}       # SC_CODE_RS, SC_CODE_EXPANDER
+
+
+def _code_id(code):
+    if code not in CODES:
+        raise ValueError("code must be one of %s, not %r" % (sorted(CODES), code))
+    return CODES[code]
 
 
 class ProximityMismatch(Error):
@@ -68,7 +81,9 @@ def eq_weights(field, point):
     return w
 
 
-def default_log_cols(num_vars, log_blowup):
+def default_log_cols(num_vars, log_blowup, code="rs"):
+    if code == "expander":
+        return min((num_vars + 1) // 2, expander_code.MAX_LOG_COLS)
     return min((num_vars + 1) // 2, MAX_LOG_LEN - log_blowup)
 
 
@@ -101,6 +116,13 @@ def rs_encode_rows(ctx, poly, log_cols, log_blowup):
     return DenseMultilinearExtension(ctx, h)
 
 
+def xc_encode_rows(ctx, poly, log_cols):
+    """sc_xc_encode_rows: the codeword matrix of `poly`'s table under the expander code, row-major, a device table of 2^(n + 1) words"""
+    h = voidp()
+    ctx.check(ctx.lib.sc_xc_encode_rows(ctx.h, poly.h, log_cols, ctypes.byref(h)))
+    return DenseMultilinearExtension(ctx, h)
+
+
 class Prover:
     """sc_ligero_*: the commitment to a device table (borrowed: kept alive by the prover) and the replies of an opening"""
 
@@ -110,13 +132,20 @@ class Prover:
         ctx.check(ctx.lib.sc_ligero_shape(handle, ctypes.byref(r), ctypes.byref(c), ctypes.byref(b)))
         self.log_rows, self.log_cols, self.log_blowup = r.value, c.value, b.value
         self.num_vars = self.log_rows + self.log_cols
+        code = ctypes.c_int()
+        ctx.check(ctx.lib.sc_ligero_code(handle, ctypes.byref(code)))
+        self.code = {v: k for k, v in CODES.items()}[code.value]
 
     @classmethod
-    def commit(cls, ctx, poly, log_cols=None, log_blowup=1):
+    def commit(cls, ctx, poly, log_cols=None, log_blowup=1, code="rs"):
+        code_id = _code_id(code)
         if log_cols is None:
-            log_cols = default_log_cols(poly.num_vars(), log_blowup)
+            log_cols = default_log_cols(poly.num_vars(), log_blowup, code)
         h = voidp()
-        ctx.check(ctx.lib.sc_ligero_commit(ctx.h, poly.h, log_cols, log_blowup, ctypes.byref(h)))
+        if code == "rs":
+            ctx.check(ctx.lib.sc_ligero_commit(ctx.h, poly.h, log_cols, log_blowup, ctypes.byref(h)))
+        else:
+            ctx.check(ctx.lib.sc_ligero_commit_code(ctx.h, poly.h, log_cols, log_blowup, code_id, ctypes.byref(h)))
         return cls(ctx, poly, h)
 
     def root(self):
@@ -172,14 +201,19 @@ class Prover:
 class Verifier:
     """The verifier of one opening.  Pure host code: draw_gamma, receive, draw_columns, verify - in that order."""
 
-    def __init__(self, field, num_vars, log_cols, log_blowup, root, queries):
+    def __init__(self, field, num_vars, log_cols, log_blowup, root, queries, code="rs"):
+        _code_id(code)
         if not 0 <= log_cols <= num_vars or log_blowup not in (1, 2):
             raise ValueError("log_cols must be in 0..num_vars and log_blowup 1 or 2")
+        if code == "expander" and log_blowup != 1:
+            raise ValueError("the expander code has rate 1/2: log_blowup must be 1")
+        self.code = code
         self.field, self.num_vars, self.log_cols, self.log_blowup = field, num_vars, log_cols, log_blowup
         self.log_rows = num_vars - log_cols
         self.log_len = log_cols + log_blowup
         self.root, self.queries = bytes(root), int(queries)
-        self.omega = root_of_unity(field, self.log_len)
+        self.omega = root_of_unity(field, self.log_len) if code == "rs" else None
+        self.enc_gamma = self.enc_z = None      # the expander code: the two whole codewords, encoded once in receive
         self.gamma = None
         self.u_gamma = self.u_z = None
         self.columns = None
@@ -194,6 +228,8 @@ class Verifier:
         if len(u_gamma) != 1 << self.log_cols or len(u_z) != 1 << self.log_cols:
             raise Error("the combined rows must have 2^log_cols = %d words" % (1 << self.log_cols))
         self.u_gamma, self.u_z = [int(x) for x in u_gamma], [int(x) for x in u_z]
+        if self.code == "expander":
+            self.enc_gamma, self.enc_z = expander_code.encode(self.field, self.u_gamma), expander_code.encode(self.field, self.u_z)
 
     def draw_columns(self, rng):
         """`queries` column indices in [0, L), with replacement; only after the prover is bound to u_gamma and u_z"""
@@ -204,8 +240,11 @@ class Verifier:
         return list(self.columns)
 
     def _encode_at(self, u, j):
-        """Enc(u)[j]: the polynomial with coefficients u at w_L^j (Horner)"""
+        """Enc(u)[j]: the polynomial with coefficients u at w_L^j (Horner); the expander code: entry j of the whole codeword
+        (verify reads the two codewords receive stored instead)"""
         F = self.field
+        if self.code == "expander":
+            return expander_code.encode(F, u)[j]
         x = F.from_int(pow(F.to_int(self.omega), j, F.p))
         acc = 0
         for coeff in reversed(u):
@@ -229,11 +268,12 @@ class Verifier:
                 raise MerkleMismatch("an opening of the wrong shape")
             if not ColumnPath(path.index, path.siblings, F).verify_column(self.root, values):
                 raise MerkleMismatch("the opening of column %d does not lead to the committed root" % index)
-            for u, weights, err in ((self.u_gamma, self.gamma, ProximityMismatch), (self.u_z, eq_rows, EvalMismatch)):
+            for u, enc, weights, err in ((self.u_gamma, self.enc_gamma, self.gamma, ProximityMismatch),
+                                         (self.u_z, self.enc_z, eq_rows, EvalMismatch)):
                 combined = 0
                 for wt, v in zip(weights, values):
                     combined = F.add(combined, F.mul(wt, int(v)))
-                encoded = self._encode_at(u, index)
+                encoded = enc[index] if enc is not None else self._encode_at(u, index)
                 if encoded != combined:
                     if err is ProximityMismatch:
                         raise ProximityMismatch(index, encoded, combined)

@@ -17,6 +17,12 @@ integers: Goldilocks products do not fit int64), at (20, 10, 1) only.
         --trace adds a rocprofv3 --kernel-trace --stats run of the encode step, stats to <out>/ligero_kernel_stats.csv
   python tools/ligero_timing.py --step encode|commit [--reps 10]      one step, one JSON line
   python tools/ligero_timing.py --skip-cpu ... ; python tools/ligero_timing.py --cpu-only    the GPU part and the CPU row apart
+  python tools/ligero_timing.py --code expander [--reps 10]
+        the linear-time expander code (sc_xc_encode_rows) at (n, c) = (20, 10), (24, 12), (26, 13):
+        in ONE child process per shape list, sc_rs_encode_rows (rho = 1) and sc_xc_encode_rows on Goldilocks, sc_xc_encode_rows on
+        2^64 - 59 (which Reed-Solomon cannot serve), and the expander commit on both fields; writes <out>/expander_timing.json and
+        <out>/expander_summary.md: the encode time, its ratio to rs_encode_rows_kernel at the same shape in the same run, and its
+        rate on 24 * 2^n bytes against the 6.29 TB/s copy rate.  The default --code rs is everything above, unchanged.
 """
 import argparse
 import glob
@@ -35,6 +41,8 @@ PEAK_BPS = 8.0e12
 COPY_BPS = 6.29e12          # the measured copy rate of the chip (read + write bytes per second)
 MERKLE_LEAF_CPS = 2.7e10    # merkle_leaf_kernel at n = 28, profiles/pcs_summary.md
 OPENINGS = 64
+XC_SHAPES = ((20, 10), (24, 12), (26, 13))
+P59 = 2**64 - 59
 
 
 def _timed(ctx, fn, reps):
@@ -106,6 +114,63 @@ def run_step(step, reps):
     return out
 
 
+def run_expander(reps):
+    """--code expander: per shape the two encoders on Goldilocks, the expander encoder on 2^64 - 59, and the expander commit"""
+    sys.path.insert(0, ROOT)
+    from __graft_entry__ import load_package
+    pkg = load_package()
+    lp = pkg.ligero_pcs
+    out = {"step": "expander", "shapes": {}}
+    ctxs = {"gold": pkg.Context(pkg.Field(pkg.GOLDILOCKS), device=0), "p59": pkg.Context(pkg.Field(P59), device=0)}
+    for n, c in XC_SHAPES:
+        row = {}
+        for name, ctx in ctxs.items():
+            t = pkg.DenseMultilinearExtension.generate(ctx, 0x11CE0000 + n, n)
+            runs = [("xc", "xc_encode", lambda: lp.xc_encode_rows(ctx, t, c))]
+            if name == "gold":
+                runs.insert(0, ("rs", "rs_encode", lambda: lp.rs_encode_rows(ctx, t, c, 1)))
+            for tag, kind, fn in runs:
+                walls, log = _timed(ctx, fn, reps)
+                [rec] = [r for r in log if r["kind"] == kind]
+                row["%s_%s" % (tag, name)] = {"wall_ms": statistics.median(walls) * 1e3, "device_ms": rec["ms"],
+                                              "bytes": rec["bytes_read"] + rec["bytes_written"]}
+            walls, log = _timed(ctx, lambda: lp.Prover.commit(ctx, t, c, 1, code="expander").close(), max(2, reps // 3))
+            row["commit_%s" % name] = {"wall_ms": statistics.median(walls) * 1e3,
+                                       "encode_ms": sum(r["ms"] for r in log if r["kind"] == "xc_encode"),
+                                       "leaf_ms": sum(r["ms"] for r in log if r["kind"] == "ligero"),
+                                       "tree_ms": sum(r["ms"] for r in log if r["kind"] == "merkle")}
+            del t
+        out["shapes"]["%d,%d" % (n, c)] = row
+    return out
+
+
+def expander_summary(res):
+    lines = ["# Expander code 1 on one MI355X: sc_xc_encode_rows beside sc_rs_encode_rows", "",
+             "Measured by `python tools/ligero_timing.py --code expander --reps %d`: every row below, the Reed-Solomon column included, "
+             "comes from ONE process, so the xc / rs ratio compares two kernels of the same run (`profiles/ligero_summary.md`, the "
+             "default `--code rs` run, is a separate process and its `rs_encode_rows_kernel` times differ by a few per cent).  Device "
+             "times: HIP events of the launch log, option `time_kernels`; wall times: median of %d calls after two warm-up calls.  Tables from "
+             "`sc_table_generate`.  Both encoders read 8·2^n bytes and write 8·2^(n+1): 24·2^n in all, the same floor; the yardstick "
+             "is the chip's measured copy rate, 6.29 TB/s." % (res["reps"], res["reps"]), "",
+             "| (n, c) | field | xc_encode_rows_kernel device ms | wall ms | rs_encode_rows_kernel device ms (Goldilocks, rho = 1) | xc / rs | "
+             "TB/s on 24·2^n bytes | of the 6.29 TB/s copy rate |", "|---|---|---|---|---|---|---|---|"]
+    for key, row in res["steps"]["expander"]["shapes"].items():
+        rs = row["rs_gold"]
+        for name, label in (("gold", "Goldilocks"), ("p59", "2^64 - 59")):
+            x = row["xc_" + name]
+            bps = x["bytes"] / (x["device_ms"] * 1e-3)
+            lines.append("| (%s) | %s | %.3f | %.3f | %.3f | %.1f | %.3f | %.1f %% |" % (key.replace(",", ", "), label, x["device_ms"], x["wall_ms"],
+                                                                                   rs["device_ms"], x["device_ms"] / rs["device_ms"], bps / 1e12,
+                                                                                   100 * bps / COPY_BPS))
+    lines += ["", "## sc_ligero_commit_code(SC_CODE_EXPANDER): encode + column hash + tree", "",
+              "| (n, c) | field | commit wall ms | encode ms | column hash ms | tree ms |", "|---|---|---|---|---|---|"]
+    for key, row in res["steps"]["expander"]["shapes"].items():
+        for name, label in (("gold", "Goldilocks"), ("p59", "2^64 - 59")):
+            k = row["commit_" + name]
+            lines.append("| (%s) | %s | %.3f | %.3f | %.3f | %.3f |" % (key.replace(",", ", "), label, k["wall_ms"], k["encode_ms"], k["leaf_ms"], k["tree_ms"]))
+    return "\n".join(lines) + "\n"
+
+
 def cpu_row(n=20, c=10, rho=1):
     """the same encoding through the numpy reference of the tests, one core"""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -155,7 +220,8 @@ def summary(res):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--step", choices=("encode", "commit"))
+    ap.add_argument("--step", choices=("encode", "commit", "expander"))
+    ap.add_argument("--code", choices=("rs", "expander"), default="rs", help="expander: the expander code beside Reed-Solomon (expander_summary.md)")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--limit", type=int, default=600, help="seconds each child step may take")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles"), help="directory of ligero_timing.json / ligero_summary.md")
@@ -177,7 +243,20 @@ def main():
             fh.write(summary(res))
         return
     if args.step:
-        print(json.dumps(run_step(args.step, args.reps)))
+        print(json.dumps(run_expander(args.reps) if args.step == "expander" else run_step(args.step, args.reps)))
+        return
+    if args.code == "expander":
+        cmd = [sys.executable, os.path.abspath(__file__), "--step", "expander", "--reps", str(args.reps)]
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=args.limit)
+        if p.returncode != 0:
+            print(json.dumps({"step": "expander", "error": "exit status %d" % p.returncode, "stderr": p.stderr[-2000:]}))
+            sys.exit(1)
+        res = {"reps": args.reps, "steps": {"expander": json.loads(p.stdout.strip().splitlines()[-1])}}
+        with open(os.path.join(args.out, "expander_timing.json"), "w") as fh:
+            json.dump(res, fh, indent=1)
+        with open(os.path.join(args.out, "expander_summary.md"), "w") as fh:
+            fh.write(expander_summary(res))
+        print(json.dumps({k: {t: round(v["device_ms"], 3) for t, v in row.items() if "device_ms" in v} for k, row in res["steps"]["expander"]["shapes"].items()}))
         return
     res = {"reps": args.reps, "steps": {}}
     for step in ("encode", "commit"):
