@@ -1,8 +1,9 @@
-// Host build of the SHA-256 compression in thaler-study_amd/csrc/kernels/pcs.hpp (the function the Merkle kernels and the
-// engine's openings share) so that its digests are checked against hashlib on CPU, and timed there as a one-core baseline.
+// Host build of the SHA-256 compression in thaler-study_amd/csrc/kernels/sha256.hpp (the function the Merkle kernels and the
+// engine's openings share) so that its digests are checked against hashlib on CPU, and timed there as a one-core baseline; and
+// of the host half of an opening and the layout of the stored levels (kernels/merkle.hpp).
 #include <chrono>
 
-#include "../../thaler-study_amd/csrc/kernels/pcs.hpp"
+#include "../../thaler-study_amd/csrc/kernels/merkle.hpp"
 using namespace sc;
 extern "C" {
 // out[8 i ..] = words of the leaf digest of canonical[i]
@@ -30,5 +31,13 @@ void ph_root(const u64* canonical, int n, u32* root, double* seconds) {
   for (int w = 0; w < 8; ++w) root[w] = lev[w];
   delete[] lev;
   *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+}
+// node offset of level l among the stored levels above `bottom_nodes` nodes
+u64 ph_level_offset(u64 bottom_nodes, int l) { return merkle_level_offset(bottom_nodes, l); }
+// one opening as sc_merkle_open finishes it on the host: vals = the 2^lb canonical values of leaf i's bottom subtree, sib[n - lb][8]
+// = its siblings at the stored levels; *leaf and path[32 n]
+void ph_path(int n, int lb, u64 i, const u64* vals, const u32* sib, u64* leaf, uint8_t* path) {
+  merkle_path_host(lb, i, vals, leaf, path);
+  put_paths(path, n, lb, sib, 1, n - lb);
 }
 }

@@ -332,6 +332,33 @@ def test_protocol_it_works(pkg, p, m):
         assert outcomes == {"strict accepts", "strict rejects"}, outcomes
 
 
+def test_merkle_launch_records_at_n14(pkg):
+    """2^14 leaves are the smallest tree that runs all three build phases: the leaf kernel up to level 4 (1024 nodes), one level
+    launch, the top kernel on 512 nodes.  The records are pinned field by field."""
+    F = pkg.Field(GOLD)
+    ctx = pkg.Context(F)
+    n, seed = 14, 1414
+    t = pkg.DenseMultilinearExtension.generate(ctx, seed, n)
+    canon = [_splitmix64(seed + i) % GOLD for i in range(1 << n)]
+    levels = levels_hl(canon)
+    ctx.set_option("time_kernels", 1)
+    ctx.launch_log()
+    tree = pkg.relaxed_pcs.merkle_commit(ctx, t)
+
+    def merkle_records():
+        return [(r["kf"], r["ks"], r["log_in"], r["bytes_read"], r["bytes_written"]) for r in ctx.launch_log() if r["kind"] == "merkle"]
+
+    assert merkle_records() == [(0, 4, 14, 8 << 14, 32 << 10), (1, 5, 14, 32 << 10, 32 << 9), (2, 6, 14, 32 * 1022, 32 * 511)]
+    assert tree.root() == levels[-1][0]
+    idx = [0, 9001, (1 << n) - 1]
+    opened = tree.open(idx)
+    m = 3 * (8 * 16 + 32 * 10)
+    assert merkle_records() == [(3, 4, 14, m, m)]
+    for i, (path, leaf) in zip(idx, opened):
+        assert leaf == canon[i] and path.siblings == path_hl(levels, i)
+        assert path.verify_canonical(levels[-1][0], leaf)
+
+
 # ---- 6. contexts that are not served, and the launch log -------------------------------------------------------------
 
 def test_sharded_and_multi_device_are_refused(pkg):

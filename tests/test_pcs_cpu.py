@@ -1,5 +1,5 @@
-"""CPU checks of the Relaxed PCS (relaxed-pcs/src/lib.rs): the shared SHA-256 compression of kernels/pcs.hpp compiled with g++
-against hashlib, the reference's grid order, the host verifier against paths built here with hashlib, and the built ISA of the
+"""CPU checks of the Relaxed PCS (relaxed-pcs/src/lib.rs): the shared SHA-256 compression of kernels/sha256.hpp and the host half of
+an opening (kernels/merkle.hpp) compiled with g++ against hashlib, the reference's grid order, the host verifier against paths built here with hashlib, and the built ISA of the
 hash kernels.  No GPU needed."""
 import ctypes
 import hashlib
@@ -30,6 +30,9 @@ def ph(tmp_path_factory):
     lib.ph_leaf.argtypes = [u64p, u32p, ctypes.c_size_t]
     lib.ph_node.argtypes = [u32p, u32p, u32p]
     lib.ph_root.argtypes = [u64p, ctypes.c_int, u32p, ctypes.POINTER(ctypes.c_double)]
+    lib.ph_level_offset.argtypes = [ctypes.c_uint64, ctypes.c_int]
+    lib.ph_level_offset.restype = ctypes.c_uint64
+    lib.ph_path.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint64, u64p, u32p, u64p, ctypes.POINTER(ctypes.c_uint8)]
     return lib
 
 
@@ -56,13 +59,19 @@ def root_hl(values):
     return lev[0]
 
 
-def path_hl(values, i):
-    lev, sib = [leaf_hl(v) for v in values], []
-    while len(lev) > 1:
-        sib.append(lev[i ^ 1])
-        lev = [node_hl(lev[2 * k], lev[2 * k + 1]) for k in range(len(lev) // 2)]
-        i >>= 1
-    return sib
+def levels_hl(values):
+    """every level of the tree, leaves first"""
+    levels = [[leaf_hl(v) for v in values]]
+    while len(levels[-1]) > 1:
+        lev = levels[-1]
+        levels.append([node_hl(lev[2 * k], lev[2 * k + 1]) for k in range(len(lev) // 2)])
+    return levels
+
+
+def path_hl(values, i, levels=None):
+    """the siblings of leaf i, bottom up (`levels`: levels_hl(values), where a caller opens many leaves of one tree)"""
+    levels = levels or levels_hl(values)
+    return [lev[(i >> l) ^ 1] for l, lev in enumerate(levels[:-1])]
 
 
 def edge_values():
@@ -101,6 +110,39 @@ def test_host_tree_root_matches_hashlib(ph, n):
     secs = ctypes.c_double()
     ph.ph_root(vals.ctypes.data_as(u64p), n, root.ctypes.data_as(u32p), ctypes.byref(secs))
     assert words_to_bytes(root) == root_hl([int(v) for v in vals])
+
+
+@pytest.mark.parametrize("log_bottom", range(7))
+def test_level_offset_is_the_running_sum_of_the_level_sizes(ph, log_bottom):
+    B = 1 << log_bottom
+    for l in range(log_bottom + 1):
+        assert ph.ph_level_offset(B, l) == sum(B >> k for k in range(l)), l
+    assert ph.ph_level_offset(B, log_bottom) == 2 * B - 2
+
+
+@pytest.mark.parametrize("n,lb", [(0, 0), (1, 1), (3, 3), (4, 4), (5, 4), (7, 4), (9, 4)])
+def test_host_opening_matches_hashlib_at_every_leaf(ph, n, lb):
+    """merkle_path_host rebuilds the levels below lb from the values; the stored levels lb .. n lie as merkle_level_offset says"""
+    rng = random.Random(100 * n + lb)
+    values = [rng.getrandbits(64) for _ in range(1 << n)]
+    levels = levels_hl(values)
+    B, per = 1 << (n - lb), 1 << lb
+    stored = np.zeros((2 * B - 1, 8), dtype=np.uint32)
+    for l in range(lb, n + 1):
+        off = ph.ph_level_offset(B, l - lb)
+        for k, d in enumerate(levels[l]):
+            stored[off + k] = bytes_to_words(d)
+    arr = np.array(values, dtype=np.uint64)
+    for i in range(1 << n):
+        vals = np.ascontiguousarray(arr[(i >> lb) << lb:((i >> lb) << lb) + per])
+        sib = np.zeros((max(1, n - lb), 8), dtype=np.uint32)
+        for l in range(lb, n):
+            sib[l - lb] = stored[ph.ph_level_offset(B, l - lb) + ((i >> l) ^ 1)]
+        leaf = ctypes.c_uint64()
+        path = (ctypes.c_uint8 * max(1, 32 * n))()
+        ph.ph_path(n, lb, i, vals.ctypes.data_as(u64p), sib.ctypes.data_as(u32p), ctypes.byref(leaf), path)
+        assert leaf.value == values[i], i
+        assert bytes(path)[:32 * n] == b"".join(path_hl(values, i, levels)), i
 
 
 @pytest.mark.parametrize("p,m", [(3, 0), (3, 1), (3, 3), (5, 2), (7, 2), (11, 3)])

@@ -1,12 +1,12 @@
 // Part of sumcheck_hip.hip (included there, in order): C ABI: the Ligero-style commitment over the linear-time expander code of
 // kernels/expander.hpp, for fields without two-adicity.  Only the encoder differs from engine/abi_ligero.inc: the commitment
-// is an ordinary sc_ligero, and the tree, the combinations and the openings are that file's, unchanged.
+// is an ordinary sc_ligero: the combinations and the openings are that file's, the tree engine/merkle.inc's.
 
 namespace {
 
 // the checks sc_xc_encode_rows and sc_ligero_commit_code(SC_CODE_EXPANDER) share; *n = log2 of the table
 int xc_shape(sc_ctx* ctx, const sc_table* t, size_t log_cols, const char* what, int* n) {
-  SC_TRY(pcs_one_device(ctx, what));
+  SC_TRY(one_device_only(ctx, what));
   SC_TRY(check_table(ctx, t, what));
   *n = log2_of(t->len);
   if (log_cols > (size_t)*n) return fail(ctx, SC_ERR_ARG, "%s: log_cols = %zu exceeds the table's %d variables", what, log_cols, *n);
@@ -22,47 +22,31 @@ int xc_shape(sc_ctx* ctx, const sc_table* t, size_t log_cols, const char* what, 
 // the inverses 1/1 .. 1/63 of this context's field (the base matrices K[j][k] = 1/(j + k + 1) of every m <= 32), built on the
 // host at first use
 int xc_inverses(sc_ctx* ctx, const u64** inv) {
-  if (!ctx->d_xc_inv) {
+  SC_TRY(upload_once(ctx, &ctx->d_xc_inv, sc::kXcInvWords, "base matrix", [&](u64* h) {
     const HostField hf(ctx->fp);
-    u64 h[sc::kXcInvWords] = {};
     u64 s = hf.one();
     for (int i = 1; i < sc::kXcInvWords; ++i, s = hf.add(s, hf.one())) h[i] = hf.inv(s);
-    u64* d = nullptr;
-    SC_HIP(ctx, hipMalloc(&d, sizeof(h)));
-    if (hipMemcpy(d, h, sizeof(h), hipMemcpyHostToDevice) != hipSuccess) {
-      (void)hipFree(d);
-      poison(ctx);
-      return fail(ctx, SC_ERR_HIP, "base matrix upload failed");
-    }
-    ctx->d_xc_inv = d;
-  }
+  }));
   *inv = ctx->d_xc_inv;
   return SC_OK;
 }
 
 // E = the encoding of the 2^(n-c) rows of `in`: one launch, every word of `in` read once and every word of E written once
 int xc_encode_impl(sc_ctx* ctx, const u64* in, int n, int c, u64* E) {
-  const int tile_log = sc::xc_tile_log(c + 1, n + 1);
+  const int tile_log = sc::row_tile_log(c + 1, n + 1);
   const u64* inv = nullptr;
   SC_TRY(xc_inverses(ctx, &inv));
   const size_t lds = sc::xc_lds_words(tile_log) * sizeof(u64);
   const unsigned blocks = 1u << (n + 1 - tile_log);
   const int vec = c >= 1 && ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(E)) & 15) == 0;
-  hipError_t ea = hipSuccess;
-  SC_TRY(timer_begin(ctx, SC_KIND_XC_ENCODE, c, sc::xc_levels(c), n, (u64)8 << n, (u64)8 << (n + 1)));
-  SC_DISPATCH_FIELD(ctx, F, f, {
-    if (lds > 65536 && !ctx->xc_lds_allowed[ctx->gold ? 1 : 0]) {
-      ea = hipFuncSetAttribute(kernel_ptr(&sc::xc_encode_rows_kernel<F>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)(sc::xc_lds_words(sc::kXcMaxLogCols + 1) * sizeof(u64)));
-      if (ea == hipSuccess) ctx->xc_lds_allowed[ctx->gold ? 1 : 0] = true;
-    }
-    if (ea == hipSuccess)
-      hipLaunchKernelGGL((sc::xc_encode_rows_kernel<F>), dim3(blocks), dim3(sc::xc_threads(tile_log)), lds, ctx->stream, f, in, E, inv, c, tile_log, vec);
+  if (lds > 65536)
+    SC_DISPATCH_FIELD(ctx, F, f, (void)f; SC_HIP(ctx, allow_dynamic_lds(ctx, kernel_ptr(&sc::xc_encode_rows_kernel<F>),
+                                                                         sc::xc_lds_words(sc::kXcMaxLogCols + 1) * sizeof(u64))));
+  return launch_recorded(ctx, {SC_KIND_XC_ENCODE, c, sc::xc_levels(c), n, (u64)8 << n, (u64)8 << (n + 1)}, "xc_encode_rows_kernel", [&] {
+    SC_DISPATCH_FIELD(ctx, F, f,
+                      hipLaunchKernelGGL((sc::xc_encode_rows_kernel<F>), dim3(blocks), dim3(sc::xc_threads(tile_log)), lds, ctx->stream, f, in, E, inv,
+                                         c, tile_log, vec));
   });
-  SC_HIP(ctx, ea);
-  SC_TRY(pcs_launched(ctx, "xc_encode_rows_kernel"));
-  SC_TRY(timer_end(ctx));
-  return SC_OK;
 }
 
 }  // namespace

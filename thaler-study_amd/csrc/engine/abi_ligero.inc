@@ -1,16 +1,15 @@
 // Part of sumcheck_hip.hip (included there, in order): C ABI: the Ligero-style commitment - Reed-Solomon encoding of the rows of a
 // table, the SHA-256 Merkle tree over the columns of the codeword matrix, and what an opening needs: linear combinations of
-// the rows and opened columns (kernels/ligero.hpp states the contract).
+// the rows and opened columns (kernels/ligero.hpp states the contract).  The tree above the column leaves is engine/merkle.inc's.
 
-// A commitment: the codeword matrix E (owned) and every level of the tree over its L columns, bottom up, 8 words per node.
+// A commitment: the codeword matrix E (owned) and every level of the tree over its L columns.
 struct sc_ligero {
   const sc_ctx* ctx = nullptr;
   const sc_table* t = nullptr;   // borrowed: must outlive the commitment
   int r = 0, c = 0, rho = 0;
   int code = SC_CODE_RS;         // the row code of E: Reed-Solomon, or the expander code of engine/abi_expander.inc
   TableBuf E;
-  PoolBuf d_levels;
-  uint32_t root[8] = {};
+  MerkleLevels levels;   // L nodes at the bottom
 };
 
 namespace {
@@ -31,7 +30,7 @@ void two_adic_root(const HostField& hf, int* s_out, u64* w_max) {
 
 // the checks sc_rs_encode_rows and sc_ligero_commit share; *n = log2 of the table
 int ligero_shape(sc_ctx* ctx, const sc_table* t, size_t log_cols, size_t log_blowup, const char* what, int* n) {
-  SC_TRY(pcs_one_device(ctx, what));
+  SC_TRY(one_device_only(ctx, what));
   SC_TRY(check_table(ctx, t, what));
   *n = log2_of(t->len);
   if (log_blowup < 1 || log_blowup > 2) return fail(ctx, SC_ERR_ARG, "%s: log_blowup is %zu, not 1 or 2", what, log_blowup);
@@ -61,88 +60,45 @@ int rs_twiddles(sc_ctx* ctx, int log_len, const u64** tw, sc::RsRoots* roots) {
     const int tz = k ? __builtin_ctz(k) : 4;
     roots->w16[k] = s + tz >= 4 ? hf.pow(ctx->rs_w_max, s >= 4 ? (u64)k << (s - 4) : (u64)k >> (4 - s)) : 0;
   }
-  if (!ctx->d_rs_twiddles[log_len]) {
+  SC_TRY(upload_once(ctx, &ctx->d_rs_twiddles[log_len], std::max<size_t>(1, ((size_t)1 << log_len) / 2), "twiddle", [&](u64* h) {
     u64 w = ctx->rs_w_max;
     for (int k = s; k > log_len; --k) w = hf.mul(w, w);
-    const size_t half = std::max<size_t>(1, ((size_t)1 << log_len) / 2);
-    std::vector<u64> h(half);
     h[0] = hf.one();
-    for (size_t i = 1; i < half; ++i) h[i] = hf.mul(h[i - 1], w);
-    u64* d = nullptr;
-    SC_HIP(ctx, hipMalloc(&d, half * sizeof(u64)));
-    if (hipMemcpy(d, h.data(), half * sizeof(u64), hipMemcpyHostToDevice) != hipSuccess) {
-      (void)hipFree(d);
-      poison(ctx);
-      return fail(ctx, SC_ERR_HIP, "twiddle upload failed");
-    }
-    ctx->d_rs_twiddles[log_len] = d;
-  }
+    for (size_t i = 1; i < ((size_t)1 << log_len) / 2; ++i) h[i] = hf.mul(h[i - 1], w);
+  }));
   *tw = ctx->d_rs_twiddles[log_len];
   return SC_OK;
 }
 
 // E = the encoding of the 2^(n-c) rows of `in`: one launch, every word of `in` read once and every word of E written once
 int rs_encode_impl(sc_ctx* ctx, const u64* in, int n, int c, int rho, u64* E) {
-  const int log_len = c + rho, tile_log = sc::rs_tile_log(log_len, n + rho);
+  const int log_len = c + rho, tile_log = sc::row_tile_log(log_len, n + rho);
   const u64* tw = nullptr;
   sc::RsRoots roots;
   SC_TRY(rs_twiddles(ctx, log_len, &tw, &roots));
   const size_t lds = sc::rs_lds_words(tile_log) * sizeof(u64);
   const unsigned blocks = 1u << (n + rho - tile_log);
   const int vec = (tile_log - rho >= 1) && ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(E)) & 15) == 0;
-  hipError_t ea = hipSuccess;
-  SC_TRY(timer_begin(ctx, SC_KIND_RS_ENCODE, c, rho, n, (u64)8 << n, (u64)8 << (n + rho)));
-  SC_DISPATCH_FIELD(ctx, F, f, {
-    if (lds > 65536 && !ctx->rs_lds_allowed[ctx->gold ? 1 : 0]) {
-      ea = hipFuncSetAttribute(kernel_ptr(&sc::rs_encode_rows_kernel<F>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)(sc::rs_lds_words(sc::kRsMaxLog) * sizeof(u64)));
-      if (ea == hipSuccess) ctx->rs_lds_allowed[ctx->gold ? 1 : 0] = true;
-    }
-    if (ea == hipSuccess)
-      hipLaunchKernelGGL((sc::rs_encode_rows_kernel<F>), dim3(blocks), dim3(sc::rs_threads(tile_log, sc::rs_max_threads<F>())), lds, ctx->stream, f, in, E, tw, roots, c, rho, tile_log,
-                         vec);
+  if (lds > 65536)
+    SC_DISPATCH_FIELD(ctx, F, f, (void)f; SC_HIP(ctx, allow_dynamic_lds(ctx, kernel_ptr(&sc::rs_encode_rows_kernel<F>),
+                                                                         sc::rs_lds_words(sc::kRsMaxLog) * sizeof(u64))));
+  return launch_recorded(ctx, {SC_KIND_RS_ENCODE, c, rho, n, (u64)8 << n, (u64)8 << (n + rho)}, "rs_encode_rows_kernel", [&] {
+    SC_DISPATCH_FIELD(ctx, F, f,
+                      hipLaunchKernelGGL((sc::rs_encode_rows_kernel<F>), dim3(blocks), dim3(sc::rs_threads(tile_log, sc::rs_max_threads<F>())), lds,
+                                         ctx->stream, f, in, E, tw, roots, c, rho, tile_log, vec));
   });
-  SC_HIP(ctx, ea);
-  SC_TRY(pcs_launched(ctx, "rs_encode_rows_kernel"));
-  SC_TRY(timer_end(ctx));
-  return SC_OK;
 }
 
-// column_leaf_kernel over E, one merkle_level_kernel launch per level while a level has more than kMerkleTopNodes nodes, then the
-// rest of the tree in one block (the kernels of the Relaxed PCS, unchanged); the root comes back to the host.
+// column_leaf_kernel over E, then the tree above the leaves
 int ligero_tree_build(sc_ctx* ctx, sc_ligero* lg) {
   const int depth = lg->c + lg->rho, n = lg->r + lg->c;
   const u64 L = (u64)1 << depth, R = (u64)1 << lg->r;
-  u32* in = reinterpret_cast<u32*>(lg->d_levels.get());
-  SC_TRY(timer_begin(ctx, SC_KIND_LIGERO, 0, lg->r, n, 8 * R * L, 32 * L));
-  SC_DISPATCH_FIELD(ctx, F, f,
-                    hipLaunchKernelGGL((sc::column_leaf_kernel<F>), dim3(pcs_grid(ctx, L)), dim3(sc::kBlock), 0, ctx->stream, f,
-                                       (const u64*)lg->E->d, (u32)R, (u32)L, in));
-  SC_TRY(pcs_launched(ctx, "column_leaf_kernel"));
-  SC_TRY(timer_end(ctx));
-  u64 in_nodes = L;
-  int level = 0;
-  while (in_nodes > 2 * (u64)sc::kMerkleTopNodes) {
-    const u64 nodes = in_nodes / 2;
-    u32* out = in + 8 * in_nodes;
-    SC_TRY(timer_begin(ctx, SC_KIND_MERKLE, 1, level + 1, depth, 32 * in_nodes, 32 * nodes));
-    hipLaunchKernelGGL(sc::merkle_level_kernel, dim3(pcs_grid(ctx, nodes)), dim3(sc::kBlock), 0, ctx->stream, (const u32*)in, nodes, out);
-    SC_TRY(pcs_launched(ctx, "merkle_level_kernel"));
-    SC_TRY(timer_end(ctx));
-    in = out;
-    in_nodes = nodes;
-    ++level;
-  }
-  if (in_nodes > 1) {
-    SC_TRY(timer_begin(ctx, SC_KIND_MERKLE, 2, level + 1, depth, 32 * (2 * in_nodes - 2), 32 * (in_nodes - 1)));
-    hipLaunchKernelGGL(sc::merkle_top_kernel, dim3(1), dim3(sc::kBlock), 0, ctx->stream, in, (u32)in_nodes);
-    SC_TRY(pcs_launched(ctx, "merkle_top_kernel"));
-    SC_TRY(timer_end(ctx));
-  }
-  SC_HIP(ctx, hipMemcpyAsync(lg->root, reinterpret_cast<const u32*>(lg->d_levels.get()) + 8 * (2 * L - 2), 32, hipMemcpyDeviceToHost,
-                             ctx->stream));
-  SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return SC_OK;
+  SC_TRY(launch_recorded(ctx, {SC_KIND_LIGERO, 0, lg->r, n, 8 * R * L, 32 * L}, "column_leaf_kernel", [&] {
+    SC_DISPATCH_FIELD(ctx, F, f,
+                      hipLaunchKernelGGL((sc::column_leaf_kernel<F>), dim3(strided_grid(ctx, L)), dim3(sc::kBlock), 0, ctx->stream, f,
+                                         (const u64*)lg->E->d, (u32)R, (u32)L, lg->levels.words()));
+  }));
+  return merkle_finish(ctx, &lg->levels, 0, depth);
 }
 
 int ligero_check(sc_ctx* ctx, const sc_ligero* lg, const char* what) {
@@ -178,7 +134,7 @@ static int ligero_commit_with(sc_ctx* ctx, const sc_table* t, int n, int c, int 
   lg->rho = rho;
   lg->code = code;
   int rc = lg->E.alloc(ctx, (size_t)1 << (n + rho));
-  if (rc == SC_OK) rc = lg->d_levels.alloc(ctx, 4 * (((size_t)2 << (c + rho)) - 1));
+  if (rc == SC_OK) rc = lg->levels.alloc(ctx, c + rho);
   if (rc == SC_OK) rc = encode(lg->E->d);
   if (rc == SC_OK) rc = ligero_tree_build(ctx, lg);
   if (rc != SC_OK) {
@@ -200,7 +156,7 @@ extern "C" int sc_ligero_commit(sc_ctx* ctx, const sc_table* t, size_t log_cols,
 
 extern "C" int sc_ligero_root(const sc_ligero* lg, uint8_t root[32]) {
   if (!lg || !root) return SC_ERR_ARG;
-  put_digest(root, lg->root);
+  sc::put_digest(root, lg->levels.root);
   return SC_OK;
 }
 
@@ -235,23 +191,20 @@ extern "C" int sc_ligero_combine_rows(sc_ctx* ctx, const sc_ligero* lg, const ui
   if (splits > 1) SC_TRY(d_part.alloc(ctx, splits * words));
   SC_HIP(ctx, hipMemcpyAsync(d_w, weights, count * R * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
   u64* part = splits > 1 ? d_part.get() : d_out.get();
-  SC_TRY(timer_begin(ctx, SC_KIND_LIGERO, 1, (int)count, lg->r + lg->c, 8 * (R * C + count * R), 8 * splits * words));
-  SC_DISPATCH_FIELD(ctx, F, f, with_const<1, 2, 3, 4>((int)count, [&](auto M) {
-                      with_const<1, 2>(V, [&](auto VV) {
-                        hipLaunchKernelGGL((sc::row_combine_kernel<F, M, VV>), dim3(bx, (unsigned)splits), dim3(sc::kBlock), 0, ctx->stream, f,
-                                           (const u64*)lg->t->d, (const u64*)d_w.get(), R, rows_per, (sc::u32)C, part);
-                      });
-                    }));
-  SC_TRY(pcs_launched(ctx, "row_combine_kernel"));
-  SC_TRY(timer_end(ctx));
-  if (splits > 1) {
-    SC_TRY(timer_begin(ctx, SC_KIND_LIGERO, 1, 0, lg->r + lg->c, 8 * splits * words, 8 * words));
-    SC_DISPATCH_FIELD(ctx, F, f,
-                      hipLaunchKernelGGL((sc::row_combine_sum_kernel<F>), dim3(pcs_grid(ctx, words)), dim3(sc::kBlock), 0, ctx->stream, f,
-                                         (const u64*)d_part.get(), (sc::u32)splits, (sc::u32)words, d_out.get()));
-    SC_TRY(pcs_launched(ctx, "row_combine_sum_kernel"));
-    SC_TRY(timer_end(ctx));
-  }
+  SC_TRY(launch_recorded(ctx, {SC_KIND_LIGERO, 1, (int)count, lg->r + lg->c, 8 * (R * C + count * R), 8 * splits * words}, "row_combine_kernel", [&] {
+    SC_DISPATCH_FIELD(ctx, F, f, with_const<1, 2, 3, 4>((int)count, [&](auto M) {
+                        with_const<1, 2>(V, [&](auto VV) {
+                          hipLaunchKernelGGL((sc::row_combine_kernel<F, M, VV>), dim3(bx, (unsigned)splits), dim3(sc::kBlock), 0, ctx->stream, f,
+                                             (const u64*)lg->t->d, (const u64*)d_w.get(), R, rows_per, (sc::u32)C, part);
+                        });
+                      }));
+  }));
+  if (splits > 1)
+    SC_TRY(launch_recorded(ctx, {SC_KIND_LIGERO, 1, 0, lg->r + lg->c, 8 * splits * words, 8 * words}, "row_combine_sum_kernel", [&] {
+      SC_DISPATCH_FIELD(ctx, F, f,
+                        hipLaunchKernelGGL((sc::row_combine_sum_kernel<F>), dim3(strided_grid(ctx, words)), dim3(sc::kBlock), 0, ctx->stream, f,
+                                           (const u64*)d_part.get(), (sc::u32)splits, (sc::u32)words, d_out.get()));
+    }));
   SC_HIP(ctx, hipMemcpyAsync(out, d_out, words * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
   SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SC_OK;
@@ -282,16 +235,14 @@ extern "C" int sc_ligero_open_columns(sc_ctx* ctx, const sc_ligero* lg, const ui
     const size_t k = std::min(chunk, count - q0);
     const u64 moved = (u64)k * (8 * R + 32 * depth);
     SC_HIP(ctx, hipMemcpyAsync(d_idx, cols + q0, k * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
-    SC_TRY(timer_begin(ctx, SC_KIND_LIGERO, 2, (int)std::min<size_t>(k, 1u << 30), lg->r + lg->c, moved, moved));
-    hipLaunchKernelGGL(sc::column_open_kernel, dim3((unsigned)std::min<size_t>(k, (size_t)8 * ctx->num_cus)), dim3(sc::kBlock), 0, ctx->stream,
-                       (const u64*)lg->E->d, reinterpret_cast<const u32*>(lg->d_levels.get()), (const u64*)d_idx, (u32)k, R, (u32)L, depth,
-                       d_vals, d_sib);
-    SC_TRY(pcs_launched(ctx, "column_open_kernel"));
-    SC_TRY(timer_end(ctx));
+    SC_TRY(launch_recorded(ctx, {SC_KIND_LIGERO, 2, (int)std::min<size_t>(k, 1u << 30), lg->r + lg->c, moved, moved}, "column_open_kernel", [&] {
+      hipLaunchKernelGGL(sc::column_open_kernel, dim3((unsigned)std::min<size_t>(k, (size_t)8 * ctx->num_cus)), dim3(sc::kBlock), 0, ctx->stream,
+                         (const u64*)lg->E->d, (const u32*)lg->levels.words(), (const u64*)d_idx, (u32)k, R, (u32)L, depth, d_vals, d_sib);
+    }));
     SC_HIP(ctx, hipMemcpyAsync(values + q0 * R, d_vals, k * R * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
     SC_HIP(ctx, hipMemcpyAsync(hs.data(), d_sib, k * depth * 32, hipMemcpyDeviceToHost, ctx->stream));
     SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (size_t e = 0; e < k * depth; ++e) put_digest(paths + (q0 * depth + e) * 32, &hs[e * 8]);
+    sc::put_paths(paths + q0 * depth * 32, depth, 0, hs.data(), k, depth);
   }
   return SC_OK;
 }

@@ -1,41 +1,19 @@
-// Part of sumcheck_hip.hip (included there, in order): C ABI: the relaxed PCS - the prover's grid evaluation and the SHA-256
-// Merkle commitment of any table (kernels/pcs.hpp, which states the leaf order and the hashing contract).
+// Part of sumcheck_hip.hip (included there, in order): C ABI: the relaxed PCS - the prover's grid evaluation (kernels/pcs.hpp, which
+// states the leaf order) and the SHA-256 Merkle commitment of any table: its leaves here, the tree above them engine/merkle.inc's.
 
-using sc::u32;
-
-// A commitment: the stored levels lb .. n of the tree over the 2^n entries of a borrowed table, bottom up, 8 words per node, in
-// one pool block.  The levels below lb are recomputed from the table by every opening.
+// A commitment: the stored levels lb .. n of the tree over the 2^n entries of a borrowed table.  The levels below lb are recomputed
+// from the table by every opening.
 struct sc_merkle_tree {
   const sc_ctx* ctx = nullptr;
   const sc_table* t = nullptr;   // borrowed: must outlive the tree
   int n = 0, lb = 0;
-  PoolBuf d_levels;
-  uint32_t root[8] = {};
+  MerkleLevels levels;   // 2^(n - lb) nodes at the bottom
 };
 
 namespace {
 
 constexpr size_t kGridMaxPoints = (size_t)1 << 28;   // p^m <= 2^28: N <= 2^28 values (2 GiB)
 constexpr size_t kOpenChunk = 4096;                  // openings per launch of merkle_open_kernel
-
-int pcs_one_device(sc_ctx* ctx, const char* what) {
-  if (is_multi(ctx) || ctx->world > 1)
-    return fail(ctx, SC_ERR_UNSUPPORTED, "%s: runs on a context of one device and one rank (this one is %s)", what,
-                is_multi(ctx) ? "a multi-device handle" : "sharded");
-  return SC_OK;
-}
-
-int pcs_launched(sc_ctx* ctx, const char* kernel) {
-  if (hipGetLastError() != hipSuccess) {
-    poison(ctx);
-    return fail(ctx, SC_ERR_HIP, "%s launch failed", kernel);
-  }
-  return SC_OK;
-}
-
-unsigned pcs_grid(const sc_ctx* ctx, u64 threads) {
-  return (unsigned)std::max<u64>(1, std::min<u64>((threads + sc::kBlock - 1) / sc::kBlock, (u64)8 * ctx->num_cus));
-}
 
 // One grid_extend_kernel launch per variable, m - 1 first (kernels/pcs.hpp): stage s reads p^s 2^(m-s) words and writes
 // p^(s+1) 2^(m-s-1).  The stages alternate between `out` and `scratch` so that the last one writes `out`.
@@ -49,78 +27,25 @@ int grid_extend_impl(sc_ctx* ctx, const u64* in, size_t m, u64* out, u64* scratc
     const int j = (int)(m - 1 - s);
     const u64 eb = E << j;
     u64* dst = (j % 2 == 0) ? out : scratch;
-    SC_TRY(timer_begin(ctx, SC_KIND_GRID_EXTEND, j, (int)m, (int)m, 16 * eb, 8 * eb * p));
-    hipLaunchKernelGGL(sc::grid_extend_kernel, dim3(pcs_grid(ctx, eb * runs)), dim3(sc::kBlock), 0, ctx->stream, f, src, dst, (u32)eb, j,
-                       runs);
-    SC_TRY(pcs_launched(ctx, "grid_extend_kernel"));
-    SC_TRY(timer_end(ctx));
+    SC_TRY(launch_recorded(ctx, {SC_KIND_GRID_EXTEND, j, (int)m, (int)m, 16 * eb, 8 * eb * p}, "grid_extend_kernel", [&] {
+      hipLaunchKernelGGL(sc::grid_extend_kernel, dim3(strided_grid(ctx, eb * runs)), dim3(sc::kBlock), 0, ctx->stream, f, src, dst, (u32)eb, j, runs);
+    }));
     src = dst;
     E *= p;
   }
   return SC_OK;
 }
 
-// The leaf kernel up to level lb, one launch per level while a level has more than kMerkleTopNodes nodes, then the rest of the
-// tree in one block; the root comes back to the host.
+// The leaf kernel up to level lb, then the tree above it
 int merkle_build(sc_ctx* ctx, sc_merkle_tree* tr) {
   const int n = tr->n, lb = tr->lb;
-  u32* in = reinterpret_cast<u32*>(tr->d_levels.get());
-  u64 in_nodes = (u64)1 << (n - lb);
-  SC_TRY(timer_begin(ctx, SC_KIND_MERKLE, 0, lb, n, (u64)8 << n, 32 * in_nodes));
-  SC_DISPATCH_FIELD(ctx, F, f,
-                    hipLaunchKernelGGL((sc::merkle_leaf_kernel<F>), dim3(pcs_grid(ctx, in_nodes)), dim3(sc::kBlock), 0, ctx->stream, f,
-                                       (const u64*)tr->t->d, lb, in_nodes, in));
-  SC_TRY(pcs_launched(ctx, "merkle_leaf_kernel"));
-  SC_TRY(timer_end(ctx));
-  int level = lb;
-  while (in_nodes > 2 * (u64)sc::kMerkleTopNodes) {
-    const u64 nodes = in_nodes / 2;
-    u32* out = in + 8 * in_nodes;
-    SC_TRY(timer_begin(ctx, SC_KIND_MERKLE, 1, level + 1, n, 32 * in_nodes, 32 * nodes));
-    hipLaunchKernelGGL(sc::merkle_level_kernel, dim3(pcs_grid(ctx, nodes)), dim3(sc::kBlock), 0, ctx->stream, (const u32*)in, nodes, out);
-    SC_TRY(pcs_launched(ctx, "merkle_level_kernel"));
-    SC_TRY(timer_end(ctx));
-    in = out;
-    in_nodes = nodes;
-    ++level;
-  }
-  if (in_nodes > 1) {
-    SC_TRY(timer_begin(ctx, SC_KIND_MERKLE, 2, level + 1, n, 32 * (2 * in_nodes - 2), 32 * (in_nodes - 1)));
-    hipLaunchKernelGGL(sc::merkle_top_kernel, dim3(1), dim3(sc::kBlock), 0, ctx->stream, in, (u32)in_nodes);
-    SC_TRY(pcs_launched(ctx, "merkle_top_kernel"));
-    SC_TRY(timer_end(ctx));
-  }
-  const u64 total = ((u64)2 << (n - lb)) - 1;
-  SC_HIP(ctx, hipMemcpyAsync(tr->root, reinterpret_cast<const u32*>(tr->d_levels.get()) + 8 * (total - 1), 32, hipMemcpyDeviceToHost,
-                             ctx->stream));
-  SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return SC_OK;
-}
-
-void put_digest(uint8_t* out, const u32* w) {   // the ABI's bytes: each word big-endian
-  for (int k = 0; k < 8; ++k) {
-    out[4 * k] = (uint8_t)(w[k] >> 24);
-    out[4 * k + 1] = (uint8_t)(w[k] >> 16);
-    out[4 * k + 2] = (uint8_t)(w[k] >> 8);
-    out[4 * k + 3] = (uint8_t)w[k];
-  }
-}
-
-// One opening on the host: the bottom subtree from its 2^lb canonical values (the shared compression function), then the
-// stored siblings the device gathered.
-void merkle_path_host(int n, int lb, u64 i, const u64* vals, const u32* sib, u64* leaf, uint8_t* path) {
-  const u32 per = 1u << lb, li = (u32)(i & (per - 1));
-  std::vector<u32> cur(8 * per), next(4 * per);
-  for (u32 j = 0; j < per; ++j) sc::sha256_leaf(vals[j], *reinterpret_cast<u32(*)[8]>(&cur[8 * j]));
-  *leaf = vals[li];
-  for (int l = 0; l < lb; ++l) {
-    put_digest(path + 32 * l, &cur[8 * ((li >> l) ^ 1)]);
-    for (u32 k = 0; k < (per >> (l + 1)); ++k)
-      sc::sha256_node(*reinterpret_cast<const u32(*)[8]>(&cur[16 * k]), *reinterpret_cast<const u32(*)[8]>(&cur[16 * k + 8]),
-                      *reinterpret_cast<u32(*)[8]>(&next[8 * k]));
-    std::swap(cur, next);
-  }
-  for (int l = lb; l < n; ++l) put_digest(path + 32 * l, sib + 8 * (l - lb));
+  const u64 subtrees = (u64)1 << (n - lb);
+  SC_TRY(launch_recorded(ctx, {SC_KIND_MERKLE, 0, lb, n, (u64)8 << n, 32 * subtrees}, "merkle_leaf_kernel", [&] {
+    SC_DISPATCH_FIELD(ctx, F, f,
+                      hipLaunchKernelGGL((sc::merkle_leaf_kernel<F>), dim3(strided_grid(ctx, subtrees)), dim3(sc::kBlock), 0, ctx->stream, f,
+                                         (const u64*)tr->t->d, lb, subtrees, tr->levels.words()));
+  }));
+  return merkle_finish(ctx, &tr->levels, lb, n);
 }
 
 }  // namespace
@@ -129,7 +54,7 @@ void merkle_path_host(int n, int lb, u64 i, const u64* vals, const u32* sib, u64
 extern "C" int sc_table_extend_grid(sc_ctx* ctx, const sc_table* t, size_t m, sc_table** out) {
   if (!ctx || !out) return SC_ERR_ARG;
   *out = nullptr;
-  SC_TRY(pcs_one_device(ctx, "sc_table_extend_grid"));
+  SC_TRY(one_device_only(ctx, "sc_table_extend_grid"));
   SC_TRY(check_table(ctx, t, "sc_table_extend_grid"));
   if (m >= 63 || t->len != ((size_t)1 << m))
     return fail(ctx, SC_ERR_ARG, "sc_table_extend_grid: the table has %zu entries, not 2^m = 2^%zu", t->len, m);
@@ -173,7 +98,7 @@ extern "C" int sc_table_extend_grid(sc_ctx* ctx, const sc_table* t, size_t m, sc
 extern "C" int sc_merkle_commit(sc_ctx* ctx, const sc_table* t, sc_merkle_tree** out) {
   if (!ctx || !out) return SC_ERR_ARG;
   *out = nullptr;
-  SC_TRY(pcs_one_device(ctx, "sc_merkle_commit"));
+  SC_TRY(one_device_only(ctx, "sc_merkle_commit"));
   SC_TRY(check_table(ctx, t, "sc_merkle_commit"));
   const int n = log2_of(t->len);
   if (n > 28) return fail(ctx, SC_ERR_ARG, "sc_merkle_commit: 2^%d leaves (at most 2^28)", n);
@@ -184,7 +109,7 @@ extern "C" int sc_merkle_commit(sc_ctx* ctx, const sc_table* t, sc_merkle_tree**
   tr->t = t;
   tr->n = n;
   tr->lb = std::min(n, sc::kMerkleBase);
-  int rc = tr->d_levels.alloc(ctx, 4 * (((size_t)2 << (n - tr->lb)) - 1));
+  int rc = tr->levels.alloc(ctx, n - tr->lb);
   if (rc == SC_OK) rc = merkle_build(ctx, tr);
   if (rc != SC_OK) {
     delete tr;
@@ -197,7 +122,7 @@ extern "C" int sc_merkle_commit(sc_ctx* ctx, const sc_table* t, sc_merkle_tree**
 // MerkleTree::root (lib.rs:197-199): 32 bytes
 extern "C" int sc_merkle_root(const sc_merkle_tree* tr, uint8_t root[32]) {
   if (!tr || !root) return SC_ERR_ARG;
-  put_digest(root, tr->root);
+  sc::put_digest(root, tr->levels.root);
   return SC_OK;
 }
 
@@ -228,35 +153,23 @@ extern "C" int sc_merkle_open(sc_ctx* ctx, const sc_merkle_tree* tr, const uint6
   u32* d_sib = reinterpret_cast<u32*>(d_vals + chunk * per);
   std::vector<u64> hv(chunk * per);
   std::vector<u32> hs(std::max<size_t>(1, chunk * ns * 8));
-  int rc = SC_OK;
-  for (size_t q0 = 0; q0 < count && rc == SC_OK; q0 += chunk) {
+  for (size_t q0 = 0; q0 < count; q0 += chunk) {
     const size_t c = std::min(chunk, count - q0);
     const u64 moved = (u64)c * (8 * per + 32 * ns);
-    if (hipMemcpyAsync(d_idx, index + q0, c * sizeof(u64), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-      poison(ctx);
-      rc = fail(ctx, SC_ERR_HIP, "sc_merkle_open: copy failed");
-      break;
-    }
-    rc = timer_begin(ctx, SC_KIND_MERKLE, 3, lb, n, moved, moved);
-    if (rc != SC_OK) break;
-    SC_DISPATCH_FIELD(ctx, F, f,
-                      hipLaunchKernelGGL((sc::merkle_open_kernel<F>), dim3(pcs_grid(ctx, c)), dim3(sc::kBlock), 0, ctx->stream, f,
-                                         (const u64*)tr->t->d, reinterpret_cast<const u32*>(tr->d_levels.get()), (const u64*)d_idx, (u32)c, n,
-                                         lb, d_vals, d_sib));
-    rc = pcs_launched(ctx, "merkle_open_kernel");
-    if (rc == SC_OK) rc = timer_end(ctx);
-    if (rc != SC_OK) break;
-    if (hipMemcpyAsync(hv.data(), d_vals, c * per * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-        (ns > 0 && hipMemcpyAsync(hs.data(), d_sib, c * ns * 32, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) ||
-        hipStreamSynchronize(ctx->stream) != hipSuccess) {
-      poison(ctx);
-      rc = fail(ctx, SC_ERR_HIP, "sc_merkle_open: read-back failed");
-      break;
-    }
-    for (size_t q = 0; q < c; ++q)
-      merkle_path_host(n, lb, index[q0 + q], &hv[q * per], &hs[q * ns * 8], &leaves[q0 + q], paths ? paths + (q0 + q) * 32 * n : nullptr);
+    SC_HIP(ctx, hipMemcpyAsync(d_idx, index + q0, c * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
+    SC_TRY(launch_recorded(ctx, {SC_KIND_MERKLE, 3, lb, n, moved, moved}, "merkle_open_kernel", [&] {
+      SC_DISPATCH_FIELD(ctx, F, f,
+                        hipLaunchKernelGGL((sc::merkle_open_kernel<F>), dim3(strided_grid(ctx, c)), dim3(sc::kBlock), 0, ctx->stream, f,
+                                           (const u64*)tr->t->d, (const u32*)tr->levels.words(), (const u64*)d_idx, (u32)c, n, lb, d_vals, d_sib));
+    }));
+    SC_HIP(ctx, hipMemcpyAsync(hv.data(), d_vals, c * per * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+    if (ns > 0) SC_HIP(ctx, hipMemcpyAsync(hs.data(), d_sib, c * ns * 32, hipMemcpyDeviceToHost, ctx->stream));
+    SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    // the levels below lb from the values, on the host; the stored ones are the gathered siblings
+    for (size_t q = 0; q < c; ++q) sc::merkle_path_host(lb, index[q0 + q], &hv[q * per], &leaves[q0 + q], paths + (q0 + q) * 32 * n);
+    sc::put_paths(paths + q0 * 32 * n, n, lb, hs.data(), c, ns);
   }
-  return rc;
+  return SC_OK;
 }
 
 extern "C" int sc_merkle_tree_destroy(sc_ctx* ctx, sc_merkle_tree* tr) {

@@ -257,7 +257,10 @@ __device__ __forceinline__ void transpose_to_pieces(ull2* __restrict__ lds, ull2
 #include "kernels/triangle.hpp"
 #include "kernels/matmul.hpp"
 #include "kernels/batch.hpp"
+#include "kernels/sha256.hpp"
+#include "kernels/merkle.hpp"
 #include "kernels/pcs.hpp"
+#include "kernels/row_code.hpp"
 #include "kernels/ligero.hpp"
 #include "kernels/expander.hpp"
 #include "kernels/peer.hpp"

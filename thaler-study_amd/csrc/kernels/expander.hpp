@@ -33,11 +33,11 @@
 // The gathers are random 8-byte LDS reads and conflict; that is the code, not the layout.  Writes are consecutive.
 #pragma once
 #include "../field.hpp"
+#include "row_code.hpp"
 
 namespace sc {
 
 constexpr int kXcMaxLogCols = 13;    // c at most: L = 2^14 words in LDS
-constexpr int kXcMinTileLog = 12;    // a block takes whole rows up to this many codeword words when L is smaller
 constexpr int kXcMaxThreads = 1024;
 constexpr int kXcDegA = 8, kXcDegB = 16;
 constexpr int kXcBaseLog = 5;        // messages of up to 2^5 words take the base code
@@ -45,8 +45,8 @@ constexpr int kXcInvWords = 64;      // the table of inverses: entry s = 1/s, s 
 constexpr u64 kXcSeed = 0x4272616B65646F77ull;
 constexpr u64 kXcGolden = 0x9E3779B97F4A7C15ull;
 
+inline int xc_tile_log(int log_len, int log_total) { return row_tile_log(log_len, log_total); }   // the host harness's name for it
 SC_HD int xc_levels(int c) { return c > kXcBaseLog ? (c - kXcBaseLog + 1) / 2 : 0; }
-inline int xc_tile_log(int log_len, int log_total) { return log_len >= kXcMinTileLog ? log_len : (log_total < kXcMinTileLog ? log_total : kXcMinTileLog); }
 inline int xc_threads(int tile_log) {
   const int t = 1 << (tile_log > 2 ? tile_log - 2 : 0);
   return t < 64 ? 64 : (t > kXcMaxThreads ? kXcMaxThreads : t);

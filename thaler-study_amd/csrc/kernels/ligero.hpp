@@ -29,12 +29,12 @@
 // (group, j) with the groups 16 h words apart: padded, 32 lanes of a half fall on 2^rho g + j mod 32, all different; in every
 // later pass h >= 32 and the lanes read consecutive words.  The padding is even, so the final 16-byte reads stay aligned.
 #pragma once
-#include "pcs.hpp"
+#include "merkle.hpp"
+#include "row_code.hpp"
 
 namespace sc {
 
 constexpr int kRsMaxLog = 14;        // c + rho at most: L = 2^14 words in LDS
-constexpr int kRsMinTileLog = 12;    // a block takes whole rows up to this many codeword words when L is smaller
 constexpr int kRsMaxThreads = 1024;     // Goldilocks: four waves per SIMD hide the LDS round trips
 constexpr int kRsMaxThreadsGeneric = 512;   // the generic field's products need more than the 128 registers of that shape
 constexpr int kLigeroMaxCombine = 4;
@@ -44,7 +44,6 @@ struct RsRoots {
 };
 
 SC_HD size_t rs_lds_words(int tile_log) { return ((size_t)1 << tile_log) + ((size_t)2 << tile_log >> 5) + 2; }
-inline int rs_tile_log(int log_len, int log_total) { return log_len >= kRsMinTileLog ? log_len : (log_total < kRsMinTileLog ? log_total : kRsMinTileLog); }
 template <class F>
 constexpr int rs_max_threads() {
   return std::is_same<F, GoldilocksMont>::value ? kRsMaxThreads : kRsMaxThreadsGeneric;
@@ -241,7 +240,7 @@ __global__ __launch_bounds__(kBlock) void row_combine_sum_kernel(F f, const u64*
 }
 
 // Opening q (one block each, grid-strided): the R Montgomery words of column index[q] of E (stride L) to vals[q][R], and the
-// c + rho sibling digests of leaf index[q] to sib[q][depth][8].  levels: the whole tree bottom up, level l at node 2L - (2L >> l).
+// c + rho sibling digests of leaf index[q] to sib[q][depth][8].  levels: the whole tree bottom up (merkle.hpp).
 __global__ __launch_bounds__(kBlock) void column_open_kernel(const u64* __restrict__ E, const u32* __restrict__ levels,
                                                              const u64* __restrict__ index, u32 count, u64 rows, u32 len, int depth,
                                                              u64* __restrict__ vals, u32* __restrict__ sib) {
@@ -250,7 +249,7 @@ __global__ __launch_bounds__(kBlock) void column_open_kernel(const u64* __restri
     for (u64 i = threadIdx.x; i < rows; i += blockDim.x) vals[(u64)q * rows + i] = E[i * len + j];
     for (u32 e = threadIdx.x; e < (u32)depth * 8; e += blockDim.x) {
       const u32 l = e >> 3;
-      const u32 off = 2 * len - ((2 * len) >> l);
+      const u32 off = merkle_level_offset(len, (int)l);
       sib[((u64)q * depth + l) * 8 + (e & 7)] = levels[(u64)(off + ((j >> l) ^ 1)) * 8 + (e & 7)];
     }
   }

@@ -26,6 +26,7 @@
 #include <map>
 #include <mutex>
 #include <new>
+#include <set>
 #include <string>
 #include <thread>
 #include <type_traits>
@@ -255,11 +256,11 @@ struct sc_ctx {
   int rs_two_adicity = 0;
   u64 rs_w_max = 0;
   u64* d_rs_twiddles[15] = {};
-  bool rs_lds_allowed[2] = {};   // rs_encode_rows_kernel<generic / Goldilocks>: its dynamic LDS above 64 KiB has been requested
+  // the row encoders whose dynamic LDS above 64 KiB has been requested, by kernel (engine/merkle.inc, allow_dynamic_lds)
+  std::set<const void*> lds_allowed;
   // sc_xc_encode_rows / sc_ligero_commit_code (engine/abi_expander.inc): the inverses 1/1 .. 1/63 behind the base matrices of the
   // expander code, built at first use (workspace like the twiddle tables)
   u64* d_xc_inv = nullptr;
-  bool xc_lds_allowed[2] = {};   // xc_encode_rows_kernel<generic / Goldilocks>, as rs_lds_allowed
 
   // kernel timing
   // pass-kernel timing (option "time_kernels"): a ring of event pairs, read back only when the
@@ -593,6 +594,7 @@ static int multi_prod2_fold_and_sums(sc_ctx* m, const sc_table* a, const sc_tabl
 #include "engine/abi_matmul.inc"
 #include "engine/abi_batch.inc"
 #include "engine/abi_restrict.inc"
+#include "engine/merkle.inc"
 #include "engine/abi_pcs.inc"
 #include "engine/abi_ligero.inc"
 #include "engine/abi_expander.inc"

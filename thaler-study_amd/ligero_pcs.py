@@ -98,10 +98,7 @@ class ColumnPath(Path):
     """relaxed_pcs.Path over column leaves: the same sibling walk, started from a column's digest"""
 
     def root_from_column(self, values):
-        h = column_digest(self.field, values)
-        for level, s in enumerate(self.siblings):
-            h = node_digest(h, s) if (self.index >> level) & 1 == 0 else node_digest(s, h)
-        return h
+        return self.root_from_digest(column_digest(self.field, values))
 
     def verify_column(self, root, values):
         return self.index < (1 << len(self.siblings)) and self.root_from_column(values) == bytes(root)

@@ -4,7 +4,7 @@ The prover evaluates W~ at every point of F^m (sc_table_extend_grid) and commits
 (sc_merkle_commit); the verifier picks a random line, receives the univariate restriction of W~ to it (restrict_poly) and checks
 it at one random point of the line against a Merkle opening.  The verifier is host code (hashlib) and never touches the GPU.
 
-Contract (kernels/pcs.hpp):
+Contract (kernels/pcs.hpp for the leaf order, kernels/sha256.hpp for the hashing):
   leaf order   all_multidimentional_values(m) (:46-63): the p^m points sorted by canonical value, v_0 the most significant
                digit; point (v_0, .., v_{m-1}) is leaf o = sum_j v_j p^(m-1-j); its value is the LE MLE at it (point[0] binds
                index bit 0 of the table); values are zero-padded to a power of two
@@ -95,11 +95,14 @@ class Path:
     def __init__(self, index, siblings, field=None):
         self.index, self.siblings, self.field = int(index), [bytes(s) for s in siblings], field
 
-    def root_from(self, canonical):
-        h = leaf_digest(canonical)
+    def root_from_digest(self, h):
+        """the sibling walk from the leaf's digest `h` up to the root it leads to"""
         for level, s in enumerate(self.siblings):
             h = node_digest(h, s) if (self.index >> level) & 1 == 0 else node_digest(s, h)
         return h
+
+    def root_from(self, canonical):
+        return self.root_from_digest(leaf_digest(canonical))
 
     def verify_canonical(self, root, canonical):
         return self.index < (1 << len(self.siblings)) and self.root_from(canonical) == bytes(root)

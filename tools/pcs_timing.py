@@ -15,7 +15,7 @@ measured that for these instructions, so the fraction is an estimate against an 
 Grid traffic: the floor is 8 * 2^m bytes read + 8 * p^m written (the zero padding up to N is a memset); the launches are one per variable (not fused), and their
 records state what each reads and writes.
 
-CPU baseline: the same compression function (kernels/pcs.hpp) compiled with g++ -O2 for the host, one core, n = 20.
+CPU baseline: the same compression function (kernels/sha256.hpp) compiled with g++ -O2 for the host, one core, n = 20.
 
   python tools/pcs_timing.py [--reps 5] [--limit 600] [--trace]    every step in a child process under its own time limit;
                                                                   writes profiles/pcs_timing.json and profiles/pcs_summary.md;
