@@ -2,6 +2,7 @@
 nothing here imports the package.  Everything is in CANONICAL integers; the tests convert to and from Montgomery words at the
 boundary (mont / canon below).
 
+  FIELDS, WIDE_NTT, ROOTS               the fields of the tests and their (s, g, w_max)
   two_adic(p), omega(p, log_len)        the root of unity the contract prescribes
   ntt(row, w, p), ntt_rows_np(..)       a radix-2 transform in big integers, and one in numpy (int64 for p < 2^31) over whole matrices
   direct(row, w, p, j)                  the defining sum, one output
@@ -18,6 +19,17 @@ BABYBEAR = 2013265921
 FIELDS = [GOLD, BABYBEAR, 65537, 257]
 # (s, g, w_max) as the contract lists them
 ROOTS = {GOLD: (32, 7, 1753635133440165772), BABYBEAR: (27, 11, 1227303670), 65537: (16, 3, 3), 257: (8, 3, 3)}
+# full-width NTT-friendly primes for the generic field (tests/test_gpu_ligero_wide.py): the closest to 2^64 with 2-adicity 18
+# (R mod p = 1835007: sums and redc carry out almost always), one with s = 34 > 32, one just above 2^63, one just above 2^32
+# (the high limb is 0 or 1) and one just below 2^32.  Not part of FIELDS.
+P64S18 = 0xFFFFFFFFFFE40001
+P64S34 = 0xFFFFFFFC00000001
+P63S16 = 0x8000000000050001
+P32HI = 0x100050001
+P32LO = 0xFFF00001
+WIDE_NTT = [P64S18, P64S34, P63S16, P32HI, P32LO]
+ROOTS.update({P64S18: (18, 7, 11880867381004357348), P64S34: (34, 5, 6307343653039168829), P63S16: (16, 3, 3283862531989034960),
+              P32HI: (16, 5, 2095801761), P32LO: (20, 17, 2948152962)})
 R64 = 2**64
 
 

@@ -1,14 +1,18 @@
 """CPU-only: the Ligero-style commitment's reference (tests/ligero_ref.py) against the defining sums and the contract's constants,
 and the package's host Verifier (thaler-study_amd/ligero_pcs.py) against the reference prover: honest transcripts are accepted
-with the right value, every tampered message is refused with its own error."""
+with the right value, every tampered message is refused with its own error.  The fields are ligero_ref.FIELDS and the full-width
+primes of ligero_ref.WIDE_NTT; wide_words.half_stride_table is checked to carry every add / sub corner of each."""
 import random
 
+import numpy as np
 import pytest
 
 import ligero_ref as ref
+import wide_words as ww
 from conftest import load_package
 
 GOLD = ref.GOLD
+NTT_FIELDS = ref.FIELDS + ref.WIDE_NTT
 
 
 @pytest.fixture(scope="module")
@@ -16,7 +20,7 @@ def lp():
     return load_package().ligero_pcs
 
 
-@pytest.mark.parametrize("p", ref.FIELDS)
+@pytest.mark.parametrize("p", NTT_FIELDS)
 def test_reference_ntt_equals_the_direct_sum(p):
     rng = random.Random(p)
     for log_len in range(0, 7):
@@ -28,7 +32,27 @@ def test_reference_ntt_equals_the_direct_sum(p):
             assert [int(x) for x in ref.ntt_rows_np([row, row], w, p)[1]] == want, (p, log_len)
 
 
-@pytest.mark.parametrize("p", ref.FIELDS)
+def _is_prime(p):
+    """Miller-Rabin with the first twelve primes as bases: exact below 2^64"""
+    d, r = p - 1, 0
+    while d % 2 == 0:
+        d, r = d // 2, r + 1
+    for a in (2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37):
+        if a % p == 0:
+            continue
+        x = pow(a, d, p)
+        if x not in (1, p - 1) and all((x := x * x % p) != p - 1 for _ in range(r - 1)):
+            return False
+    return True
+
+
+def test_the_wide_fields_are_prime_and_full_width():
+    assert all(_is_prime(p) for p in NTT_FIELDS) and not _is_prime(2**64 - 1) and not _is_prime(0xFFFFFFFFFFE40001 - 2**18)
+    assert sorted(p.bit_length() for p in ref.WIDE_NTT) == [32, 33, 64, 64, 64]
+    assert set(ref.WIDE_NTT).isdisjoint(ref.FIELDS) and ref.FIELDS == [GOLD, ref.BABYBEAR, 65537, 257]
+
+
+@pytest.mark.parametrize("p", NTT_FIELDS)
 def test_derived_roots_are_the_contracts(p, lp):
     assert ref.two_adic(p) == ref.ROOTS[p]
     assert lp.two_adic_root(p) == ref.ROOTS[p]
@@ -89,13 +113,14 @@ def run_protocol(pkg, p, n, c, rho, queries, seed, tamper=None):
     return value, F.from_int(ref.mle_eval(table, ref.canon(p, point), p))
 
 
-@pytest.mark.parametrize("p,n,c,rho", [(GOLD, 6, 3, 1), (GOLD, 6, 2, 2), (65537, 5, 3, 1), (65537, 5, 0, 2)])
+@pytest.mark.parametrize("p,n,c,rho", [(GOLD, 6, 3, 1), (GOLD, 6, 2, 2), (65537, 5, 3, 1), (65537, 5, 0, 2),
+                                       (ref.P64S18, 6, 3, 1), (ref.P64S18, 6, 2, 2), (ref.P32HI, 5, 3, 1), (ref.P32HI, 5, 0, 2)])
 def test_verifier_accepts_the_reference_prover(pkg, p, n, c, rho):
     value, want = run_protocol(pkg, p, n, c, rho, 16, 100 * n + c)
     assert value == want
 
 
-@pytest.mark.parametrize("p,n,c", [(GOLD, 6, 3), (65537, 5, 3)])
+@pytest.mark.parametrize("p,n,c", [(GOLD, 6, 3), (65537, 5, 3), (ref.P64S18, 6, 3), (ref.P32HI, 5, 3)])
 def test_tampering_is_caught(pkg, p, n, c):
     lp = pkg.ligero_pcs
     for tamper, err in (("u_z", lp.EvalMismatch), ("u_gamma", lp.ProximityMismatch), ("column", lp.MerkleMismatch),
@@ -121,3 +146,23 @@ def test_errors_are_the_relaxed_pcs_family(pkg):
     lp, rp = pkg.ligero_pcs, pkg.relaxed_pcs
     assert lp.MerkleMismatch is rp.MerkleMismatch and lp.EvalMismatch is rp.EvalMismatch
     assert issubclass(lp.ProximityMismatch, rp.Error) and issubclass(lp.ColumnPath, rp.Path)
+
+
+@pytest.mark.parametrize("p", [GOLD] + ref.WIDE_NTT)
+def test_half_stride_table_covers_every_class(p):
+    """one row of 64 words, 32 rows of 2 and two rows of 2^13 put every add / sub corner that exists for p on the pairs the
+    encoder's first level adds and subtracts; every word is a residue"""
+    want = ww.classes_present(p)
+    assert {"no_borrow", "diff_zero", "diff_minus_one", "sum_p", "sum_p_plus_1", "sum_p_to_2_64"} <= want
+    assert ("sum_carry" in want) == (p > 2**63)
+    for rows, c in ((1, 6), (32, 1), (2, 13)):
+        t = ww.half_stride_table(p, rows, c, np.random.default_rng(rows + c))
+        assert t.dtype == np.uint64 and t.size == rows << c and int(t.max()) < p
+        assert ww.half_stride_classes(p, t, c) >= want, (rows, c, want - ww.half_stride_classes(p, t, c))
+    # at c = 1 the reference's outputs are the sums and differences of the pairs themselves
+    t = ww.half_stride_table(p, 32, 1, np.random.default_rng(3))
+    E = ref.encode(ref.canon(p, t), 1, 1, p)
+    for i, row in enumerate(E):
+        hi, lo = int(t[2 * i]), int(t[2 * i + 1])
+        assert ref.mont(p, [row[0], row[2]]) == [(hi + lo) % p, (hi - lo) % p]
+    assert ref.encode([5, p - 3], 1, 1, p)[0][0::2] == [2, 8]

@@ -1,5 +1,5 @@
 """Words and moduli for testing the generic field at full word width (tests/test_oracle_wide_moduli.py,
-tests/test_gpu_wide_moduli.py)."""
+tests/test_gpu_wide_moduli.py, tests/test_gpu_ligero_wide.py)."""
 import numpy as np
 
 from util import pid
@@ -157,6 +157,34 @@ def stride_classes(p, t, s):
     for i in range(len(t)):
         if not (i & 7) & s and (i & 7) + s < 8 and i + s < len(t):
             out |= classes_of(p, t[i], t[i + s])
+    return out
+
+
+def half_stride_table(p, rows, c, rng):
+    """`rows` rows of 2^c raw words for the Reed-Solomon encoder (tests/test_gpu_ligero_wide.py).  Its first executed level, at
+    the position whose twiddle is the field's one, takes t[k] + t[k + C/2] and t[k] - t[k + C/2] of the raw words of a row, k <
+    C/2 = 2^(c-1) (with c = 1 those are the outputs themselves).  Each row's pairs (k, k + C/2) take the pairs of
+    diff_classes(p) in turn, going on from row to row from a seeded start: t[k] = hi, t[k + C/2] = lo.  rows * C/2 >=
+    len(diff_classes(p)) pairs carry them all; positions past the list's end hold uniform residues (c = 0: every position)."""
+    C = 1 << c
+    t = rng.integers(0, p, size=(rows, C), dtype=np.uint64)
+    pairs = diff_classes(p)
+    start, h = int(rng.integers(0, len(pairs))), C // 2
+    for i in range(rows):
+        for k in range(min(h, max(0, len(pairs) - i * h))):
+            lo, hi = pairs[(start + i * h + k) % len(pairs)]
+            t[i, k], t[i, k + h] = hi, lo
+    return t.reshape(rows * C)
+
+
+def half_stride_classes(p, t, c):
+    """the classes met by the pairs (lo, hi) = (t[k + C/2], t[k]), k < C/2, of every row of 2^c words of t"""
+    C = 1 << c
+    t = [int(x) for x in t]
+    out = set()
+    for row in range(0, len(t), C):
+        for k in range(C // 2):
+            out |= classes_of(p, t[row + k + C // 2], t[row + k])
     return out
 
 
