@@ -236,6 +236,10 @@ int sc_ctx_kernel_time(sc_ctx* ctx, double out[2], int reset);
 #define SC_KIND_XC_ENCODE 21   /* xc_encode_rows_kernel: the row encoder of sc_xc_encode_rows / sc_ligero_commit_code(SC_CODE_EXPANDER), one launch;
                                 * kf = log_cols, ks = recursion levels, log_in = n; it reads the table once (8 * 2^n bytes) and writes the
                                 * codewords once (8 * 2^(n + 1)) */
+#define SC_KIND_RS_LONG 22     /* the two launches of a long row transform (sc_rs_encode_rows_long / sc_ligero_commit_long, codewords of 2^15 .. 2^24
+                                * words): kf = 0 the column step, rs_long_column_kernel (ks = a; reads the table, 8 * 2^n bytes, writes the codewords,
+                                * 8 * 2^(n + log_blowup)), kf = 1 the row step, rs_long_row_kernel (ks = b; reads and writes the codewords in place);
+                                * a + b = log_cols + log_blowup, log_in = n */
 typedef struct sc_launch_record {
   int32_t kind;           /* SC_KIND_* */
   int32_t kf, ks;         /* variables folded / rounds served (meaning per kind above) */
@@ -557,6 +561,15 @@ int sc_ligero_combine_rows(sc_ctx* ctx, const sc_ligero* lg, const uint64_t* wei
  * sibling digests of leaf cols[q] bottom up (verified as sc_merkle_open's, from the column's leaf digest).  Indices may repeat. */
 int sc_ligero_open_columns(sc_ctx* ctx, const sc_ligero* lg, const uint64_t* cols, size_t count, uint64_t* values, uint8_t* paths);
 int sc_ligero_destroy(sc_ctx* ctx, sc_ligero* lg);
+
+/* Rows longer than the LDS of a CU: the same encoding and the same commitment for log_cols + log_blowup up to 24, through a
+ * four-step transform (kernels/ligero_long.hpp): two launches, SC_KIND_RS_LONG, the second in place on the codeword matrix -
+ * 8 * 2^n * (1 + 3 * 2^log_blowup) bytes of traffic in all.  Up to log_cols + log_blowup = 14 they run the single launch of the calls
+ * above (SC_KIND_RS_ENCODE).  Every other limit and every error is as above, with SC_ERR_UNSUPPORTED for log_cols + log_blowup > 24
+ * (the message names 2^24: there the stored tree is 1 GiB).  The commitment is an ordinary sc_ligero with code SC_CODE_RS:
+ * sc_ligero_root / shape / code / combine_rows / open_columns / destroy serve it unchanged; its tree is 64 bytes per column. */
+int sc_rs_encode_rows_long(sc_ctx* ctx, const sc_table* t, size_t log_cols, size_t log_blowup, sc_table** out);
+int sc_ligero_commit_long(sc_ctx* ctx, const sc_table* t, size_t log_cols, size_t log_blowup, sc_ligero** out);
 
 /* ---- the same commitment over a linear-time expander code, for fields without two-adicity ------------------------------
  * (Thaler's book, section 10.5: Ligero with a linear-time code, as in Brakedown; kernels/expander.hpp states the contract,

@@ -493,6 +493,10 @@ extern "C" {
         paths: *mut u8,
     ) -> c_int;
     pub fn sc_ligero_destroy(ctx: *mut sc_ctx, lg: *mut sc_ligero) -> c_int;
+    /// sc_rs_encode_rows for log_cols + log_blowup up to 24: above 14 a four-step transform in two launches (SC_KIND_RS_LONG)
+    pub fn sc_rs_encode_rows_long(ctx: *mut sc_ctx, t: *const sc_table, log_cols: usize, log_blowup: usize, out: *mut *mut sc_table) -> c_int;
+    /// sc_ligero_commit over sc_rs_encode_rows_long: an ordinary sc_ligero with code SC_CODE_RS
+    pub fn sc_ligero_commit_long(ctx: *mut sc_ctx, t: *const sc_table, log_cols: usize, log_blowup: usize, out: *mut *mut sc_ligero) -> c_int;
 
     /// the rows of `t` (2^log_cols words each) under the linear-time expander code: every row followed by as many check words
     pub fn sc_xc_encode_rows(ctx: *mut sc_ctx, t: *const sc_table, log_cols: usize, out: *mut *mut sc_table) -> c_int;

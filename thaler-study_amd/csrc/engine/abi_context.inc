@@ -142,6 +142,8 @@ extern "C" int sc_ctx_destroy(sc_ctx* ctx) {
   if (ctx->d_points) (void)hipFree(ctx->d_points);
   for (u64* tw : ctx->d_rs_twiddles)
     if (tw) (void)hipFree(tw);
+  for (u64* tw : ctx->d_rs_twist)
+    if (tw) (void)hipFree(tw);
   if (ctx->d_xc_inv) (void)hipFree(ctx->d_xc_inv);
   if (ctx->h_batch_desc) (void)hipHostFree(ctx->h_batch_desc);
   if (ctx->h_batch) (void)hipHostFree(ctx->h_batch);

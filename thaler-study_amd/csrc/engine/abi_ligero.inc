@@ -28,16 +28,20 @@ void two_adic_root(const HostField& hf, int* s_out, u64* w_max) {
   *w_max = hf.pow(g, (p - 1) >> s);
 }
 
-// the checks sc_rs_encode_rows and sc_ligero_commit share; *n = log2 of the table
-int ligero_shape(sc_ctx* ctx, const sc_table* t, size_t log_cols, size_t log_blowup, const char* what, int* n) {
+// the checks sc_rs_encode_rows and sc_ligero_commit share with their _long forms; *n = log2 of the table.  max_log: kRsMaxLog (a
+// codeword in the LDS of a CU) or kRsLongMaxLog (the two launches of kernels/ligero_long.hpp)
+int ligero_shape(sc_ctx* ctx, const sc_table* t, size_t log_cols, size_t log_blowup, const char* what, int* n, int max_log = sc::kRsMaxLog) {
   SC_TRY(one_device_only(ctx, what));
   SC_TRY(check_table(ctx, t, what));
   *n = log2_of(t->len);
   if (log_blowup < 1 || log_blowup > 2) return fail(ctx, SC_ERR_ARG, "%s: log_blowup is %zu, not 1 or 2", what, log_blowup);
   if (log_cols > (size_t)*n) return fail(ctx, SC_ERR_ARG, "%s: log_cols = %zu exceeds the table's %d variables", what, log_cols, *n);
-  if (log_cols + log_blowup > (size_t)sc::kRsMaxLog)
-    return fail(ctx, SC_ERR_UNSUPPORTED, "%s: a codeword of 2^(%zu+%zu) words does not fit the LDS of a CU (at most 2^%d)", what, log_cols,
-                log_blowup, sc::kRsMaxLog);
+  if (log_cols + log_blowup > (size_t)max_log)
+    return max_log == sc::kRsMaxLog
+               ? fail(ctx, SC_ERR_UNSUPPORTED, "%s: a codeword of 2^(%zu+%zu) words does not fit the LDS of a CU (at most 2^%d)", what, log_cols,
+                      log_blowup, sc::kRsMaxLog)
+               : fail(ctx, SC_ERR_UNSUPPORTED, "%s: a codeword of 2^(%zu+%zu) words is longer than 2^%d (there the stored tree is 1 GiB and a tile's strided segments 32 bytes)",
+                      what, log_cols, log_blowup, max_log);
   if (*n + log_blowup > 29) return fail(ctx, SC_ERR_UNSUPPORTED, "%s: 2^(%d+%zu) codeword words (at most 2^29)", what, *n, log_blowup);
   int s = 0;
   while ((((ctx->fp.p - 1) >> s) & 1) == 0) ++s;
@@ -89,6 +93,54 @@ int rs_encode_impl(sc_ctx* ctx, const u64* in, int n, int c, int rho, u64* E) {
   });
 }
 
+// lo[i] = w_L^i, i < 2^12, then hi[i] = w_L^(2^12 i), i < 2^(log_len - 12): the twist tables of this context for L = 2^log_len,
+// 2^12 + 2^(log_len - 12) host products at first use
+int rs_twist_tables(sc_ctx* ctx, int log_len, const u64** lo, const u64** hi) {
+  const HostField hf(ctx->fp);
+  const size_t n_lo = (size_t)1 << sc::kRsTwistLoLog, n_hi = (size_t)1 << (log_len - sc::kRsTwistLoLog);
+  SC_TRY(upload_once(ctx, &ctx->d_rs_twist[log_len], n_lo + n_hi, "twist table", [&](u64* h) {
+    u64 w = ctx->rs_w_max;
+    for (int k = ctx->rs_two_adicity; k > log_len; --k) w = hf.mul(w, w);
+    h[0] = hf.one();
+    for (size_t i = 1; i < n_lo; ++i) h[i] = hf.mul(h[i - 1], w);
+    const u64 step = hf.mul(h[n_lo - 1], w);
+    h[n_lo] = hf.one();
+    for (size_t i = 1; i < n_hi; ++i) h[n_lo + i] = hf.mul(h[n_lo + i - 1], step);
+  }));
+  *lo = ctx->d_rs_twist[log_len];
+  *hi = *lo + n_lo;
+  return SC_OK;
+}
+
+// E = the encoding of the rows of `in` at any c + rho <= kRsLongMaxLog: up to kRsMaxLog rs_encode_impl itself, above it the two
+// launches of kernels/ligero_long.hpp - the column step writes E, the row step transforms it in place
+int rs_encode_long_impl(sc_ctx* ctx, const u64* in, int n, int c, int rho, u64* E) {
+  const int log_len = c + rho;
+  if (log_len <= sc::kRsMaxLog) return rs_encode_impl(ctx, in, n, c, rho, E);
+  const sc::RsLongSplit sp = sc::rs_long_split(log_len);
+  const u64 *tw_a = nullptr, *tw_b = nullptr, *lo = nullptr, *hi = nullptr;
+  sc::RsRoots roots;
+  SC_TRY(rs_twiddles(ctx, sp.a, &tw_a, &roots));
+  SC_TRY(rs_twiddles(ctx, sp.b, &tw_b, &roots));
+  SC_TRY(rs_twist_tables(ctx, log_len, &lo, &hi));
+  const size_t lds = sc::rs_lds_words(sp.tile_log) * sizeof(u64);
+  const unsigned blocks = (unsigned)sc::rs_long_blocks(sp, n + rho);
+  const int vec = ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(E)) & 15) == 0;
+  SC_DISPATCH_FIELD(ctx, F, f, (void)f; SC_HIP(ctx, allow_dynamic_lds(ctx, kernel_ptr(&sc::rs_long_column_kernel<F>), lds));
+                    SC_HIP(ctx, allow_dynamic_lds(ctx, kernel_ptr(&sc::rs_long_row_kernel<F>), lds)));
+  const u64 e_bytes = (u64)8 << (n + rho);
+  SC_TRY(launch_recorded(ctx, {SC_KIND_RS_LONG, 0, sp.a, n, (u64)8 << n, e_bytes}, "rs_long_column_kernel", [&] {
+    SC_DISPATCH_FIELD(ctx, F, f,
+                      hipLaunchKernelGGL((sc::rs_long_column_kernel<F>), dim3(blocks), dim3(sc::rs_threads(sp.tile_log, sc::rs_max_threads<F>())),
+                                         lds, ctx->stream, f, in, E, tw_a, roots, lo, hi, c, rho, vec));
+  }));
+  return launch_recorded(ctx, {SC_KIND_RS_LONG, 1, sp.b, n, e_bytes, e_bytes}, "rs_long_row_kernel", [&] {
+    SC_DISPATCH_FIELD(ctx, F, f,
+                      hipLaunchKernelGGL((sc::rs_long_row_kernel<F>), dim3(blocks), dim3(sc::rs_threads(sp.tile_log, sc::rs_max_threads<F>())), lds,
+                                         ctx->stream, f, E, tw_b, roots, log_len, vec));
+  });
+}
+
 // column_leaf_kernel over E, then the tree above the leaves
 int ligero_tree_build(sc_ctx* ctx, sc_ligero* lg) {
   const int depth = lg->c + lg->rho, n = lg->r + lg->c;
@@ -117,6 +169,19 @@ extern "C" int sc_rs_encode_rows(sc_ctx* ctx, const sc_table* t, size_t log_cols
   TableBuf E;
   SC_TRY(E.alloc(ctx, (size_t)1 << (n + log_blowup)));
   SC_TRY(rs_encode_impl(ctx, t->d, n, (int)log_cols, (int)log_blowup, E->d));
+  *out = E.release();
+  return SC_OK;
+}
+
+extern "C" int sc_rs_encode_rows_long(sc_ctx* ctx, const sc_table* t, size_t log_cols, size_t log_blowup, sc_table** out) {
+  if (!ctx || !out) return SC_ERR_ARG;
+  *out = nullptr;
+  int n = 0;
+  SC_TRY(ligero_shape(ctx, t, log_cols, log_blowup, "sc_rs_encode_rows_long", &n, sc::kRsLongMaxLog));
+  SC_TRY(set_device(ctx));
+  TableBuf E;
+  SC_TRY(E.alloc(ctx, (size_t)1 << (n + log_blowup)));
+  SC_TRY(rs_encode_long_impl(ctx, t->d, n, (int)log_cols, (int)log_blowup, E->d));
   *out = E.release();
   return SC_OK;
 }
@@ -152,6 +217,15 @@ extern "C" int sc_ligero_commit(sc_ctx* ctx, const sc_table* t, size_t log_cols,
   SC_TRY(ligero_shape(ctx, t, log_cols, log_blowup, "sc_ligero_commit", &n));
   return ligero_commit_with(ctx, t, n, (int)log_cols, (int)log_blowup, SC_CODE_RS,
                             [&](u64* E) { return rs_encode_impl(ctx, t->d, n, (int)log_cols, (int)log_blowup, E); }, out);
+}
+
+extern "C" int sc_ligero_commit_long(sc_ctx* ctx, const sc_table* t, size_t log_cols, size_t log_blowup, sc_ligero** out) {
+  if (!ctx || !out) return SC_ERR_ARG;
+  *out = nullptr;
+  int n = 0;
+  SC_TRY(ligero_shape(ctx, t, log_cols, log_blowup, "sc_ligero_commit_long", &n, sc::kRsLongMaxLog));
+  return ligero_commit_with(ctx, t, n, (int)log_cols, (int)log_blowup, SC_CODE_RS,
+                            [&](u64* E) { return rs_encode_long_impl(ctx, t->d, n, (int)log_cols, (int)log_blowup, E); }, out);
 }
 
 extern "C" int sc_ligero_root(const sc_ligero* lg, uint8_t root[32]) {

@@ -262,5 +262,6 @@ __device__ __forceinline__ void transpose_to_pieces(ull2* __restrict__ lds, ull2
 #include "kernels/pcs.hpp"
 #include "kernels/row_code.hpp"
 #include "kernels/ligero.hpp"
+#include "kernels/ligero_long.hpp"
 #include "kernels/expander.hpp"
 #include "kernels/peer.hpp"

@@ -9,9 +9,11 @@
 // Root       s = the 2-adicity of p - 1; g = the smallest integer >= 2 with g^((p-1)/2) = -1; w_max = g^((p-1)/2^s);
 //            w_L = w_max^(2^(s-c-rho)).  Derived on the host from the context's modulus, never passed in.
 //            (Goldilocks: s = 32, g = 7, w_max = 1753635133440165772; 2013265921: 27, 11, 1227303670; 65537: 16, 3, 3; 257: 8, 3, 3.)
-// Limits     c + rho <= 14 (one codeword row, 128 KiB, in the LDS of a CU); n + rho <= 29; c + rho <= s; one device, one rank.
+// Limits     c + rho <= 14 (one codeword row, 128 KiB, in the LDS of a CU) for sc_rs_encode_rows / sc_ligero_commit, c + rho <= 24 for
+//            their _long forms, which run this file's kernel up to 14 and the two launches of ligero_long.hpp above (at 2^24 the
+//            stored tree is 1 GiB); n + rho <= 29; c + rho <= s; one device, one rank.
 // Digest     Leaf j = SHA-256 of the R 8 bytes le64(canon E[0][j]) || .. || le64(canon E[R-1][j]), standard padding (R = 1:
-//            sha256_leaf); nodes are sha256_node; L leaves, every level kept (at most 1 MiB); paths bottom up, bytes as
+//            sha256_leaf); nodes are sha256_node; L leaves, every level kept (64 L bytes: 1 MiB at L = 2^14); paths bottom up, bytes as
 //            sc_merkle_open's.
 //
 // rs_encode_rows_kernel is a decimation-in-TIME transform: the bit reversal happens on the way IN.  Coefficient k of a row goes

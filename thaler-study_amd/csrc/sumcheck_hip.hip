@@ -256,6 +256,9 @@ struct sc_ctx {
   int rs_two_adicity = 0;
   u64 rs_w_max = 0;
   u64* d_rs_twiddles[15] = {};
+  // sc_rs_encode_rows_long / sc_ligero_commit_long: the two twist tables of w_L (kernels/ligero_long.hpp), one run per codeword
+  // length 2^15 .. 2^24 used so far
+  u64* d_rs_twist[25] = {};
   // the row encoders whose dynamic LDS above 64 KiB has been requested, by kernel (engine/merkle.inc, allow_dynamic_lds)
   std::set<const void*> lds_allowed;
   // sc_xc_encode_rows / sc_ligero_commit_code (engine/abi_expander.inc): the inverses 1/1 .. 1/63 behind the base matrices of the

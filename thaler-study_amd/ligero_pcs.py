@@ -18,6 +18,10 @@ Contract (kernels/ligero.hpp):
                  w_L = w_max^(2^(s - c - log_blowup))
   leaf j         SHA-256(le64(canon E[0][j]) || .. || le64(canon E[R-1][j])); nodes SHA-256(left || right); paths bottom up
   limits         c + log_blowup <= 14 and <= s, n + log_blowup <= 29, log_blowup in {1, 2}, one device and one rank
+  long rows      rs_encode_rows_long / Prover.commit_long (sc_rs_encode_rows_long, sc_ligero_commit_long; DESIGN.md section 9
+                 item 11) lift the first limit to c + log_blowup <= 24 = LONG_MAX_LOG_LEN: above 14 the rows go through a
+                 four-step transform in two launches; the encoding, the commitment and the Verifier are the same.
+                 opening_bytes and long_log_cols give the size of an opening and the log_cols that makes it smallest.
 
 Field elements are Montgomery words, as everywhere in this package; leaves hash canonical integers.  `queries` is the caller's
 parameter: DESIGN.md gives the book's soundness expression for it; no security level is claimed here.
@@ -37,6 +41,7 @@ from .dense_mle import DenseMultilinearExtension, _u64p, _words
 from .relaxed_pcs import Error, EvalMismatch, MerkleMismatch, Path, _draw, node_digest
 
 MAX_LOG_LEN = 14
+LONG_MAX_LOG_LEN = 24                  # c + log_blowup of rs_encode_rows_long / Prover.commit_long
 CODES = {"rs": 0, "expander": 1}       # SC_CODE_RS, SC_CODE_EXPANDER
 
 
@@ -87,6 +92,17 @@ def default_log_cols(num_vars, log_blowup, code="rs"):
     return min((num_vars + 1) // 2, MAX_LOG_LEN - log_blowup)
 
 
+def opening_bytes(num_vars, log_cols, log_blowup, queries):
+    """bytes of an opening: `queries` columns of 2^(n - c) words with their paths of c + log_blowup digests, and the two combined
+    rows of 2^c words"""
+    return queries * (8 * (1 << (num_vars - log_cols)) + 32 * (log_cols + log_blowup)) + 2 * 8 * (1 << log_cols)
+
+
+def long_log_cols(num_vars, log_blowup, queries, max_log_len=LONG_MAX_LOG_LEN):
+    """the log_cols in 0 .. min(num_vars, max_log_len - log_blowup) with the smallest opening (ties: the smaller)"""
+    return min(range(min(num_vars, max_log_len - log_blowup) + 1), key=lambda c: (opening_bytes(num_vars, c, log_blowup, queries), c))
+
+
 # ---- hashing (host) --------------------------------------------------------------------------------------------------
 
 def column_digest(field, values):
@@ -110,6 +126,13 @@ def rs_encode_rows(ctx, poly, log_cols, log_blowup):
     """sc_rs_encode_rows: the codeword matrix of `poly`'s table, row-major, a device table of 2^(n + log_blowup) words"""
     h = voidp()
     ctx.check(ctx.lib.sc_rs_encode_rows(ctx.h, poly.h, log_cols, log_blowup, ctypes.byref(h)))
+    return DenseMultilinearExtension(ctx, h)
+
+
+def rs_encode_rows_long(ctx, poly, log_cols, log_blowup):
+    """sc_rs_encode_rows_long: rs_encode_rows for log_cols + log_blowup up to LONG_MAX_LOG_LEN"""
+    h = voidp()
+    ctx.check(ctx.lib.sc_rs_encode_rows_long(ctx.h, poly.h, log_cols, log_blowup, ctypes.byref(h)))
     return DenseMultilinearExtension(ctx, h)
 
 
@@ -143,6 +166,19 @@ class Prover:
             ctx.check(ctx.lib.sc_ligero_commit(ctx.h, poly.h, log_cols, log_blowup, ctypes.byref(h)))
         else:
             ctx.check(ctx.lib.sc_ligero_commit_code(ctx.h, poly.h, log_cols, log_blowup, code_id, ctypes.byref(h)))
+        return cls(ctx, poly, h)
+
+    @classmethod
+    def commit_long(cls, ctx, poly, log_cols=None, log_blowup=1, queries=None):
+        """sc_ligero_commit_long: Reed-Solomon rows of up to 2^LONG_MAX_LOG_LEN words.  log_cols=None: the shape whose opening
+        of `queries` columns is smallest (long_log_cols), as far as the field's two-adicity allows"""
+        if log_cols is None:
+            if queries is None:
+                raise ValueError("commit_long chooses log_cols from the number of queries: give log_cols or queries")
+            s = two_adic_root(ctx.field.p)[0]
+            log_cols = long_log_cols(poly.num_vars(), log_blowup, queries, min(LONG_MAX_LOG_LEN, s))
+        h = voidp()
+        ctx.check(ctx.lib.sc_ligero_commit_long(ctx.h, poly.h, log_cols, log_blowup, ctypes.byref(h)))
         return cls(ctx, poly, h)
 
     def root(self):

@@ -23,6 +23,12 @@ integers: Goldilocks products do not fit int64), at (20, 10, 1) only.
         2^64 - 59 (which Reed-Solomon cannot serve), and the expander commit on both fields; writes <out>/expander_timing.json and
         <out>/expander_summary.md: the encode time, its ratio to rs_encode_rows_kernel at the same shape in the same run, and its
         rate on 24 * 2^n bytes against the 6.29 TB/s copy rate.  The default --code rs is everything above, unchanged.
+  python tools/ligero_timing.py --long [--reps 7]
+        rows longer than the LDS (sc_rs_encode_rows_long) at (n, c, rho) = (24, 16, 1), (26, 17, 1),
+        (26, 16, 2), (28, 17, 1), each beside the in-LDS shape of the same n and rho (c = 14 - rho), in ONE child process: the
+        device time of the two launches and their rate on the modelled bytes, their sum against rs_encode_rows_kernel,
+        column_leaf_kernel at both widths, the commit's wall time, and the wall time and size of a 64-column opening at both
+        widths; writes <out>/ligero_long_timing.json and <out>/ligero_long_summary.md.
 """
 import argparse
 import glob
@@ -42,6 +48,7 @@ COPY_BPS = 6.29e12          # the measured copy rate of the chip (read + write b
 MERKLE_LEAF_CPS = 2.7e10    # merkle_leaf_kernel at n = 28, profiles/pcs_summary.md
 OPENINGS = 64
 XC_SHAPES = ((20, 10), (24, 12), (26, 13))
+LONG_SHAPES = ((24, 16, 1), (26, 17, 1), (26, 16, 2), (28, 17, 1))
 P59 = 2**64 - 59
 
 
@@ -144,6 +151,71 @@ def run_expander(reps):
     return out
 
 
+def run_long(reps):
+    """--long: per shape the long encoder and commitment beside the in-LDS ones of the same n and rho"""
+    import random
+    sys.path.insert(0, ROOT)
+    from __graft_entry__ import load_package
+    pkg = load_package()
+    lp = pkg.ligero_pcs
+    ctx = pkg.Context(pkg.Field(pkg.GOLDILOCKS), device=0)
+    out = {"step": "long", "shapes": {}}
+    for n, c, rho in LONG_SHAPES:
+        t = pkg.DenseMultilinearExtension.generate(ctx, 0x11CE0000 + n, n)
+        row = {}
+        for tag, cc, encode, commit in (("long", c, lp.rs_encode_rows_long, lp.Prover.commit_long), ("short", 14 - rho, lp.rs_encode_rows, lp.Prover.commit)):
+            walls, log = _timed(ctx, lambda: encode(ctx, t, cc, rho), reps)
+            enc = [r for r in log if r["kind"] in ("rs_long", "rs_encode")]
+            cw, clog = _timed(ctx, lambda: commit(ctx, t, cc, rho).close(), max(2, reps // 3))
+            prover = commit(ctx, t, cc, rho)
+            rng = random.Random(n)
+            cols = [rng.randrange(1 << (cc + rho)) for _ in range(OPENINGS)]
+            ow, olog = _timed(ctx, lambda: prover.open_columns(cols), max(2, reps // 3))
+            prover.close()
+            row[tag] = {"log_cols": cc, "encode_wall_ms": statistics.median(walls) * 1e3,
+                        "launches": [{"kf": r["kf"], "ks": r["ks"], "ms": r["ms"], "bytes": r["bytes_read"] + r["bytes_written"]} for r in enc],
+                        "encode_device_ms": sum(r["ms"] for r in enc),
+                        "commit_wall_ms": statistics.median(cw) * 1e3,
+                        "commit_encode_ms": sum(r["ms"] for r in clog if r["kind"] in ("rs_long", "rs_encode")),
+                        "leaf_ms": sum(r["ms"] for r in clog if r["kind"] == "ligero"),
+                        "tree_ms": sum(r["ms"] for r in clog if r["kind"] == "merkle"),
+                        "open_wall_ms": statistics.median(ow) * 1e3, "open_device_ms": sum(r["ms"] for r in olog),
+                        "open_bytes": lp.opening_bytes(n, cc, rho, OPENINGS)}
+        out["shapes"]["%d,%d,%d" % (n, c, rho)] = row
+        del t
+    return out
+
+
+def long_summary(res):
+    lines = ["# Ligero rows longer than the LDS on one MI355X: the four-step transform beside the in-LDS encoder", "",
+             "Measured by `python tools/ligero_timing.py --long --reps %d`: every figure, the in-LDS columns included, comes from ONE "
+             "process.  Goldilocks, tables from `sc_table_generate`.  Device times: HIP events of the launch log, option `time_kernels`; "
+             "wall times: medians after two warm-up calls.  Modelled bytes: the column step reads 8·2^n and writes 8·2^(n+rho), the row "
+             "step reads and writes 8·2^(n+rho); the in-LDS encoder reads 8·2^n and writes 8·2^(n+rho).  The yardstick is the chip's "
+             "measured copy rate, 6.29 TB/s." % res["reps"], "",
+             "## The encoder", "",
+             "| (n, c, rho) | a + b | column step ms | TB/s | row step ms | TB/s | sum ms | in-LDS (c = 14 - rho) ms | long / in-LDS |", "|---|---|---|---|---|---|---|---|---|"]
+    shapes = res["steps"]["long"]["shapes"]
+    for key, row in shapes.items():
+        lo, sh = row["long"], row["short"]
+        s0, s1 = lo["launches"]
+        lines.append("| (%s) | %d + %d | %.3f | %.2f | %.3f | %.2f | %.3f | %.3f | %.2f |" % (
+            key.replace(",", ", "), s0["ks"], s1["ks"], s0["ms"], s0["bytes"] / (s0["ms"] * 1e-3) / 1e12, s1["ms"],
+            s1["bytes"] / (s1["ms"] * 1e-3) / 1e12, lo["encode_device_ms"], sh["encode_device_ms"], lo["encode_device_ms"] / sh["encode_device_ms"]))
+    lines += ["", "## The commitment and a %d-column opening, at both widths" % OPENINGS, "",
+              "| (n, c, rho) | width | commit wall ms | encode ms | column_leaf_kernel ms | tree ms | open wall ms | open device ms | opening bytes |",
+              "|---|---|---|---|---|---|---|---|---|"]
+    for key, row in shapes.items():
+        for tag in ("long", "short"):
+            k = row[tag]
+            lines.append("| (%s) | c = %d | %.3f | %.3f | %.3f | %.3f | %.3f | %.3f | %d |" % (
+                key.replace(",", ", "), k["log_cols"], k["commit_wall_ms"], k["commit_encode_ms"], k["leaf_ms"], k["tree_ms"], k["open_wall_ms"],
+                k["open_device_ms"], k["open_bytes"]))
+    if res.get("notes"):
+        lines += ["", "## What binds", ""] + res["notes"]
+    return "\n".join(lines) + "\n"
+
+
 def expander_summary(res):
     lines = ["# Expander code 1 on one MI355X: sc_xc_encode_rows beside sc_rs_encode_rows", "",
              "Measured by `python tools/ligero_timing.py --code expander --reps %d`: every row below, the Reed-Solomon column included, "
@@ -220,7 +292,8 @@ def summary(res):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--step", choices=("encode", "commit", "expander"))
+    ap.add_argument("--step", choices=("encode", "commit", "expander", "long"))
+    ap.add_argument("--long", action="store_true", help="rows longer than the LDS beside the in-LDS encoder (ligero_long_summary.md)")
     ap.add_argument("--code", choices=("rs", "expander"), default="rs", help="expander: the expander code beside Reed-Solomon (expander_summary.md)")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--limit", type=int, default=600, help="seconds each child step may take")
@@ -232,6 +305,24 @@ def main():
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
     path = os.path.join(args.out, "ligero_timing.json")
+    if args.long and not args.step:
+        long_path = os.path.join(args.out, "ligero_long_timing.json")
+        if args.summary_only:
+            with open(long_path) as fh:
+                res = json.load(fh)
+        else:
+            cmd = [sys.executable, os.path.abspath(__file__), "--step", "long", "--reps", str(args.reps)]
+            p = subprocess.run(cmd, capture_output=True, text=True, timeout=args.limit)
+            if p.returncode != 0:
+                print(json.dumps({"step": "long", "error": "exit status %d" % p.returncode, "stderr": p.stderr[-2000:]}))
+                sys.exit(1)
+            res = {"reps": args.reps, "steps": {"long": json.loads(p.stdout.strip().splitlines()[-1])}}
+            with open(long_path, "w") as fh:
+                json.dump(res, fh, indent=1)
+        with open(os.path.join(args.out, "ligero_long_summary.md"), "w") as fh:
+            fh.write(long_summary(res))
+        print(json.dumps({k: {t: round(v["encode_device_ms"], 3) for t, v in row.items()} for k, row in res["steps"]["long"]["shapes"].items()}))
+        return
     if args.summary_only or args.cpu_only:
         with open(path) as fh:
             res = json.load(fh)
@@ -243,7 +334,8 @@ def main():
             fh.write(summary(res))
         return
     if args.step:
-        print(json.dumps(run_expander(args.reps) if args.step == "expander" else run_step(args.step, args.reps)))
+        runs = {"expander": run_expander, "long": run_long}
+        print(json.dumps(runs[args.step](args.reps) if args.step in runs else run_step(args.step, args.reps)))
         return
     if args.code == "expander":
         cmd = [sys.executable, os.path.abspath(__file__), "--step", "expander", "--reps", str(args.reps)]
