@@ -240,6 +240,12 @@ int sc_ctx_kernel_time(sc_ctx* ctx, double out[2], int reset);
                                 * words): kf = 0 the column step, rs_long_column_kernel (ks = a; reads the table, 8 * 2^n bytes, writes the codewords,
                                 * 8 * 2^(n + log_blowup)), kf = 1 the row step, rs_long_row_kernel (ks = b; reads and writes the codewords in place);
                                 * a + b = log_cols + log_blowup, log_in = n */
+#define SC_KIND_XC_LONG 23     /* the launches of a long expander-code row (sc_xc_encode_rows_long / sc_ligero_commit_code_long, log_cols 14 .. 23;
+                                * kernels/expander_long.hpp): kf = 0 xc_long_copy_kernel, the systematic part (ks = log_cols; reads and writes
+                                * 8 * 2^n bytes); kf = 1 xc_long_down_kernel, one per level kept in global memory, ks = lm = log2 of the level's
+                                * message (reads 8 * R * 2^lm, writes 8 * R * 2^(lm-2), R = 2^(n - log_cols) rows); kf = 2 xc_long_inner_kernel, the
+                                * code below them in LDS (ks = lm_i = 12 or 13; reads and writes 8 * R * 2^lm_i); kf = 3 xc_long_up_kernel, one per
+                                * global level (reads and writes 8 * R * 2^(lm-1)); log_in = n */
 typedef struct sc_launch_record {
   int32_t kind;           /* SC_KIND_* */
   int32_t kf, ks;         /* variables folded / rounds served (meaning per kind above) */
@@ -587,6 +593,16 @@ int sc_xc_encode_rows(sc_ctx* ctx, const sc_table* t, size_t log_cols, sc_table*
  * sc_ligero_root / shape / combine_rows / open_columns / destroy serve it unchanged. */
 int sc_ligero_commit_code(sc_ctx* ctx, const sc_table* t, size_t log_cols, size_t log_blowup, int code, sc_ligero** out);
 int sc_ligero_code(const sc_ligero* lg, int* code);
+/* Expander-code rows longer than the LDS of a CU: the same code and the same commitment for log_cols up to 23 (codewords of up
+ * to 2^24 words).  Above 13 the largest levels of the recursion run as launches over the codeword matrix in global memory
+ * (kernels/expander_long.hpp; SC_KIND_XC_LONG records: a copy, one launch per such level on the way down, the in-LDS code
+ * below them, one launch per level on the way up); up to 13 both run the single launch of the calls above
+ * (SC_KIND_XC_ENCODE).  Every other limit and every error is as above, with SC_ERR_UNSUPPORTED for log_cols > 23 (the message
+ * names 2^24: there the stored tree is 1 GiB).  sc_ligero_commit_code_long(SC_CODE_RS) is sc_ligero_commit_long itself; with
+ * SC_CODE_EXPANDER the commitment is an ordinary sc_ligero of that code: sc_ligero_root / shape / code / combine_rows /
+ * open_columns / destroy serve it unchanged. */
+int sc_xc_encode_rows_long(sc_ctx* ctx, const sc_table* t, size_t log_cols, sc_table** out);
+int sc_ligero_commit_code_long(sc_ctx* ctx, const sc_table* t, size_t log_cols, size_t log_blowup, int code, sc_ligero** out);
 
 /* ---- gkr_protocol::circuit::Circuit on the device, and the whole GKR prover over it ----------------------------------
  * A circuit lives on ONE context of one device and one rank: sharded contexts (world > 1) and multi-device handles get

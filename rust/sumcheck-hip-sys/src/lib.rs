@@ -510,4 +510,15 @@ extern "C" {
         out: *mut *mut sc_ligero,
     ) -> c_int;
     pub fn sc_ligero_code(lg: *const sc_ligero, code: *mut c_int) -> c_int;
+    /// sc_xc_encode_rows for log_cols up to 23: above 13 the largest levels run as launches over global memory (SC_KIND_XC_LONG)
+    pub fn sc_xc_encode_rows_long(ctx: *mut sc_ctx, t: *const sc_table, log_cols: usize, out: *mut *mut sc_table) -> c_int;
+    /// sc_ligero_commit_code over the long row encoders: SC_CODE_RS is sc_ligero_commit_long, SC_CODE_EXPANDER needs log_blowup = 1
+    pub fn sc_ligero_commit_code_long(
+        ctx: *mut sc_ctx,
+        t: *const sc_table,
+        log_cols: usize,
+        log_blowup: usize,
+        code: c_int,
+        out: *mut *mut sc_ligero,
+    ) -> c_int;
 }

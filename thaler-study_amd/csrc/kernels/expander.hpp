@@ -21,7 +21,8 @@
 //            defined by gathers alone - nothing is stored, nothing is scattered.  The relative distance of the recursive
 //            code is NOT proved; the base code's distance is exact.
 // Layout     In place, Enc_m at [o, o + 2m): x at o; y at o + m and z = Enc_(m/4)(y) over it at [o + m, o + 3m/2); v at o + 3m/2.
-// Limits     c <= 13 (one codeword, 128 KiB, in the LDS of a CU); n + 1 <= 29; p > 63; one device, one rank.
+// Limits     c <= 13 (one codeword, 128 KiB, in the LDS of a CU; expander_long.hpp serves c up to 23); n + 1 <= 29; p > 63; one
+//            device, one rank.
 //
 // xc_encode_rows_kernel: a block owns 2^tile_log codeword words in LDS - one row, or several when L < 2^12.  A "down" sweep
 // writes each level's y behind its input (32 gathered products per output, accumulated unreduced), one dense product with the
@@ -135,6 +136,35 @@ SC_HD void xc_up_item(const F& f, u64* tile, int log_len, u32 o, int lm, u32 it)
 #if defined(__HIPCC__)
 namespace sc {
 
+// The sweeps over an LDS image of 2^log_rows codeword rows of 2^(c+1) words whose messages are in place: every level's down step,
+// the base product, every level's up step, a barrier behind each.  The caller's barrier stands between its loads and this.
+template <class F>
+__device__ __forceinline__ void xc_sweeps(const F& f, u64* lds, const u64* kinv, int c, int log_rows) {
+  const int log_len = c + 1;
+  const int levels = xc_levels(c);
+  u32 o = 0;
+  for (int l = 0; l < levels; ++l) {
+    const int lm = c - 2 * l;
+    const u32 items = 1u << (log_rows + lm - 2);
+    for (u32 it = threadIdx.x; it < items; it += blockDim.x) xc_down_item(f, lds, log_len, o, lm, it);
+    __syncthreads();
+    o += 1u << lm;
+  }
+  {
+    const int log_mb = c - 2 * levels;
+    const u32 items = 1u << (log_rows + log_mb);
+    for (u32 it = threadIdx.x; it < items; it += blockDim.x) xc_base_item(f, lds, kinv, log_len, o, log_mb, it);
+    __syncthreads();
+  }
+  for (int l = levels - 1; l >= 0; --l) {
+    const int lm = c - 2 * l;
+    o -= 1u << lm;
+    const u32 items = 1u << (log_rows + lm - 1);
+    for (u32 it = threadIdx.x; it < items; it += blockDim.x) xc_up_item(f, lds, log_len, o, lm, it);
+    __syncthreads();
+  }
+}
+
 // One block encodes 2^(tile_log - c - 1) consecutive rows: their messages are one contiguous run of w, their codewords one
 // contiguous run of E.  inv: the kXcInvWords inverses.  vec: both runs are 16-byte aligned and a row is at least two words.
 template <class F>
@@ -158,28 +188,7 @@ __global__ __launch_bounds__(kXcMaxThreads) void xc_encode_rows_kernel(F f, cons
   }
   if (threadIdx.x < (u32)kXcInvWords) kinv[threadIdx.x] = inv[threadIdx.x];
   __syncthreads();
-  const int levels = xc_levels(c);
-  u32 o = 0;
-  for (int l = 0; l < levels; ++l) {
-    const int lm = c - 2 * l;
-    const u32 items = 1u << (log_rows + lm - 2);
-    for (u32 it = threadIdx.x; it < items; it += blockDim.x) xc_down_item(f, lds, log_len, o, lm, it);
-    __syncthreads();
-    o += 1u << lm;
-  }
-  {
-    const int log_mb = c - 2 * levels;
-    const u32 items = 1u << (log_rows + log_mb);
-    for (u32 it = threadIdx.x; it < items; it += blockDim.x) xc_base_item(f, lds, kinv, log_len, o, log_mb, it);
-    __syncthreads();
-  }
-  for (int l = levels - 1; l >= 0; --l) {
-    const int lm = c - 2 * l;
-    o -= 1u << lm;
-    const u32 items = 1u << (log_rows + lm - 1);
-    for (u32 it = threadIdx.x; it < items; it += blockDim.x) xc_up_item(f, lds, log_len, o, lm, it);
-    __syncthreads();
-  }
+  xc_sweeps(f, lds, kinv, c, log_rows);
   // out: the whole tile, one coalesced run
   const u32 out_words = 1u << tile_log;
   if (vec) {

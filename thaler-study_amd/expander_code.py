@@ -19,6 +19,7 @@ D_A = 8
 D_B = 16
 BASE_MAX = 32          # messages of up to 32 words take the base code
 MAX_LOG_COLS = 13      # the device encoder keeps one codeword of 2^14 words in the LDS of a CU
+LONG_MAX_LOG_COLS = 23 # sc_xc_encode_rows_long: above 13 the largest levels run through global memory; at 2^24 the tree is 1 GiB
 MIN_MODULUS = 64       # the base matrices invert 1 .. 63
 
 

@@ -29,7 +29,10 @@ parameter: DESIGN.md gives the book's soundness expression for it; no security l
 code="expander" (sc_xc_encode_rows, sc_ligero_commit_code) replaces Reed-Solomon by the linear-time
 code of expander_code.py - systematic, rate 1/2 (log_blowup = 1), additions and multiplications by constants only - for fields
 without two-adicity such as 2^64 - 59: any p > 63, log_cols <= 13.  Everything above the encoder is the same; Enc(u)[j] is then
-entry j of expander_code.encode(u).  The distance of that code is not proved."""
+entry j of expander_code.encode(u).  The distance of that code is not proved.  xc_encode_rows_long and
+Prover.commit_long(code="expander") (sc_xc_encode_rows_long, sc_ligero_commit_code_long) serve
+log_cols up to expander_code.LONG_MAX_LOG_COLS = 23; the Verifier's host encoding of the two combined rows then costs seconds
+at log_cols 14 - 15 and far more above."""
 import ctypes
 import hashlib
 
@@ -143,6 +146,13 @@ def xc_encode_rows(ctx, poly, log_cols):
     return DenseMultilinearExtension(ctx, h)
 
 
+def xc_encode_rows_long(ctx, poly, log_cols):
+    """sc_xc_encode_rows_long: xc_encode_rows for log_cols up to expander_code.LONG_MAX_LOG_COLS"""
+    h = voidp()
+    ctx.check(ctx.lib.sc_xc_encode_rows_long(ctx.h, poly.h, log_cols, ctypes.byref(h)))
+    return DenseMultilinearExtension(ctx, h)
+
+
 class Prover:
     """sc_ligero_*: the commitment to a device table (borrowed: kept alive by the prover) and the replies of an opening"""
 
@@ -169,16 +179,21 @@ class Prover:
         return cls(ctx, poly, h)
 
     @classmethod
-    def commit_long(cls, ctx, poly, log_cols=None, log_blowup=1, queries=None):
-        """sc_ligero_commit_long: Reed-Solomon rows of up to 2^LONG_MAX_LOG_LEN words.  log_cols=None: the shape whose opening
-        of `queries` columns is smallest (long_log_cols), as far as the field's two-adicity allows"""
+    def commit_long(cls, ctx, poly, log_cols=None, log_blowup=1, queries=None, code="rs"):
+        """sc_ligero_commit_long / sc_ligero_commit_code_long: rows of up to 2^LONG_MAX_LOG_LEN codeword words.  log_cols=None: the
+        shape whose opening of `queries` columns is smallest (long_log_cols) - for Reed-Solomon as far as the field's two-adicity
+        allows; the expander code has no such bound"""
+        code_id = _code_id(code)
         if log_cols is None:
             if queries is None:
                 raise ValueError("commit_long chooses log_cols from the number of queries: give log_cols or queries")
-            s = two_adic_root(ctx.field.p)[0]
+            s = two_adic_root(ctx.field.p)[0] if code == "rs" else LONG_MAX_LOG_LEN
             log_cols = long_log_cols(poly.num_vars(), log_blowup, queries, min(LONG_MAX_LOG_LEN, s))
         h = voidp()
-        ctx.check(ctx.lib.sc_ligero_commit_long(ctx.h, poly.h, log_cols, log_blowup, ctypes.byref(h)))
+        if code == "rs":
+            ctx.check(ctx.lib.sc_ligero_commit_long(ctx.h, poly.h, log_cols, log_blowup, ctypes.byref(h)))
+        else:
+            ctx.check(ctx.lib.sc_ligero_commit_code_long(ctx.h, poly.h, log_cols, log_blowup, code_id, ctypes.byref(h)))
         return cls(ctx, poly, h)
 
     def root(self):

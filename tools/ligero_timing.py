@@ -29,6 +29,12 @@ integers: Goldilocks products do not fit int64), at (20, 10, 1) only.
         device time of the two launches and their rate on the modelled bytes, their sum against rs_encode_rows_kernel,
         column_leaf_kernel at both widths, the commit's wall time, and the wall time and size of a 64-column opening at both
         widths; writes <out>/ligero_long_timing.json and <out>/ligero_long_summary.md.
+  python tools/ligero_timing.py --long --code expander [--reps 7]
+        expander-code rows longer than the LDS (sc_xc_encode_rows_long) at (n, c) = (24, 16), (26, 17),
+        (28, 17) over Goldilocks and 2^64 - 59, each beside the in-LDS expander shape (c = 13) of the same n, in ONE child process:
+        the device time of every launch, the gathers per second of the level launches, their sum against xc_encode_rows_kernel,
+        column_leaf_kernel at both widths, the commit's wall time, and the wall time and size of a 64-column opening at both
+        widths; writes <out>/expander_long_timing.json and <out>/expander_long_summary.md.
 """
 import argparse
 import glob
@@ -49,6 +55,8 @@ MERKLE_LEAF_CPS = 2.7e10    # merkle_leaf_kernel at n = 28, profiles/pcs_summary
 OPENINGS = 64
 XC_SHAPES = ((20, 10), (24, 12), (26, 13))
 LONG_SHAPES = ((24, 16, 1), (26, 17, 1), (26, 16, 2), (28, 17, 1))
+XC_LONG_SHAPES = ((24, 16), (26, 17), (28, 17))
+XC_LONG_KERNELS = {0: "copy", 1: "down", 2: "inner", 3: "up"}
 P59 = 2**64 - 59
 
 
@@ -186,6 +194,88 @@ def run_long(reps):
     return out
 
 
+def run_xc_long(reps):
+    """--long --code expander: per shape and field the long expander encoder and commitment beside the in-LDS ones (c = 13)"""
+    import random
+    sys.path.insert(0, ROOT)
+    from __graft_entry__ import load_package
+    pkg = load_package()
+    lp = pkg.ligero_pcs
+    out = {"step": "xc_long", "shapes": {}}
+    ctxs = {"gold": pkg.Context(pkg.Field(pkg.GOLDILOCKS), device=0), "p59": pkg.Context(pkg.Field(P59), device=0)}
+    short_c = pkg.expander_code.MAX_LOG_COLS
+    for n, c in XC_LONG_SHAPES:
+        row = {}
+        for name, ctx in ctxs.items():
+            t = pkg.DenseMultilinearExtension.generate(ctx, 0x11CE0000 + n, n)
+            for tag, cc, encode, commit in (("long", c, lp.xc_encode_rows_long, lp.Prover.commit_long), ("short", short_c, lp.xc_encode_rows, lp.Prover.commit)):
+                walls, log = _timed(ctx, lambda: encode(ctx, t, cc), reps)
+                enc = [r for r in log if r["kind"] in ("xc_long", "xc_encode")]
+                cw, clog = _timed(ctx, lambda: commit(ctx, t, cc, 1, code="expander").close(), max(2, reps // 3))
+                prover = commit(ctx, t, cc, 1, code="expander")
+                rng = random.Random(n)
+                cols = [rng.randrange(2 << cc) for _ in range(OPENINGS)]
+                ow, olog = _timed(ctx, lambda: prover.open_columns(cols), max(2, reps // 3))
+                prover.close()
+                row["%s_%s" % (tag, name)] = {
+                    "log_cols": cc, "encode_wall_ms": statistics.median(walls) * 1e3,
+                    "launches": [{"kind": r["kind"], "kf": r["kf"], "ks": r["ks"], "ms": r["ms"], "bytes_read": r["bytes_read"],
+                                  "bytes_written": r["bytes_written"]} for r in enc],
+                    "encode_device_ms": sum(r["ms"] for r in enc),
+                    "commit_wall_ms": statistics.median(cw) * 1e3,
+                    "commit_encode_ms": sum(r["ms"] for r in clog if r["kind"] in ("xc_long", "xc_encode")),
+                    "leaf_ms": sum(r["ms"] for r in clog if r["kind"] == "ligero"),
+                    "tree_ms": sum(r["ms"] for r in clog if r["kind"] == "merkle"),
+                    "open_wall_ms": statistics.median(ow) * 1e3, "open_device_ms": sum(r["ms"] for r in olog),
+                    "open_bytes": lp.opening_bytes(n, cc, 1, OPENINGS)}
+            del t
+        out["shapes"]["%d,%d" % (n, c)] = row
+    return out
+
+
+def xc_long_summary(res):
+    fields = (("gold", "Goldilocks"), ("p59", "2^64 - 59"))
+    lines = ["# Expander-code rows longer than the LDS on one MI355X: levels through global memory beside the in-LDS encoder", "",
+             "Measured by `python tools/ligero_timing.py --long --code expander --reps %d`: every figure, the in-LDS (c = 13) columns "
+             "included, comes from ONE process.  Tables from `sc_table_generate`.  Device times: HIP events of the launch log, option "
+             "`time_kernels`; wall times: medians after two warm-up calls.  A level launch gathers 8·R·2^lm words of 8 bytes (down: 32 per "
+             "output, R·2^(lm-2) outputs; up: 16 per output, R·2^(lm-1) outputs); the gather rates below are those counts over the "
+             "launch's device time and are measurements of this run, not figures from a data sheet." % res["reps"], "",
+             "## The launches", "",
+             "| (n, c) | field | launch | lm | device ms | bytes read + written | G gathers/s |", "|---|---|---|---|---|---|---|"]
+    shapes = res["steps"]["xc_long"]["shapes"]
+    for key, row in shapes.items():
+        n = int(key.split(",")[0])
+        for name, label in fields:
+            lo = row["long_" + name]
+            for r in lo["launches"]:
+                gathers = (8 << (n - lo["log_cols"] + r["ks"])) if r["kf"] in (1, 3) else 0
+                lines.append("| (%s) | %s | %s | %d | %.3f | %d | %s |" % (
+                    key.replace(",", ", "), label, XC_LONG_KERNELS[r["kf"]], r["ks"], r["ms"], r["bytes_read"] + r["bytes_written"],
+                    "%.1f" % (gathers / (r["ms"] * 1e-3) / 1e9) if gathers else "-"))
+    lines += ["", "## The encoder: all launches against xc_encode_rows_kernel at c = 13", "",
+              "| (n, c) | field | long: launches | long: device ms | wall ms | in-LDS (c = 13) device ms | wall ms | long / in-LDS |", "|---|---|---|---|---|---|---|---|"]
+    for key, row in shapes.items():
+        for name, label in fields:
+            lo, sh = row["long_" + name], row["short_" + name]
+            lines.append("| (%s) | %s | %d | %.3f | %.3f | %.3f | %.3f | %.2f |" % (
+                key.replace(",", ", "), label, len(lo["launches"]), lo["encode_device_ms"], lo["encode_wall_ms"], sh["encode_device_ms"],
+                sh["encode_wall_ms"], lo["encode_device_ms"] / sh["encode_device_ms"]))
+    lines += ["", "## The commitment and a %d-column opening, at both widths" % OPENINGS, "",
+              "| (n, c) | field | width | commit wall ms | encode ms | column_leaf_kernel ms | tree ms | open wall ms | open device ms | opening bytes |",
+              "|---|---|---|---|---|---|---|---|---|---|"]
+    for key, row in shapes.items():
+        for name, label in fields:
+            for tag in ("long", "short"):
+                k = row["%s_%s" % (tag, name)]
+                lines.append("| (%s) | %s | c = %d | %.3f | %.3f | %.3f | %.3f | %.3f | %.3f | %d |" % (
+                    key.replace(",", ", "), label, k["log_cols"], k["commit_wall_ms"], k["commit_encode_ms"], k["leaf_ms"], k["tree_ms"],
+                    k["open_wall_ms"], k["open_device_ms"], k["open_bytes"]))
+    if res.get("notes"):
+        lines += ["", "## What binds", ""] + res["notes"]
+    return "\n".join(lines) + "\n"
+
+
 def long_summary(res):
     lines = ["# Ligero rows longer than the LDS on one MI355X: the four-step transform beside the in-LDS encoder", "",
              "Measured by `python tools/ligero_timing.py --long --reps %d`: every figure, the in-LDS columns included, comes from ONE "
@@ -292,7 +382,7 @@ def summary(res):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--step", choices=("encode", "commit", "expander", "long"))
+    ap.add_argument("--step", choices=("encode", "commit", "expander", "long", "xc_long"))
     ap.add_argument("--long", action="store_true", help="rows longer than the LDS beside the in-LDS encoder (ligero_long_summary.md)")
     ap.add_argument("--code", choices=("rs", "expander"), default="rs", help="expander: the expander code beside Reed-Solomon (expander_summary.md)")
     ap.add_argument("--reps", type=int, default=10)
@@ -306,22 +396,23 @@ def main():
     os.makedirs(args.out, exist_ok=True)
     path = os.path.join(args.out, "ligero_timing.json")
     if args.long and not args.step:
-        long_path = os.path.join(args.out, "ligero_long_timing.json")
+        step, stem, render = ("xc_long", "expander_long", xc_long_summary) if args.code == "expander" else ("long", "ligero_long", long_summary)
+        long_path = os.path.join(args.out, stem + "_timing.json")
         if args.summary_only:
             with open(long_path) as fh:
                 res = json.load(fh)
         else:
-            cmd = [sys.executable, os.path.abspath(__file__), "--step", "long", "--reps", str(args.reps)]
+            cmd = [sys.executable, os.path.abspath(__file__), "--step", step, "--reps", str(args.reps)]
             p = subprocess.run(cmd, capture_output=True, text=True, timeout=args.limit)
             if p.returncode != 0:
-                print(json.dumps({"step": "long", "error": "exit status %d" % p.returncode, "stderr": p.stderr[-2000:]}))
+                print(json.dumps({"step": step, "error": "exit status %d" % p.returncode, "stderr": p.stderr[-2000:]}))
                 sys.exit(1)
-            res = {"reps": args.reps, "steps": {"long": json.loads(p.stdout.strip().splitlines()[-1])}}
+            res = {"reps": args.reps, "steps": {step: json.loads(p.stdout.strip().splitlines()[-1])}}
             with open(long_path, "w") as fh:
                 json.dump(res, fh, indent=1)
-        with open(os.path.join(args.out, "ligero_long_summary.md"), "w") as fh:
-            fh.write(long_summary(res))
-        print(json.dumps({k: {t: round(v["encode_device_ms"], 3) for t, v in row.items()} for k, row in res["steps"]["long"]["shapes"].items()}))
+        with open(os.path.join(args.out, stem + "_summary.md"), "w") as fh:
+            fh.write(render(res))
+        print(json.dumps({k: {t: round(v["encode_device_ms"], 3) for t, v in row.items()} for k, row in res["steps"][step]["shapes"].items()}))
         return
     if args.summary_only or args.cpu_only:
         with open(path) as fh:
@@ -334,7 +425,7 @@ def main():
             fh.write(summary(res))
         return
     if args.step:
-        runs = {"expander": run_expander, "long": run_long}
+        runs = {"expander": run_expander, "long": run_long, "xc_long": run_xc_long}
         print(json.dumps(runs[args.step](args.reps) if args.step in runs else run_step(args.step, args.reps)))
         return
     if args.code == "expander":
