@@ -1,13 +1,17 @@
 """A pure-Python restatement of "expander code 1" (thaler-study_amd/csrc/kernels/expander.hpp),
-test-local: nothing here imports the package.  Everything is in CANONICAL integers.
+test-local: nothing here imports the package.  Everything is in CANONICAL integers.  What a commitment has above its row code -
+the digests, the combinations, the prover - is tests/ligero_ref.py's, under the same names here.
 
   mix, key, coef, frnd, perm            the hashes that define the two sparse maps of a level
   base_matrix(m, p)                     the Cauchy matrix K[j][k] = 1 / (j + k + 1) of the base code
   encode(x, p)                          Enc_m(x), a list of 2 m values (m a power of two)
   encode_rows(table, c, p)              the codeword matrix of a table's rows of 2^c entries
   known_answer(p, c)                    (E[m], E[2m-1], sha256 hex) of the message x[i] = 3 i + 1
-  RefProver                             ligero_ref.RefProver's interface over this code (log_blowup = 1)"""
+  RefProver                             ligero_ref.RefProver over this code (log_blowup = 1)"""
 import hashlib
+
+import ligero_ref
+from ligero_ref import column_leaf, combine, eq_weights, root_of, tree_levels   # noqa: F401 (expander_ref.root_of and the rest)
 
 M64 = 2**64 - 1
 SEED = 0x4272616B65646F77
@@ -108,49 +112,8 @@ def known_answer(p, c):
     return E[m], E[2 * m - 1], digest_of(E)
 
 
-# ---- the commitment over this code: the digests, combinations and openings of ligero_ref, restated ----------------------
-
-def column_leaf(E, j):
-    return hashlib.sha256(b"".join(int(row[j]).to_bytes(8, "little") for row in E)).digest()
-
-
-def tree_levels(leaves):
-    lev = [list(leaves)]
-    while len(lev[-1]) > 1:
-        prev = lev[-1]
-        lev.append([hashlib.sha256(prev[2 * k] + prev[2 * k + 1]).digest() for k in range(len(prev) // 2)])
-    return lev
-
-
-def root_of(E):
-    return tree_levels([column_leaf(E, j) for j in range(len(E[0]))])[-1][0]
-
-
-def eq_weights(point, p):
-    w = [1]
-    for r in point:
-        w = [x * (1 - r) % p for x in w] + [x * r % p for x in w]
-    return w
-
-
-def combine(table, c, weights, p):
-    C = 1 << c
-    return [sum(weights[i] * table[i * C + k] for i in range(len(table) // C)) % p for k in range(C)]
-
-
-class RefProver:
-    """the prover of the protocol in canonical integers"""
+class RefProver(ligero_ref.RefProver):
+    """the prover of the protocol over this code"""
 
     def __init__(self, table, c, p):
-        self.table, self.c, self.p = [int(x) for x in table], c, p
-        self.E = encode_rows(self.table, c, p)
-        self.levels = tree_levels([column_leaf(self.E, j) for j in range(2 << c)])
-
-    def root(self):
-        return self.levels[-1][0]
-
-    def combine(self, point, gamma):
-        return combine(self.table, self.c, gamma, self.p), combine(self.table, self.c, eq_weights(point[self.c:], self.p), self.p)
-
-    def open_columns(self, indices):
-        return [(j, [row[j] for row in self.E], [self.levels[l][(j >> l) ^ 1] for l in range(len(self.levels) - 1)]) for j in indices]
+        super().__init__(table, c, 1, p, E=encode_rows([int(x) for x in table], c, p))

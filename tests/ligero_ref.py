@@ -152,11 +152,12 @@ def mle_eval(table, point, p):
 
 
 class RefProver:
-    """the prover of the protocol in canonical integers"""
+    """the prover of the protocol in canonical integers.  E: the codeword matrix, a list of rows, where the row code is not
+    Reed-Solomon (tests/expander_ref.py)"""
 
-    def __init__(self, table, c, rho, p):
+    def __init__(self, table, c, rho, p, E=None):
         self.table, self.c, self.rho, self.p = [int(x) for x in table], c, rho, p
-        self.E = encode(self.table, c, rho, p)
+        self.E = encode(self.table, c, rho, p) if E is None else E
         self.levels = tree_levels([column_leaf(self.E, j) for j in range(1 << (c + rho))])
 
     def root(self):

@@ -18,6 +18,7 @@ import expander_ref as ref
 import ligero_ref
 import wide_words
 from conftest import load_package
+from ligero_common import context_cache, expect, flat, mont_np, upload
 from test_gpu_sharded import Loopback
 
 pytestmark = pytest.mark.gpu
@@ -30,46 +31,12 @@ BIG = (GOLD, P59)
 IDS = {GOLD: "gold", P59: "p59", BABYBEAR: "p2013265921", 257: "p257"}
 R64 = 2**64
 
-_ctx = {}
-
-
-def ctx_of(pkg, p):
-    """one ordinary context per field for the whole file"""
-    if p not in _ctx:
-        _ctx[p] = pkg.Context(pkg.Field(p))
-    return _ctx[p]
-
-
-def teardown_module(module):
-    for ctx in _ctx.values():
-        ctx.close()
-    _ctx.clear()
-
-
-def expect(pkg, code, fn, *needles):
-    with pytest.raises(pkg.SumcheckHipError) as ei:
-        fn()
-    assert ei.value.code == code, str(ei.value)
-    for s in needles:
-        assert s in str(ei.value), (s, str(ei.value))
-
-
-def mont_np(p, canon):
-    return (np.array([int(x) for x in canon], dtype=object) * R64 % p).astype(np.uint64)
+ctx_of, teardown_module = context_cache()
 
 
 def canon_of(p, words):
     rinv = pow(R64, -1, p)
     return [int(w) * rinv % p for w in words]
-
-
-def upload(pkg, ctx, p, canon):
-    n = len(canon).bit_length() - 1
-    return pkg.DenseMultilinearExtension.from_evaluations_vec(ctx, n, mont_np(p, canon))
-
-
-def flat(E):
-    return [x for row in E for x in row]
 
 
 def check_encode(pkg, p, r, c, table):

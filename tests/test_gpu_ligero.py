@@ -15,6 +15,7 @@ import pytest
 
 import ligero_ref as ref
 from conftest import load_package
+from ligero_common import context_cache, expect, flat, mont_np, upload
 from test_gpu_sharded import Loopback
 
 pytestmark = pytest.mark.gpu
@@ -23,44 +24,7 @@ GOLD = ref.GOLD
 P59 = 2**64 - 59
 IDS = {GOLD: "gold", ref.BABYBEAR: "p2013265921", 65537: "p65537", 257: "p257", P59: "p59"}
 
-_ctx = {}
-
-
-def ctx_of(pkg, p):
-    """one ordinary context per field for the whole file"""
-    if p not in _ctx:
-        _ctx[p] = pkg.Context(pkg.Field(p))
-    return _ctx[p]
-
-
-def teardown_module(module):
-    for ctx in _ctx.values():
-        ctx.close()
-    _ctx.clear()
-
-
-def expect(pkg, code, fn, *needles):
-    with pytest.raises(pkg.SumcheckHipError) as ei:
-        fn()
-    assert ei.value.code == code, str(ei.value)
-    for s in needles:
-        assert s in str(ei.value), (s, str(ei.value))
-
-
-def mont_np(p, canon):
-    """canonical integers -> Montgomery words, uint64"""
-    if p < 2**31:
-        return ((np.asarray(canon, dtype=np.int64) % p) * (ref.R64 % p) % p).astype(np.uint64)
-    return (np.array([int(x) for x in canon], dtype=object) * ref.R64 % p).astype(np.uint64)
-
-
-def upload(pkg, ctx, p, canon):
-    n = len(canon).bit_length() - 1
-    return pkg.DenseMultilinearExtension.from_evaluations_vec(ctx, n, mont_np(p, canon))
-
-
-def flat(E):
-    return [x for row in E for x in row]
+ctx_of, teardown_module = context_cache()
 
 
 # ---- 1. the encoding, bit for bit ------------------------------------------------------------------------------------

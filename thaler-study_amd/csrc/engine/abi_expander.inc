@@ -1,26 +1,28 @@
-// Part of sumcheck_hip.hip (included there, in order): C ABI: the Ligero-style commitment over the linear-time expander code of
-// kernels/expander.hpp, for fields without two-adicity.  Only the encoder differs from engine/abi_ligero.inc: the commitment
-// is an ordinary sc_ligero: the combinations and the openings are that file's, the tree engine/merkle.inc's.  The _long entry points
-// serve rows longer than the LDS of a CU through the launches of kernels/expander_long.hpp.
+// Part of sumcheck_hip.hip (included there, in order): the row code for fields without two-adicity - the linear-time expander
+// code of kernels/expander.hpp: its shape check, its workspace (the table of inverses) and its encoder, which serves rows longer
+// than the LDS of a CU through the launches of kernels/expander_long.hpp.  Only the encoder differs from engine/abi_ligero.inc:
+// engine/abi_row_code.inc puts both behind the same entry points, and a commitment over this code is an ordinary sc_ligero.
 
 namespace {
 
-// the checks sc_xc_encode_rows and sc_ligero_commit_code(SC_CODE_EXPANDER) share with their _long forms; *n = log2 of the table.
-// max_log: kXcMaxLogCols (a codeword in the LDS of a CU) or kXcLongMaxLogCols (the launches of kernels/expander_long.hpp)
-int xc_shape(sc_ctx* ctx, const sc_table* t, size_t log_cols, const char* what, int* n, int max_log = sc::kXcMaxLogCols) {
+// RowCode::shape of the expander code (engine/abi_row_code.inc): what a table and a shape must satisfy, in the order a caller is
+// told; *n = log2 of the table.  Short rows: a codeword in the LDS of a CU; long_rows: the launches of kernels/expander_long.hpp.
+// The rate is 1/2: an encode entry point has no log_blowup and passes 1
+int xc_shape(sc_ctx* ctx, const sc_table* t, size_t log_cols, size_t log_blowup, bool long_rows, const char* what, int* n) {
   SC_TRY(one_device_only(ctx, what));
   SC_TRY(check_table(ctx, t, what));
   *n = log2_of(t->len);
   if (log_cols > (size_t)*n) return fail(ctx, SC_ERR_ARG, "%s: log_cols = %zu exceeds the table's %d variables", what, log_cols, *n);
-  if (log_cols > (size_t)max_log)
-    return max_log == sc::kXcMaxLogCols
-               ? fail(ctx, SC_ERR_UNSUPPORTED, "%s: a codeword of 2^(%zu+1) words does not fit the LDS of a CU (at most 2^%d)", what, log_cols,
-                      sc::kXcMaxLogCols + 1)
-               : fail(ctx, SC_ERR_UNSUPPORTED, "%s: a codeword of 2^(%zu+1) words is longer than 2^%d (there the stored tree is 1 GiB)", what,
-                      log_cols, max_log + 1);
+  if (!long_rows && log_cols > (size_t)sc::kXcMaxLogCols)
+    return fail(ctx, SC_ERR_UNSUPPORTED, "%s: a codeword of 2^(%zu+1) words does not fit the LDS of a CU (at most 2^%d)", what, log_cols,
+                sc::kXcMaxLogCols + 1);
+  if (log_cols > (size_t)sc::kXcLongMaxLogCols)
+    return fail(ctx, SC_ERR_UNSUPPORTED, "%s: a codeword of 2^(%zu+1) words is longer than 2^%d (there the stored tree is 1 GiB)", what,
+                log_cols, sc::kXcLongMaxLogCols + 1);
   if (*n + 1 > 29) return fail(ctx, SC_ERR_UNSUPPORTED, "%s: 2^(%d+1) codeword words (at most 2^29)", what, *n);
   if (ctx->fp.p <= 63)
     return fail(ctx, SC_ERR_UNSUPPORTED, "%s: p = %llu: the base code inverts 1 .. 63 and needs p > 63", what, (unsigned long long)ctx->fp.p);
+  if (log_blowup != 1) return fail(ctx, SC_ERR_ARG, "%s: the expander code has rate 1/2: log_blowup is %zu, not 1", what, log_blowup);
   return SC_OK;
 }
 
@@ -54,9 +56,10 @@ int xc_encode_impl(sc_ctx* ctx, const u64* in, int n, int c, u64* E) {
   });
 }
 
-// E = the encoding of the rows of `in` at any c <= kXcLongMaxLogCols: up to kXcMaxLogCols xc_encode_impl itself, above it the
-// launches of kernels/expander_long.hpp on E - the systematic copy, the global levels down, the inner code, the global levels up
-int xc_encode_long_impl(sc_ctx* ctx, const u64* in, int n, int c, u64* E) {
+// RowCode::encode: E = the encoding of the rows of `in` at any c <= kXcLongMaxLogCols (rho is 1): up to kXcMaxLogCols xc_encode_impl
+// itself, above it the launches of kernels/expander_long.hpp on E - the systematic copy, the global levels down, the inner code,
+// the global levels up
+int xc_encode_long_impl(sc_ctx* ctx, const u64* in, int n, int c, int /*rho*/, u64* E) {
   if (c <= sc::kXcMaxLogCols) return xc_encode_impl(ctx, in, n, c, E);
   const sc::XcLongPlan pl = sc::xc_long_plan(c);
   const u64* inv = nullptr;
@@ -95,59 +98,3 @@ int xc_encode_long_impl(sc_ctx* ctx, const u64* in, int n, int c, u64* E) {
 }
 
 }  // namespace
-
-extern "C" int sc_xc_encode_rows(sc_ctx* ctx, const sc_table* t, size_t log_cols, sc_table** out) {
-  if (!ctx || !out) return SC_ERR_ARG;
-  *out = nullptr;
-  int n = 0;
-  SC_TRY(xc_shape(ctx, t, log_cols, "sc_xc_encode_rows", &n));
-  SC_TRY(set_device(ctx));
-  TableBuf E;
-  SC_TRY(E.alloc(ctx, (size_t)2 << n));
-  SC_TRY(xc_encode_impl(ctx, t->d, n, (int)log_cols, E->d));
-  *out = E.release();
-  return SC_OK;
-}
-
-extern "C" int sc_ligero_commit_code(sc_ctx* ctx, const sc_table* t, size_t log_cols, size_t log_blowup, int code, sc_ligero** out) {
-  if (!ctx || !out) return SC_ERR_ARG;
-  *out = nullptr;
-  if (code == SC_CODE_RS) return sc_ligero_commit(ctx, t, log_cols, log_blowup, out);
-  if (code != SC_CODE_EXPANDER) return fail(ctx, SC_ERR_ARG, "sc_ligero_commit_code: code %d is neither SC_CODE_RS nor SC_CODE_EXPANDER", code);
-  int n = 0;
-  SC_TRY(xc_shape(ctx, t, log_cols, "sc_ligero_commit_code", &n));
-  if (log_blowup != 1) return fail(ctx, SC_ERR_ARG, "sc_ligero_commit_code: the expander code has rate 1/2: log_blowup is %zu, not 1", log_blowup);
-  return ligero_commit_with(ctx, t, n, (int)log_cols, 1, SC_CODE_EXPANDER, [&](u64* E) { return xc_encode_impl(ctx, t->d, n, (int)log_cols, E); }, out);
-}
-
-extern "C" int sc_xc_encode_rows_long(sc_ctx* ctx, const sc_table* t, size_t log_cols, sc_table** out) {
-  if (!ctx || !out) return SC_ERR_ARG;
-  *out = nullptr;
-  int n = 0;
-  SC_TRY(xc_shape(ctx, t, log_cols, "sc_xc_encode_rows_long", &n, sc::kXcLongMaxLogCols));
-  SC_TRY(set_device(ctx));
-  TableBuf E;
-  SC_TRY(E.alloc(ctx, (size_t)2 << n));
-  SC_TRY(xc_encode_long_impl(ctx, t->d, n, (int)log_cols, E->d));
-  *out = E.release();
-  return SC_OK;
-}
-
-extern "C" int sc_ligero_commit_code_long(sc_ctx* ctx, const sc_table* t, size_t log_cols, size_t log_blowup, int code, sc_ligero** out) {
-  if (!ctx || !out) return SC_ERR_ARG;
-  *out = nullptr;
-  if (code == SC_CODE_RS) return sc_ligero_commit_long(ctx, t, log_cols, log_blowup, out);
-  if (code != SC_CODE_EXPANDER)
-    return fail(ctx, SC_ERR_ARG, "sc_ligero_commit_code_long: code %d is neither SC_CODE_RS nor SC_CODE_EXPANDER", code);
-  int n = 0;
-  SC_TRY(xc_shape(ctx, t, log_cols, "sc_ligero_commit_code_long", &n, sc::kXcLongMaxLogCols));
-  if (log_blowup != 1)
-    return fail(ctx, SC_ERR_ARG, "sc_ligero_commit_code_long: the expander code has rate 1/2: log_blowup is %zu, not 1", log_blowup);
-  return ligero_commit_with(ctx, t, n, (int)log_cols, 1, SC_CODE_EXPANDER, [&](u64* E) { return xc_encode_long_impl(ctx, t->d, n, (int)log_cols, E); }, out);
-}
-
-extern "C" int sc_ligero_code(const sc_ligero* lg, int* code) {
-  if (!lg || !code) return SC_ERR_ARG;
-  *code = lg->code;
-  return SC_OK;
-}

@@ -1,6 +1,9 @@
-// Part of sumcheck_hip.hip (included there, in order): C ABI: the Ligero-style commitment - Reed-Solomon encoding of the rows of a
-// table, the SHA-256 Merkle tree over the columns of the codeword matrix, and what an opening needs: linear combinations of
-// the rows and opened columns (kernels/ligero.hpp states the contract).  The tree above the column leaves is engine/merkle.inc's.
+// Part of sumcheck_hip.hip (included there, in order): the Ligero-style commitment - the commitment itself (sc_ligero), the
+// Reed-Solomon row code (its shape check, its workspace - the field's two-adic root, the twiddle and twist tables - and its encoder,
+// which serves rows longer than the LDS of a CU through kernels/ligero_long.hpp), the SHA-256 Merkle tree over the columns of the
+// codeword matrix, and the C ABI of what an opening needs: linear combinations of the rows and opened columns (kernels/ligero.hpp
+// states the contract).  The tree above the column leaves is engine/merkle.inc's; the entry points that encode and commit, over
+// this code or the one of engine/abi_expander.inc, are engine/abi_row_code.inc's.
 
 // A commitment: the codeword matrix E (owned) and every level of the tree over its L columns.
 struct sc_ligero {
@@ -16,35 +19,41 @@ namespace {
 
 constexpr size_t kLigeroOpenWords = (size_t)1 << 22;   // column words gathered per launch of column_open_kernel
 
-// s, the 2-adicity of p - 1, and w_max = g^((p-1)/2^s) (Montgomery) for the smallest g >= 2 with g^((p-1)/2) = -1
-void two_adic_root(const HostField& hf, int* s_out, u64* w_max) {
-  const u64 p = hf.f.p;
-  int s = 0;
-  while ((((p - 1) >> s) & 1) == 0) ++s;
-  const u64 minus_one = hf.neg(hf.one());
-  u64 g = hf.add(hf.one(), hf.one());
-  while (hf.pow(g, (p - 1) / 2) != minus_one) g = hf.add(g, hf.one());
-  *s_out = s;
-  *w_max = hf.pow(g, (p - 1) >> s);
+// s, the 2-adicity of p - 1, and w_max = g^((p-1)/2^s) (Montgomery) for the smallest g >= 2 with g^((p-1)/2) = -1: found at the
+// first call on this context and kept on it.  Everything that needs either number asks here
+struct TwoAdicRoot { int s; u64 w_max; };
+TwoAdicRoot two_adic_root(sc_ctx* ctx) {
+  if (!ctx->rs_root_known) {
+    const HostField hf(ctx->fp);
+    const u64 p = hf.f.p;
+    int s = 0;
+    while ((((p - 1) >> s) & 1) == 0) ++s;
+    const u64 minus_one = hf.neg(hf.one());
+    u64 g = hf.add(hf.one(), hf.one());
+    while (hf.pow(g, (p - 1) / 2) != minus_one) g = hf.add(g, hf.one());
+    ctx->rs_two_adicity = s;
+    ctx->rs_w_max = hf.pow(g, (p - 1) >> s);
+    ctx->rs_root_known = true;
+  }
+  return {ctx->rs_two_adicity, ctx->rs_w_max};
 }
 
-// the checks sc_rs_encode_rows and sc_ligero_commit share with their _long forms; *n = log2 of the table.  max_log: kRsMaxLog (a
-// codeword in the LDS of a CU) or kRsLongMaxLog (the two launches of kernels/ligero_long.hpp)
-int ligero_shape(sc_ctx* ctx, const sc_table* t, size_t log_cols, size_t log_blowup, const char* what, int* n, int max_log = sc::kRsMaxLog) {
+// RowCode::shape of Reed-Solomon (engine/abi_row_code.inc): what a table and a shape must satisfy, in the order a caller is told;
+// *n = log2 of the table.  Short rows: a codeword in the LDS of a CU; long_rows: the two launches of kernels/ligero_long.hpp
+int rs_shape(sc_ctx* ctx, const sc_table* t, size_t log_cols, size_t log_blowup, bool long_rows, const char* what, int* n) {
   SC_TRY(one_device_only(ctx, what));
   SC_TRY(check_table(ctx, t, what));
   *n = log2_of(t->len);
   if (log_blowup < 1 || log_blowup > 2) return fail(ctx, SC_ERR_ARG, "%s: log_blowup is %zu, not 1 or 2", what, log_blowup);
   if (log_cols > (size_t)*n) return fail(ctx, SC_ERR_ARG, "%s: log_cols = %zu exceeds the table's %d variables", what, log_cols, *n);
-  if (log_cols + log_blowup > (size_t)max_log)
-    return max_log == sc::kRsMaxLog
-               ? fail(ctx, SC_ERR_UNSUPPORTED, "%s: a codeword of 2^(%zu+%zu) words does not fit the LDS of a CU (at most 2^%d)", what, log_cols,
-                      log_blowup, sc::kRsMaxLog)
-               : fail(ctx, SC_ERR_UNSUPPORTED, "%s: a codeword of 2^(%zu+%zu) words is longer than 2^%d (there the stored tree is 1 GiB and a tile's strided segments 32 bytes)",
-                      what, log_cols, log_blowup, max_log);
+  if (!long_rows && log_cols + log_blowup > (size_t)sc::kRsMaxLog)
+    return fail(ctx, SC_ERR_UNSUPPORTED, "%s: a codeword of 2^(%zu+%zu) words does not fit the LDS of a CU (at most 2^%d)", what, log_cols,
+                log_blowup, sc::kRsMaxLog);
+  if (log_cols + log_blowup > (size_t)sc::kRsLongMaxLog)
+    return fail(ctx, SC_ERR_UNSUPPORTED, "%s: a codeword of 2^(%zu+%zu) words is longer than 2^%d (there the stored tree is 1 GiB and a tile's strided segments 32 bytes)",
+                what, log_cols, log_blowup, sc::kRsLongMaxLog);
   if (*n + log_blowup > 29) return fail(ctx, SC_ERR_UNSUPPORTED, "%s: 2^(%d+%zu) codeword words (at most 2^29)", what, *n, log_blowup);
-  int s = 0;
-  while ((((ctx->fp.p - 1) >> s) & 1) == 0) ++s;
+  const int s = two_adic_root(ctx).s;
   if (log_cols + log_blowup > (size_t)s)
     return fail(ctx, SC_ERR_UNSUPPORTED, "%s: p = %llu has 2-adicity %d: no root of unity of order 2^(%zu+%zu)", what,
                 (unsigned long long)ctx->fp.p, s, log_cols, log_blowup);
@@ -54,18 +63,15 @@ int ligero_shape(sc_ctx* ctx, const sc_table* t, size_t log_cols, size_t log_blo
 // the powers w_L^i, i < L/2 (at least one word), of this context, built on the host at first use; and the powers of W16
 int rs_twiddles(sc_ctx* ctx, int log_len, const u64** tw, sc::RsRoots* roots) {
   const HostField hf(ctx->fp);
-  if (!ctx->rs_root_known) {
-    two_adic_root(hf, &ctx->rs_two_adicity, &ctx->rs_w_max);
-    ctx->rs_root_known = true;
-  }
-  const int s = ctx->rs_two_adicity;
+  const TwoAdicRoot root = two_adic_root(ctx);
+  const int s = root.s;
   for (int k = 0; k < 8; ++k) {
     // W16^k = w_max^(k 2^s / 16) where the field has that root
     const int tz = k ? __builtin_ctz(k) : 4;
-    roots->w16[k] = s + tz >= 4 ? hf.pow(ctx->rs_w_max, s >= 4 ? (u64)k << (s - 4) : (u64)k >> (4 - s)) : 0;
+    roots->w16[k] = s + tz >= 4 ? hf.pow(root.w_max, s >= 4 ? (u64)k << (s - 4) : (u64)k >> (4 - s)) : 0;
   }
   SC_TRY(upload_once(ctx, &ctx->d_rs_twiddles[log_len], std::max<size_t>(1, ((size_t)1 << log_len) / 2), "twiddle", [&](u64* h) {
-    u64 w = ctx->rs_w_max;
+    u64 w = root.w_max;
     for (int k = s; k > log_len; --k) w = hf.mul(w, w);
     h[0] = hf.one();
     for (size_t i = 1; i < ((size_t)1 << log_len) / 2; ++i) h[i] = hf.mul(h[i - 1], w);
@@ -98,9 +104,10 @@ int rs_encode_impl(sc_ctx* ctx, const u64* in, int n, int c, int rho, u64* E) {
 int rs_twist_tables(sc_ctx* ctx, int log_len, const u64** lo, const u64** hi) {
   const HostField hf(ctx->fp);
   const size_t n_lo = (size_t)1 << sc::kRsTwistLoLog, n_hi = (size_t)1 << (log_len - sc::kRsTwistLoLog);
+  const TwoAdicRoot root = two_adic_root(ctx);
   SC_TRY(upload_once(ctx, &ctx->d_rs_twist[log_len], n_lo + n_hi, "twist table", [&](u64* h) {
-    u64 w = ctx->rs_w_max;
-    for (int k = ctx->rs_two_adicity; k > log_len; --k) w = hf.mul(w, w);
+    u64 w = root.w_max;
+    for (int k = root.s; k > log_len; --k) w = hf.mul(w, w);
     h[0] = hf.one();
     for (size_t i = 1; i < n_lo; ++i) h[i] = hf.mul(h[i - 1], w);
     const u64 step = hf.mul(h[n_lo - 1], w);
@@ -112,8 +119,8 @@ int rs_twist_tables(sc_ctx* ctx, int log_len, const u64** lo, const u64** hi) {
   return SC_OK;
 }
 
-// E = the encoding of the rows of `in` at any c + rho <= kRsLongMaxLog: up to kRsMaxLog rs_encode_impl itself, above it the two
-// launches of kernels/ligero_long.hpp - the column step writes E, the row step transforms it in place
+// RowCode::encode: E = the encoding of the rows of `in` at any c + rho <= kRsLongMaxLog: up to kRsMaxLog rs_encode_impl itself,
+// above it the two launches of kernels/ligero_long.hpp - the column step writes E, the row step transforms it in place
 int rs_encode_long_impl(sc_ctx* ctx, const u64* in, int n, int c, int rho, u64* E) {
   const int log_len = c + rho;
   if (log_len <= sc::kRsMaxLog) return rs_encode_impl(ctx, in, n, c, rho, E);
@@ -159,74 +166,6 @@ int ligero_check(sc_ctx* ctx, const sc_ligero* lg, const char* what) {
 }
 
 }  // namespace
-
-extern "C" int sc_rs_encode_rows(sc_ctx* ctx, const sc_table* t, size_t log_cols, size_t log_blowup, sc_table** out) {
-  if (!ctx || !out) return SC_ERR_ARG;
-  *out = nullptr;
-  int n = 0;
-  SC_TRY(ligero_shape(ctx, t, log_cols, log_blowup, "sc_rs_encode_rows", &n));
-  SC_TRY(set_device(ctx));
-  TableBuf E;
-  SC_TRY(E.alloc(ctx, (size_t)1 << (n + log_blowup)));
-  SC_TRY(rs_encode_impl(ctx, t->d, n, (int)log_cols, (int)log_blowup, E->d));
-  *out = E.release();
-  return SC_OK;
-}
-
-extern "C" int sc_rs_encode_rows_long(sc_ctx* ctx, const sc_table* t, size_t log_cols, size_t log_blowup, sc_table** out) {
-  if (!ctx || !out) return SC_ERR_ARG;
-  *out = nullptr;
-  int n = 0;
-  SC_TRY(ligero_shape(ctx, t, log_cols, log_blowup, "sc_rs_encode_rows_long", &n, sc::kRsLongMaxLog));
-  SC_TRY(set_device(ctx));
-  TableBuf E;
-  SC_TRY(E.alloc(ctx, (size_t)1 << (n + log_blowup)));
-  SC_TRY(rs_encode_long_impl(ctx, t->d, n, (int)log_cols, (int)log_blowup, E->d));
-  *out = E.release();
-  return SC_OK;
-}
-
-// the commitment to a table whose shape has been checked: E from `encode(E)`, then the tree over its columns
-template <class Encode>
-static int ligero_commit_with(sc_ctx* ctx, const sc_table* t, int n, int c, int rho, int code, Encode&& encode, sc_ligero** out) {
-  SC_TRY(set_device(ctx));
-  sc_ligero* lg = new (std::nothrow) sc_ligero;
-  if (!lg) return fail(ctx, SC_ERR_OOM, "host allocation failed");
-  lg->ctx = ctx;
-  lg->t = t;
-  lg->c = c;
-  lg->r = n - c;
-  lg->rho = rho;
-  lg->code = code;
-  int rc = lg->E.alloc(ctx, (size_t)1 << (n + rho));
-  if (rc == SC_OK) rc = lg->levels.alloc(ctx, c + rho);
-  if (rc == SC_OK) rc = encode(lg->E->d);
-  if (rc == SC_OK) rc = ligero_tree_build(ctx, lg);
-  if (rc != SC_OK) {
-    delete lg;
-    return rc;
-  }
-  *out = lg;
-  return SC_OK;
-}
-
-extern "C" int sc_ligero_commit(sc_ctx* ctx, const sc_table* t, size_t log_cols, size_t log_blowup, sc_ligero** out) {
-  if (!ctx || !out) return SC_ERR_ARG;
-  *out = nullptr;
-  int n = 0;
-  SC_TRY(ligero_shape(ctx, t, log_cols, log_blowup, "sc_ligero_commit", &n));
-  return ligero_commit_with(ctx, t, n, (int)log_cols, (int)log_blowup, SC_CODE_RS,
-                            [&](u64* E) { return rs_encode_impl(ctx, t->d, n, (int)log_cols, (int)log_blowup, E); }, out);
-}
-
-extern "C" int sc_ligero_commit_long(sc_ctx* ctx, const sc_table* t, size_t log_cols, size_t log_blowup, sc_ligero** out) {
-  if (!ctx || !out) return SC_ERR_ARG;
-  *out = nullptr;
-  int n = 0;
-  SC_TRY(ligero_shape(ctx, t, log_cols, log_blowup, "sc_ligero_commit_long", &n, sc::kRsLongMaxLog));
-  return ligero_commit_with(ctx, t, n, (int)log_cols, (int)log_blowup, SC_CODE_RS,
-                            [&](u64* E) { return rs_encode_long_impl(ctx, t->d, n, (int)log_cols, (int)log_blowup, E); }, out);
-}
 
 extern "C" int sc_ligero_root(const sc_ligero* lg, uint8_t root[32]) {
   if (!lg || !root) return SC_ERR_ARG;

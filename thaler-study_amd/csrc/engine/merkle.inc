@@ -1,6 +1,6 @@
 // Part of sumcheck_hip.hip (included there, in order): what the three commitments (engine/abi_pcs.inc, abi_ligero.inc,
-// abi_expander.inc) share on the host: their guards, the one way they launch a kernel, and the tree of digests above whatever
-// leaves each of them hashes (kernels/merkle.hpp).
+// abi_expander.inc; the entry points of the last two: abi_row_code.inc) share on the host: their guards, the one way they launch
+// a kernel, and the tree of digests above whatever leaves each of them hashes (kernels/merkle.hpp).
 
 using sc::u32;
 

@@ -250,8 +250,9 @@ struct sc_ctx {
   u64* h_batch = nullptr;
   u64* d_batch = nullptr;
   size_t batch_words = 0;
-  // sc_rs_encode_rows / sc_ligero_commit (engine/abi_ligero.inc): the field's two-adic root, found at first use, and the device
-  // tables of the powers of w_L, one per codeword length 2^k used so far (workspace like d_points: not pool blocks)
+  // sc_rs_encode_rows / sc_ligero_commit (engine/abi_ligero.inc): the field's two-adic root, found at first use (two_adic_root
+  // there: read these three through it), and the device tables of the powers of w_L, one per codeword length 2^k used so far
+  // (workspace like d_points: not pool blocks)
   bool rs_root_known = false;
   int rs_two_adicity = 0;
   u64 rs_w_max = 0;
@@ -599,6 +600,7 @@ static int multi_prod2_fold_and_sums(sc_ctx* m, const sc_table* a, const sc_tabl
 #include "engine/abi_restrict.inc"
 #include "engine/merkle.inc"
 #include "engine/abi_pcs.inc"
-#include "engine/abi_ligero.inc"
-#include "engine/abi_expander.inc"
+#include "engine/abi_ligero.inc"     // the commitment, and the Reed-Solomon row code
+#include "engine/abi_expander.inc"   // the expander row code
+#include "engine/abi_row_code.inc"   // the table of both, and the entry points that encode and commit through it
 #include "engine/abi_multi.inc"

@@ -125,32 +125,31 @@ class ColumnPath(Path):
 
 # ---- the device side -------------------------------------------------------------------------------------------------
 
+def _encode_rows(ctx, symbol, poly, *shape):
+    """call an encode symbol on `poly`'s table and wrap the handle of the codeword matrix"""
+    h = voidp()
+    ctx.check(getattr(ctx.lib, symbol)(ctx.h, poly.h, *shape, ctypes.byref(h)))
+    return DenseMultilinearExtension(ctx, h)
+
+
 def rs_encode_rows(ctx, poly, log_cols, log_blowup):
     """sc_rs_encode_rows: the codeword matrix of `poly`'s table, row-major, a device table of 2^(n + log_blowup) words"""
-    h = voidp()
-    ctx.check(ctx.lib.sc_rs_encode_rows(ctx.h, poly.h, log_cols, log_blowup, ctypes.byref(h)))
-    return DenseMultilinearExtension(ctx, h)
+    return _encode_rows(ctx, "sc_rs_encode_rows", poly, log_cols, log_blowup)
 
 
 def rs_encode_rows_long(ctx, poly, log_cols, log_blowup):
     """sc_rs_encode_rows_long: rs_encode_rows for log_cols + log_blowup up to LONG_MAX_LOG_LEN"""
-    h = voidp()
-    ctx.check(ctx.lib.sc_rs_encode_rows_long(ctx.h, poly.h, log_cols, log_blowup, ctypes.byref(h)))
-    return DenseMultilinearExtension(ctx, h)
+    return _encode_rows(ctx, "sc_rs_encode_rows_long", poly, log_cols, log_blowup)
 
 
 def xc_encode_rows(ctx, poly, log_cols):
     """sc_xc_encode_rows: the codeword matrix of `poly`'s table under the expander code, row-major, a device table of 2^(n + 1) words"""
-    h = voidp()
-    ctx.check(ctx.lib.sc_xc_encode_rows(ctx.h, poly.h, log_cols, ctypes.byref(h)))
-    return DenseMultilinearExtension(ctx, h)
+    return _encode_rows(ctx, "sc_xc_encode_rows", poly, log_cols)
 
 
 def xc_encode_rows_long(ctx, poly, log_cols):
     """sc_xc_encode_rows_long: xc_encode_rows for log_cols up to expander_code.LONG_MAX_LOG_COLS"""
-    h = voidp()
-    ctx.check(ctx.lib.sc_xc_encode_rows_long(ctx.h, poly.h, log_cols, ctypes.byref(h)))
-    return DenseMultilinearExtension(ctx, h)
+    return _encode_rows(ctx, "sc_xc_encode_rows_long", poly, log_cols)
 
 
 class Prover:
@@ -167,34 +166,32 @@ class Prover:
         self.code = {v: k for k, v in CODES.items()}[code.value]
 
     @classmethod
+    def _commit(cls, ctx, poly, log_cols, log_blowup, code, long_rows):
+        """sc_ligero_commit_code or its _long form, which hand Reed-Solomon to sc_ligero_commit / sc_ligero_commit_long"""
+        symbol = "sc_ligero_commit_code_long" if long_rows else "sc_ligero_commit_code"
+        h = voidp()
+        ctx.check(getattr(ctx.lib, symbol)(ctx.h, poly.h, log_cols, log_blowup, _code_id(code), ctypes.byref(h)))
+        return cls(ctx, poly, h)
+
+    @classmethod
     def commit(cls, ctx, poly, log_cols=None, log_blowup=1, code="rs"):
-        code_id = _code_id(code)
+        _code_id(code)
         if log_cols is None:
             log_cols = default_log_cols(poly.num_vars(), log_blowup, code)
-        h = voidp()
-        if code == "rs":
-            ctx.check(ctx.lib.sc_ligero_commit(ctx.h, poly.h, log_cols, log_blowup, ctypes.byref(h)))
-        else:
-            ctx.check(ctx.lib.sc_ligero_commit_code(ctx.h, poly.h, log_cols, log_blowup, code_id, ctypes.byref(h)))
-        return cls(ctx, poly, h)
+        return cls._commit(ctx, poly, log_cols, log_blowup, code, False)
 
     @classmethod
     def commit_long(cls, ctx, poly, log_cols=None, log_blowup=1, queries=None, code="rs"):
         """sc_ligero_commit_long / sc_ligero_commit_code_long: rows of up to 2^LONG_MAX_LOG_LEN codeword words.  log_cols=None: the
         shape whose opening of `queries` columns is smallest (long_log_cols) - for Reed-Solomon as far as the field's two-adicity
         allows; the expander code has no such bound"""
-        code_id = _code_id(code)
+        _code_id(code)
         if log_cols is None:
             if queries is None:
                 raise ValueError("commit_long chooses log_cols from the number of queries: give log_cols or queries")
             s = two_adic_root(ctx.field.p)[0] if code == "rs" else LONG_MAX_LOG_LEN
             log_cols = long_log_cols(poly.num_vars(), log_blowup, queries, min(LONG_MAX_LOG_LEN, s))
-        h = voidp()
-        if code == "rs":
-            ctx.check(ctx.lib.sc_ligero_commit_long(ctx.h, poly.h, log_cols, log_blowup, ctypes.byref(h)))
-        else:
-            ctx.check(ctx.lib.sc_ligero_commit_code_long(ctx.h, poly.h, log_cols, log_blowup, code_id, ctypes.byref(h)))
-        return cls(ctx, poly, h)
+        return cls._commit(ctx, poly, log_cols, log_blowup, code, True)
 
     def root(self):
         buf = (ctypes.c_uint8 * 32)()
