@@ -246,6 +246,9 @@ int sc_ctx_kernel_time(sc_ctx* ctx, double out[2], int reset);
                                 * message (reads 8 * R * 2^lm, writes 8 * R * 2^(lm-2), R = 2^(n - log_cols) rows); kf = 2 xc_long_inner_kernel, the
                                 * code below them in LDS (ks = lm_i = 12 or 13; reads and writes 8 * R * 2^lm_i); kf = 3 xc_long_up_kernel, one per
                                 * global level (reads and writes 8 * R * 2^(lm-1)); log_in = n */
+#define SC_KIND_RS_FOLD 24     /* rs_fold_kernel: one fold of a Reed-Solomon codeword of M = 2^ks words (sc_rs_fold, sc_ligero_fold_prove), one launch; kf = 1 if
+                                * it also hashed the leaves of the folded codeword's tree, else 0; log_in = n (sc_rs_fold: ks); it reads 8 * M bytes
+                                * and writes 4 * M, plus 8 * M of digests with kf = 1.  The tree levels above the leaves are SC_KIND_MERKLE records */
 typedef struct sc_launch_record {
   int32_t kind;           /* SC_KIND_* */
   int32_t kf, ks;         /* variables folded / rounds served (meaning per kind above) */
@@ -603,6 +606,39 @@ int sc_ligero_code(const sc_ligero* lg, int* code);
  * open_columns / destroy serve it unchanged. */
 int sc_xc_encode_rows_long(sc_ctx* ctx, const sc_table* t, size_t log_cols, sc_table** out);
 int sc_ligero_commit_code_long(sc_ctx* ctx, const sc_table* t, size_t log_cols, size_t log_blowup, int code, sc_ligero** out);
+
+/* ---- folded openings of the Reed-Solomon commitment: prove the combined row instead of sending it ----------------------
+ * (kernels/rs_fold.hpp states the contract)  An opening of an sc_ligero with code SC_CODE_RS and
+ * log_cols = c >= 1 at a point z: the prover sends v = u_z(z[:c]) and v_gamma = u_gamma(z[:c]) instead of the two combined rows,
+ * and proves them by c rounds of the product sumcheck over (m, eq(z[:c])), m = u_z + beta u_gamma, interleaved with c folds of the
+ * codeword U_0 = Enc(m) (Basefold); the layers U_1 .. U_(c-1) are committed with the commitment's column leaf (two rows) and tree.
+ * With l0 = log_cols + log_blowup, w_l the contract's root of order 2^l: U_(i+1)[j] = even + alpha_i (odd - even), even =
+ * (U_i[j] + U_i[j + M/2]) / 2, odd = (U_i[j] - U_i[j + M/2]) / (2 w_(l0-i)^j), M = 2^(l0-i), j < M / 2.  No security level is claimed.
+ * SC_ERR_ARG: a null pointer, log_cols = 0 (use the plain opening), a commitment or an opening of another context, an index
+ * >= L / 2, an unreduced point, gamma, beta, alpha or challenge, sc_rs_fold on a table of fewer than 4 words.
+ * SC_ERR_UNSUPPORTED: an expander-code commitment, sc_rs_fold on more than 2^24 or more than 2^s words, a sharded context or a
+ * multi-device handle.  SC_ERR_STATE: sc_ligero_fold_prove called twice, sc_ligero_fold_query before it. */
+
+/* one fold alone: u holds M = 2^l words, 2 <= l <= min(24, s), a codeword in the contract's order; *out = its fold with alpha
+ * at x = w_l^j, a new table of M / 2 words.  One launch (SC_KIND_RS_FOLD, kf = 0). */
+int sc_rs_fold(sc_ctx* ctx, const sc_table* u, uint64_t alpha, sc_table** out);
+typedef struct sc_ligero_fold sc_ligero_fold;
+/* the verifier's alpha_i for round i, called with the round's three sums and, for round >= 1, root_i (32 bytes; NULL at round 0) */
+typedef uint64_t (*sc_draw_fold_fn)(void* user, size_t round, const uint64_t evals[3], const uint8_t* root);
+/* steps 2 - 3: point = the n words of z, gamma = 2^log_rows words; claims[0] = v, claims[1] = v_gamma.  The two combined rows stay
+ * on the device.  lg is borrowed: it must outlive the opening. */
+int sc_ligero_fold_begin(sc_ctx* ctx, const sc_ligero* lg, const uint64_t* point, const uint64_t* gamma, uint64_t claims[2],
+                         sc_ligero_fold** out);
+/* steps 4 - 7, once per opening: evals = 3 c words (every round's H(0), H(1), H(2)), roots = 32 (c - 1) bytes (root_1 ..
+ * root_(c-1); may be NULL for c = 1), challenges = c words or NULL, *final_value = the word of U_c; `draw` is required and is
+ * called once per round, in order.  One rs_fold_kernel launch per round; U_0 is encoded by the row encoder and not kept. */
+int sc_ligero_fold_prove(sc_ctx* ctx, sc_ligero_fold* fd, uint64_t beta, sc_draw_fold_fn draw, void* user, uint64_t* evals,
+                         uint8_t* roots, uint64_t* challenges, uint64_t* final_value);
+/* step 9's layer openings for `count` indices q < L / 2 (the columns q and q + L / 2 come from sc_ligero_open_columns):
+ * pairs[q][c - 1][2] = (U_i[j_i], U_i[j_i + M_i / 2]), j_i = q mod 2^(l0-i-1), for i = 1 .. c - 1 (Montgomery words);
+ * paths[q][P][32], P = sum_{i=1}^{c-1} (l0 - i - 1): the layers in order, each path bottom up.  c = 1: nothing is written. */
+int sc_ligero_fold_query(sc_ctx* ctx, const sc_ligero_fold* fd, const uint64_t* q, size_t count, uint64_t* pairs, uint8_t* paths);
+int sc_ligero_fold_destroy(sc_ctx* ctx, sc_ligero_fold* fd);
 
 /* ---- gkr_protocol::circuit::Circuit on the device, and the whole GKR prover over it ----------------------------------
  * A circuit lives on ONE context of one device and one rank: sharded contexts (world > 1) and multi-device handles get

@@ -99,11 +99,18 @@ pub struct sc_merkle_tree {
 pub struct sc_ligero {
     _private: [u8; 0],
 }
+/// a folded opening in progress (`sc_ligero_fold_begin`)
+#[repr(C)]
+pub struct sc_ligero_fold {
+    _private: [u8; 0],
+}
 
 pub type sc_allreduce_fn = Option<unsafe extern "C" fn(user: *mut c_void, buf: *mut u64, count: usize) -> c_int>;
 pub type sc_allgather_fn =
     Option<unsafe extern "C" fn(user: *mut c_void, send: *const u64, recv: *mut u64, count: usize) -> c_int>;
 pub type sc_draw_fn = Option<unsafe extern "C" fn(user: *mut c_void, round: usize, evals: *const u64) -> u64>;
+/// `sc_ligero_fold_prove`: the verifier's alpha of a round; `root` = the round's layer root (32 bytes), null at round 0.
+pub type sc_draw_fold_fn = Option<unsafe extern "C" fn(user: *mut c_void, round: usize, evals: *const u64, root: *const u8) -> u64>;
 /// `sc_prove_batch`: called round by round, within a round in instance order.
 pub type sc_draw_batch_fn = Option<unsafe extern "C" fn(user: *mut c_void, instance: usize, round: usize, evals: *const u64) -> u64>;
 
@@ -521,4 +528,37 @@ extern "C" {
         code: c_int,
         out: *mut *mut sc_ligero,
     ) -> c_int;
+    /// one fold of a Reed-Solomon codeword of 2^l words (2 <= l <= 24) with alpha: one launch, SC_KIND_RS_FOLD (24)
+    pub fn sc_rs_fold(ctx: *mut sc_ctx, u: *const sc_table, alpha: u64, out: *mut *mut sc_table) -> c_int;
+    /// a folded opening of a Reed-Solomon commitment at `point`: claims = (v, v_gamma); the combined rows stay on the device
+    pub fn sc_ligero_fold_begin(
+        ctx: *mut sc_ctx,
+        lg: *const sc_ligero,
+        point: *const u64,
+        gamma: *const u64,
+        claims: *mut u64,
+        out: *mut *mut sc_ligero_fold,
+    ) -> c_int;
+    /// the c sumcheck rounds with a fold and a layer tree between them: evals 3 c words, roots 32 (c - 1) bytes, challenges c words or null
+    pub fn sc_ligero_fold_prove(
+        ctx: *mut sc_ctx,
+        fd: *mut sc_ligero_fold,
+        beta: u64,
+        draw: sc_draw_fold_fn,
+        user: *mut c_void,
+        evals: *mut u64,
+        roots: *mut u8,
+        challenges: *mut u64,
+        final_value: *mut u64,
+    ) -> c_int;
+    /// the opened layer pairs of `count` indices below L / 2: pairs count x (c - 1) x 2 words, paths count x P x 32 bytes
+    pub fn sc_ligero_fold_query(
+        ctx: *mut sc_ctx,
+        fd: *const sc_ligero_fold,
+        q: *const u64,
+        count: usize,
+        pairs: *mut u64,
+        paths: *mut u8,
+    ) -> c_int;
+    pub fn sc_ligero_fold_destroy(ctx: *mut sc_ctx, fd: *mut sc_ligero_fold) -> c_int;
 }

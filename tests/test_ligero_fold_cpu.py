@@ -1,0 +1,226 @@
+"""CPU-only: the folded opening's reference (tests/ligero_fold_ref.py) against the identity it rests on, the package's host
+FoldVerifier (thaler-study_amd/ligero_pcs.py) against the reference prover - honest transcripts are accepted with the right value,
+every tampered message is refused with its own error - the opening-size helpers against the counted bytes of the reference's
+messages, and the per-item code of rs_fold_kernel, compiled for the host (tests/cpp/rs_fold_host_harness.cpp), against the
+reference bit for bit."""
+import ctypes
+import hashlib
+import os
+import random
+import subprocess
+
+import numpy as np
+import pytest
+
+import ligero_fold_ref as fref
+import ligero_ref as ref
+from conftest import ROOT
+
+GOLD = ref.GOLD
+SHAPES = [(3, 3, 1), (5, 1, 1), (6, 3, 1), (7, 2, 2)]   # (n, c, rho): R = 1; no trees; the ordinary case; two blow-up bits
+
+
+@pytest.mark.parametrize("p", [GOLD, ref.BABYBEAR, 257])
+def test_fold_of_a_codeword_is_the_codeword_of_the_fixed_message(p):
+    rng = random.Random(p)
+    for c, rho in ((1, 1), (2, 1), (3, 2), (5, 1)):
+        m = [rng.randrange(p) for _ in range(1 << c)]
+        for alpha in (0, 1, p - 1, rng.randrange(p)):
+            U = ref.encode(m, c, rho, p)[0]
+            assert fref.fold(U, alpha, p) == ref.encode(fref.fix_variables(m, [alpha], p), c - 1, rho, p)[0], (c, rho, alpha)
+    # .. down to 2^rho equal words
+    m = [rng.randrange(p) for _ in range(8)]
+    U, alphas = ref.encode(m, 3, 2, p)[0], [rng.randrange(p) for _ in range(3)]
+    for a in alphas:
+        U = fref.fold(U, a, p)
+    assert U == [ref.mle_eval(m, alphas, p)] * 4
+
+
+def run_fold_protocol(pkg, p, n, c, rho, queries, seed, tamper=None):
+    """the reference prover against the package's FoldVerifier; `tamper` names the message to corrupt.  Returns (value, expected,
+    reference prover)"""
+    lp = pkg.ligero_pcs
+    F = pkg.Field(p)
+    rng = random.Random(seed)
+    table = [rng.randrange(p) for _ in range(1 << n)]
+    corrupt = None
+    if tamper == "layer":
+        corrupt = lambda i, U: [(x + k % 2) % p for k, x in enumerate(U)] if i == 1 else U   # noqa: E731 (wrong odd words of U_1, hashed as they are: the final value does not depend on them)
+    prover = fref.RefFoldProver(table, c, rho, p, corrupt=corrupt)
+    v = lp.FoldVerifier(F, n, c, rho, prover.root(), queries)
+    gamma = v.draw_gamma(rng)
+    point = [F.rand(rng) for _ in range(n)]
+    claims = ref.mont(p, prover.begin(ref.canon(p, point), ref.canon(p, gamma)))
+    if tamper == "v":
+        claims[0] = F.add(claims[0], F.one)
+    if tamper == "v_gamma":
+        claims[1] = F.add(claims[1], F.one)
+    v.receive_claims(*claims)
+    beta = v.draw_beta(rng)
+
+    def draw(i, sums, root):
+        sums = ref.mont(p, sums)
+        if tamper == "round" and i == c - 1:
+            sums[2] = F.add(sums[2], F.one)       # the last round's H(2): only the final check sees it
+        if tamper == "round0" and i == 0:
+            sums[0] = F.add(sums[0], F.one)
+        if tamper == "root" and i == 1:
+            root = bytes([root[0] ^ 1]) + root[1:]
+        return F.to_int(v.round(i, sums, root, rng))
+
+    _, _, _, final = prover.prove(F.to_int(beta), draw)
+    final = F.from_int(final)
+    if tamper == "final":
+        final = F.add(final, F.one)
+    v.receive_final(final)
+    indices = v.draw_queries(rng)
+    asked = list(indices)
+    if tamper == "index":
+        asked[2] = (asked[2] + 1) % (1 << (c + rho - 1))
+    openings = []
+    for q, col_lo, col_hi, layers in prover.query(asked):
+        cols = [(j, ref.mont(p, vals), lp.ColumnPath(j, sib, F)) for j, vals, sib in (col_lo, col_hi)]
+        openings.append((q, cols[0], cols[1], [(tuple(ref.mont(p, pair)), list(sib)) for pair, sib in layers]))
+    if tamper == "index":
+        q, col_lo, col_hi, layers = openings[2]
+        openings[2] = (indices[2], col_lo, col_hi, layers)     # answered for another index, labelled as the drawn one
+    if tamper == "pair":
+        q, col_lo, col_hi, layers = openings[1]
+        pair, sib = layers[-1]
+        openings[1] = (q, col_lo, col_hi, layers[:-1] + [((pair[0], F.add(pair[1], F.one)), sib)])
+    if tamper == "path":
+        q, col_lo, col_hi, layers = openings[3]
+        pair, sib = layers[0]
+        openings[3] = (q, col_lo, col_hi, [(pair, sib[:-1] + [bytes(32)])] + layers[1:])
+    if tamper == "column":
+        q, col_lo, (j, vals, path), layers = openings[0]
+        openings[0] = (q, col_lo, (j, [F.add(vals[0], F.one)] + vals[1:], path), layers)
+    value = v.verify(point, openings)
+    return value, F.from_int(ref.mle_eval(table, ref.canon(p, point), p)), prover
+
+
+@pytest.mark.parametrize("p", [GOLD, 257])
+@pytest.mark.parametrize("n,c,rho", SHAPES)
+def test_fold_verifier_accepts_the_reference_prover(pkg, p, n, c, rho):
+    value, want, _ = run_fold_protocol(pkg, p, n, c, rho, 8, 10 * n + c)
+    assert value == want
+
+
+@pytest.mark.parametrize("p", [GOLD, 257])
+def test_fold_tampering_is_caught(pkg, p):
+    lp = pkg.ligero_pcs
+    for tamper, err in (("v", lp.RoundMismatch), ("v_gamma", lp.RoundMismatch), ("round0", lp.RoundMismatch), ("round", lp.EvalMismatch),
+                        ("root", lp.MerkleMismatch), ("final", lp.EvalMismatch), ("pair", lp.MerkleMismatch), ("path", lp.MerkleMismatch),
+                        ("column", lp.MerkleMismatch), ("index", lp.MerkleMismatch), ("layer", lp.FoldMismatch)):
+        with pytest.raises(err):
+            run_fold_protocol(pkg, p, 6, 3, 1, 8, 31, tamper=tamper)
+    # without trees (c = 1) the claims, the round and the column still bind
+    for tamper, err in (("v", lp.RoundMismatch), ("round", lp.EvalMismatch), ("final", lp.EvalMismatch), ("column", lp.MerkleMismatch)):
+        with pytest.raises(err):
+            run_fold_protocol(pkg, p, 5, 1, 1, 8, 32, tamper=tamper)
+
+
+def test_fold_errors_are_the_relaxed_pcs_family_and_the_order_is_enforced(pkg):
+    lp, rp = pkg.ligero_pcs, pkg.relaxed_pcs
+    assert issubclass(lp.FoldMismatch, rp.Error) and issubclass(lp.RoundMismatch, rp.Error)
+    F = pkg.Field(GOLD)
+    with pytest.raises(ValueError):
+        lp.FoldVerifier(F, 6, 0, 1, bytes(32), 4)      # log_cols = 0: the plain opening
+    v = lp.FoldVerifier(F, 6, 3, 1, bytes(32), 4)
+    rng = random.Random(1)
+    with pytest.raises(rp.Error):
+        v.draw_beta(rng)
+    v.draw_gamma(rng)
+    v.receive_claims(F.one, F.one)
+    with pytest.raises(rp.Error):
+        v.draw_queries(rng)
+    with pytest.raises(rp.Error):
+        v.round(1, [0, 0, 0], bytes(32), rng)
+
+
+@pytest.mark.parametrize("n,c,rho", SHAPES)
+def test_fold_opening_bytes_counts_the_reference_messages(pkg, n, c, rho):
+    lp = pkg.ligero_pcs
+    _, _, prover = run_fold_protocol(pkg, GOLD, n, c, rho, 5, 77)
+    assert fref.message_bytes(prover.messages) == lp.fold_opening_bytes(n, c, rho, 5)
+
+
+def test_fold_size_helpers(pkg):
+    lp = pkg.ligero_pcs
+    assert lp.fold_opening_bytes(28, 22, 1, 128) == 1309896
+    assert lp.fold_log_cols(28, 1, 128) == 22 and lp.fold_log_cols(24, 1, 128) == 18
+    assert lp.fold_log_cols(28, 1, 128, max_log_len=15) == 14
+    # the issue's table, and where the plain opening stays smaller
+    assert round(lp.fold_opening_bytes(28, lp.fold_log_cols(28, 1, 64), 1, 64) / 2**20, 3) == 0.625
+    assert round(lp.fold_opening_bytes(24, 18, 1, 128) / 2**20, 3) == 0.905
+    assert round(lp.fold_opening_bytes(20, lp.fold_log_cols(20, 1, 128), 1, 128) / 2**20, 3) == 0.624
+    assert lp.opening_bytes(20, lp.long_log_cols(20, 1, 128), 1, 128) < lp.fold_opening_bytes(20, lp.fold_log_cols(20, 1, 128), 1, 128)
+    assert lp.opening_bytes(24, lp.long_log_cols(24, 1, 128), 1, 128) > lp.fold_opening_bytes(24, 18, 1, 128)
+    with pytest.raises(ValueError):
+        lp.fold_opening_bytes(8, 0, 1, 4)
+
+
+# ---- the kernel's per-item code on the host --------------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def rf(tmp_path_factory):
+    out = tmp_path_factory.mktemp("rf") / "librs_fold_host.so"
+    src = os.path.join(ROOT, "tests", "cpp", "rs_fold_host_harness.cpp")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", str(out), src])
+    lib = ctypes.CDLL(str(out))
+    u64p = ctypes.POINTER(ctypes.c_uint64)
+    lib.rf_fold.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, u64p, u64p,
+                            ctypes.POINTER(ctypes.c_uint8)]
+    lib.rf_fold.restype = None
+    lib.rf_exp.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32]
+    lib.rf_exp.restype = ctypes.c_uint32
+    return lib
+
+
+def host_fold(rf, p, log_len0, shift, alpha, U, leaves=True):
+    """rs_fold_kernel's items over the canonical codeword U of 2^(log_len0 - shift) words: (folded canonical words, leaf digests)"""
+    M = len(U)
+    u = np.array(ref.mont(p, U), dtype=np.uint64)
+    out = np.zeros(M // 2, dtype=np.uint64)
+    dig = (ctypes.c_uint8 * (32 * (M // 4)))()
+    u64p = ctypes.POINTER(ctypes.c_uint64)
+    rf.rf_fold(p, int(p == GOLD), ref.mont(p, [ref.omega(p, log_len0)])[0], log_len0, shift, ref.mont(p, [alpha])[0],
+               u.ctypes.data_as(u64p), out.ctypes.data_as(u64p), dig if leaves else None)
+    raw = bytes(dig)
+    return ref.canon(p, out), [raw[32 * j:32 * j + 32] for j in range(M // 4)]
+
+
+def worst_case_words(p, M, rng):
+    """codeword-shaped input of worst-case words: p - 1 and 0 alternating, runs of p - 1, and random words"""
+    return [p - 1 if k % 4 == 0 else 0 if k % 4 == 1 else p - 1 - (k % 3) if k % 4 == 2 else rng.randrange(p) for k in range(M)]
+
+
+@pytest.mark.parametrize("p", [GOLD, ref.BABYBEAR, ref.P64S18])
+def test_host_item_equals_the_reference_fold(rf, p):
+    rng = random.Random(p + 5)
+    for log_m in range(2, 11):
+        M = 1 << log_m
+        for U in ([rng.randrange(p) for _ in range(M)], worst_case_words(p, M, rng), [p - 1] * M):
+            for alpha in (0, 1, p - 1, rng.randrange(p)):
+                got, leaves = host_fold(rf, p, log_m, 0, alpha, U)
+                want = fref.fold(U, alpha, p)
+                assert got == want, (p, log_m, alpha)
+                assert leaves == [fref.pair_leaf(want[j], want[j + M // 4]) for j in range(M // 4)], (p, log_m, alpha)
+
+
+@pytest.mark.parametrize("p", [GOLD, ref.P64S18])
+def test_host_item_serves_every_layer_from_the_layer_0_tables(rf, p):
+    """a layer of 2^(l0 - shift) words folds with the tables of length 2^l0, on both sides of the twist tables' boundary"""
+    rng = random.Random(p + 6)
+    for log_len0 in (5, 11, 12, 13):
+        for shift in (1, 2, log_len0 - 4, log_len0 - 2):
+            M = 1 << (log_len0 - shift)
+            U, alpha = worst_case_words(p, M, rng), rng.randrange(p)
+            assert host_fold(rf, p, log_len0, shift, alpha, U, leaves=False)[0] == fref.fold(U, alpha, p), (p, log_len0, shift)
+    # the exponent of 1 / x: L - j 2^shift mod L
+    for log_len0, shift, j in ((12, 0, 0), (12, 0, 1), (12, 3, 255), (5, 2, 3), (24, 0, (1 << 23) - 1), (24, 10, 8191)):
+        assert rf.rf_exp(log_len0, shift, j) == ((1 << log_len0) - (j << shift)) % (1 << log_len0)
+
+
+def test_pair_leaf_is_the_column_leaf_of_two_rows():
+    assert fref.pair_leaf(3, 5) == ref.column_leaf([[3], [5]], 0) == hashlib.sha256((3).to_bytes(8, "little") + (5).to_bytes(8, "little")).digest()

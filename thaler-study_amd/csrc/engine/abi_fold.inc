@@ -1,0 +1,272 @@
+// Part of sumcheck_hip.hip (included there, in order, after abi_row_code.inc): C ABI: the folded opening of a Reed-Solomon
+// sc_ligero (kernels/rs_fold.hpp states the contract) - one fold of a codeword (sc_rs_fold), and the prover of an opening: the
+// two claims (begin), the sumcheck rounds with the folds and the layer trees between them (prove), and the opened layer pairs
+// (query).  The rows are combined by engine/abi_ligero.inc, encoded by the row code's encoder, the rounds are sc_prover_round's
+// and the trees engine/merkle.inc's; what is new is rs_fold_kernel.
+
+// An opening in progress: the two combined rows until prove has run, then the layers U_1 .. U_(c-1) and their trees.
+struct sc_ligero_fold {
+  const sc_ctx* ctx = nullptr;
+  const sc_ligero* lg = nullptr;   // borrowed: must outlive the opening
+  bool proved = false;
+  std::vector<u64> z_lo;
+  PoolBuf rows;                    // u_z, then u_gamma: C words each
+  std::vector<PoolBuf> layers;     // layers[k] = U_(k+1), 2^(l0-k-1) words
+  std::vector<MerkleLevels> trees; // trees[k]: over the 2^(l0-k-2) leaves of U_(k+1)
+};
+
+namespace {
+
+// out = the fold of the 2^log_m words of U with alpha, as layer l0 - log_m of an opening whose layer 0 has 2^log_len0 words;
+// leaves != null: the digests of out's leaves go there too.  One launch
+int rs_fold_launch(sc_ctx* ctx, const u64* U, int log_m, int log_len0, u64 alpha, int log_in, u64* out, u32* leaves) {
+  const HostField hf(ctx->fp);
+  const TwoAdicRoot root = two_adic_root(ctx);
+  sc::RsFoldArgs a;
+  const u64 half = hf.inv(hf.add(hf.one(), hf.one()));
+  a.c1 = hf.mul(half, alpha);
+  a.c0 = hf.sub(half, a.c1);
+  a.inv_w4 = hf.neg(hf.pow(root.w_max, (u64)1 << (root.s - 2)));   // 1 / i = -i
+  a.log_len0 = log_len0;
+  a.shift = log_len0 - log_m;
+  a.hi = nullptr;
+  if (log_len0 >= sc::kRsFoldTwistMinLog) {
+    SC_TRY(rs_twist_tables(ctx, log_len0, &a.lo, &a.hi));
+  } else {
+    sc::RsRoots unused;
+    SC_TRY(rs_twiddles(ctx, log_len0, &a.lo, &unused));
+  }
+  const u64 M = (u64)1 << log_m;
+  const u32 quarter = (u32)(M / 4);
+  return launch_recorded(ctx, {SC_KIND_RS_FOLD, leaves ? 1 : 0, log_m, log_in, 8 * M, 4 * M + (leaves ? 8 * M : 0)}, "rs_fold_kernel", [&] {
+    SC_DISPATCH_FIELD(ctx, F, f, with_bool(leaves != nullptr, [&](auto H) {
+                        hipLaunchKernelGGL((sc::rs_fold_kernel<F, H>), dim3(strided_grid(ctx, quarter)), dim3(sc::kBlock), 0, ctx->stream, f, U,
+                                           out, a, quarter, leaves);
+                      }));
+  });
+}
+
+int fold_check(sc_ctx* ctx, const sc_ligero_fold* fd, const char* what) {
+  if (fd->ctx != ctx) return fail(ctx, SC_ERR_ARG, "%s: the opening belongs to another context", what);
+  return SC_OK;
+}
+
+struct ProverGuard {
+  sc_prover* p = nullptr;
+  ~ProverGuard() { sc_prover_destroy(p); }
+};
+struct FoldGuard {
+  sc_ligero_fold* p = nullptr;
+  ~FoldGuard() { delete p; }
+};
+
+}  // namespace
+
+extern "C" int sc_rs_fold(sc_ctx* ctx, const sc_table* u, uint64_t alpha, sc_table** out) {
+  if (!ctx || !out) return SC_ERR_ARG;
+  *out = nullptr;
+  SC_TRY(one_device_only(ctx, "sc_rs_fold"));
+  SC_TRY(check_table(ctx, u, "sc_rs_fold"));
+  if (u->len < 4) return fail(ctx, SC_ERR_ARG, "sc_rs_fold: a codeword of %zu words (at least 4)", u->len);
+  const int log_m = log2_of(u->len), s = two_adic_root(ctx).s;
+  if (log_m > sc::kRsLongMaxLog)
+    return fail(ctx, SC_ERR_UNSUPPORTED, "sc_rs_fold: a codeword of 2^%d words is longer than 2^%d", log_m, sc::kRsLongMaxLog);
+  if (log_m > s)
+    return fail(ctx, SC_ERR_UNSUPPORTED, "sc_rs_fold: p = %llu has 2-adicity %d: no root of unity of order 2^%d", (unsigned long long)ctx->fp.p,
+                s, log_m);
+  if (alpha >= ctx->fp.p) return fail(ctx, SC_ERR_ARG, "sc_rs_fold: alpha is not reduced");
+  SC_TRY(set_device(ctx));
+  TableBuf t;
+  SC_TRY(t.alloc(ctx, u->len / 2));
+  SC_TRY(rs_fold_launch(ctx, u->d, log_m, log_m, alpha, log_m, t->d, nullptr));
+  return table_done(ctx, t, hipSuccess, "sc_rs_fold", out);
+}
+
+extern "C" int sc_ligero_fold_begin(sc_ctx* ctx, const sc_ligero* lg, const uint64_t* point, const uint64_t* gamma, uint64_t claims[2],
+                                    sc_ligero_fold** out) {
+  if (!ctx || !out) return SC_ERR_ARG;
+  *out = nullptr;
+  if (!lg || !point || !gamma || !claims) return fail(ctx, SC_ERR_ARG, "sc_ligero_fold_begin: null pointer");
+  SC_TRY(one_device_only(ctx, "sc_ligero_fold_begin"));
+  SC_TRY(ligero_check(ctx, lg, "sc_ligero_fold_begin"));
+  if (lg->code != SC_CODE_RS)
+    return fail(ctx, SC_ERR_UNSUPPORTED, "sc_ligero_fold_begin: the expander code does not fold: a Reed-Solomon commitment is needed");
+  if (lg->c == 0)
+    return fail(ctx, SC_ERR_ARG, "sc_ligero_fold_begin: log_cols = 0 leaves nothing to fold: use the plain opening");
+  const size_t R = (size_t)1 << lg->r, C = (size_t)1 << lg->c;
+  const u64 p = ctx->fp.p;
+  for (int k = 0; k < lg->r + lg->c; ++k)
+    if (point[k] >= p) return fail(ctx, SC_ERR_ARG, "sc_ligero_fold_begin: coordinate %d of the point is not reduced", k);
+  for (size_t i = 0; i < R; ++i)
+    if (gamma[i] >= p) return fail(ctx, SC_ERR_ARG, "sc_ligero_fold_begin: gamma[%zu] is not reduced", i);
+  SC_TRY(set_device(ctx));
+  FoldGuard guard{new (std::nothrow) sc_ligero_fold};
+  sc_ligero_fold* fd = guard.p;
+  if (!fd) return fail(ctx, SC_ERR_OOM, "host allocation failed");
+  fd->ctx = ctx;
+  fd->lg = lg;
+  fd->z_lo.assign(point, point + lg->c);
+  // the weights of u_z - eq(z_hi, i), LE - then gamma
+  const HostField hf(ctx->fp);
+  std::vector<u64> w(2 * R);
+  w[0] = hf.one();
+  for (int k = 0; k < lg->r; ++k) {
+    const u64 r = point[lg->c + k];
+    for (size_t i = 0; i < (size_t)1 << k; ++i) {
+      const u64 hi = hf.mul(w[i], r);
+      w[i + ((size_t)1 << k)] = hi;
+      w[i] = hf.sub(w[i], hi);
+    }
+  }
+  std::copy(gamma, gamma + R, w.begin() + R);
+  SC_TRY(ligero_combine_device(ctx, lg, w.data(), 2, &fd->rows));
+  for (int m = 0; m < 2; ++m) {
+    sc_table row;   // (a view of the block: nothing to free)
+    row.d = fd->rows.get() + m * C;
+    row.len = C;
+    SC_TRY(sc_table_evaluate(ctx, &row, fd->z_lo.data(), (size_t)lg->c, SC_ORDER_LE, &claims[m]));
+  }
+  guard.p = nullptr;
+  *out = fd;
+  return SC_OK;
+}
+
+extern "C" int sc_ligero_fold_prove(sc_ctx* ctx, sc_ligero_fold* fd, uint64_t beta, sc_draw_fold_fn draw, void* user, uint64_t* evals,
+                                    uint8_t* roots, uint64_t* challenges, uint64_t* final_value) {
+  if (!ctx || !fd) return SC_ERR_ARG;
+  SC_TRY(fold_check(ctx, fd, "sc_ligero_fold_prove"));
+  const sc_ligero* lg = fd->lg;
+  const int c = lg->c, rho = lg->rho, n = lg->r + lg->c, l0 = c + rho;
+  if (!draw || !evals || !final_value || (c > 1 && !roots)) return fail(ctx, SC_ERR_ARG, "sc_ligero_fold_prove: null pointer");
+  if (fd->proved) return fail(ctx, SC_ERR_STATE, "sc_ligero_fold_prove: this opening has been proved already");
+  if (beta >= ctx->fp.p) return fail(ctx, SC_ERR_ARG, "sc_ligero_fold_prove: beta is not reduced");
+  SC_TRY(set_device(ctx));
+  const size_t C = (size_t)1 << c;
+  // m = u_z + beta u_gamma and eq(z_lo): the two tables of the sumcheck
+  TableBuf tm, teq;
+  {
+    PoolBuf m, eq;
+    SC_TRY(m.alloc(ctx, C));
+    const u64* rows = fd->rows.get();
+    SC_DISPATCH_FIELD(ctx, F, f,
+                      hipLaunchKernelGGL((sc::rs_fold_mix_kernel<F>), dim3(strided_grid(ctx, C)), dim3(sc::kBlock), 0, ctx->stream, f, rows,
+                                         rows + C, beta, (u32)C, m.get()));
+    if (hipGetLastError() != hipSuccess) {
+      poison(ctx);
+      return fail(ctx, SC_ERR_HIP, "rs_fold_mix_kernel launch failed");
+    }
+    SC_TRY(build_eq_table(ctx, fd->z_lo.data(), c, &eq));
+    SC_TRY(tm.wrap(ctx, std::move(m), C));
+    SC_TRY(teq.wrap(ctx, std::move(eq), C));
+  }
+  // U_0 = Enc(m): one row through the row code's encoder
+  PoolBuf u0;
+  SC_TRY(u0.alloc(ctx, (size_t)1 << l0));
+  SC_TRY(rs_encode_long_impl(ctx, tm->d, c, c, rho, u0));
+  const u64* cur = u0.get();
+  ProverGuard pr;
+  SC_TRY(sc_prover_create(ctx, tm.get(), teq.get(), &pr.p));
+  std::vector<PoolBuf> layers;
+  std::vector<MerkleLevels> trees;
+  u64 alpha = 0;
+  for (int i = 0; i < c; ++i) {
+    SC_TRY(sc_prover_round(pr.p, alpha, (size_t)i, evals + 3 * i));
+    uint8_t* root = i ? roots + 32 * (size_t)(i - 1) : nullptr;
+    if (i) sc::put_digest(root, trees.back().root);
+    alpha = draw(user, (size_t)i, evals + 3 * i, root);
+    if (alpha >= ctx->fp.p) return fail(ctx, SC_ERR_ARG, "sc_ligero_fold_prove: draw() returned an unreduced challenge");
+    if (challenges) challenges[i] = alpha;
+    // U_i -> U_(i+1); every layer but the last gets its tree
+    const int log_m = l0 - i;
+    PoolBuf next;
+    SC_TRY(next.alloc(ctx, (size_t)1 << (log_m - 1)));
+    if (i + 1 < c) {
+      MerkleLevels t;
+      SC_TRY(t.alloc(ctx, log_m - 2));
+      SC_TRY(rs_fold_launch(ctx, cur, log_m, l0, alpha, n, next, t.words()));
+      SC_TRY(merkle_finish(ctx, &t, 0, n));
+      u0.reset();   // (U_0 goes back to the pool once it is folded; a layer stays with `layers`)
+      cur = next.get();
+      layers.push_back(std::move(next));
+      trees.push_back(std::move(t));
+    } else {
+      SC_TRY(rs_fold_launch(ctx, cur, log_m, l0, alpha, n, next, nullptr));
+      SC_HIP(ctx, hipMemcpyAsync(final_value, next.get(), sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+      SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+  }
+  fd->layers = std::move(layers);
+  fd->trees = std::move(trees);
+  fd->rows.reset();
+  fd->proved = true;
+  return SC_OK;
+}
+
+// pairs[q][c-1][2] (Montgomery) and paths[q][P][32], P = sum_{i=1}^{c-1} (l0 - i - 1): the layers in order, each path bottom up
+extern "C" int sc_ligero_fold_query(sc_ctx* ctx, const sc_ligero_fold* fd, const uint64_t* q, size_t count, uint64_t* pairs, uint8_t* paths) {
+  if (!ctx || !fd) return SC_ERR_ARG;
+  SC_TRY(fold_check(ctx, fd, "sc_ligero_fold_query"));
+  if (!fd->proved) return fail(ctx, SC_ERR_STATE, "sc_ligero_fold_query: the opening has not been proved yet (sc_ligero_fold_prove)");
+  if (count == 0) return SC_OK;
+  const int c = fd->lg->c, l0 = c + fd->lg->rho, n = fd->lg->r + c;
+  if (!q || (c > 1 && (!pairs || !paths))) return fail(ctx, SC_ERR_ARG, "sc_ligero_fold_query: null array");
+  for (size_t k = 0; k < count; ++k)
+    if (q[k] >= (u64)1 << (l0 - 1))
+      return fail(ctx, SC_ERR_ARG, "sc_ligero_fold_query: index %llu of query %zu is not below L / 2 = 2^%d", (unsigned long long)q[k], k, l0 - 1);
+  if (c == 1) return SC_OK;
+  SC_TRY(set_device(ctx));
+  size_t P = 0;
+  for (int i = 1; i < c; ++i) P += (size_t)(l0 - i - 1);
+  // every layer's launch is queued, then one wait: per chunk of queries and layer i, chunk indices, 2 chunk words and
+  // chunk (l0 - i - 1) digests, the layers one behind the other
+  const size_t chunk = std::min<size_t>(count, 1024), layers = (size_t)(c - 1);
+  PoolBuf buf;
+  SC_TRY(buf.alloc(ctx, chunk * (3 * layers + 4 * P)));
+  u64* d_idx = buf;
+  u64* d_vals = d_idx + layers * chunk;
+  u32* d_sib = reinterpret_cast<u32*>(d_vals + 2 * layers * chunk);
+  std::vector<u64> idx(layers * chunk), vals(2 * layers * chunk);
+  std::vector<u32> hs(8 * P * chunk);
+  for (size_t q0 = 0; q0 < count; q0 += chunk) {
+    const size_t k = std::min(chunk, count - q0);
+    for (int i = 1; i < c; ++i)
+      for (size_t t = 0; t < k; ++t) idx[(size_t)(i - 1) * chunk + t] = q[q0 + t] & (((u64)1 << (l0 - i - 1)) - 1);
+    SC_HIP(ctx, hipMemcpyAsync(d_idx, idx.data(), layers * chunk * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
+    size_t first = 0;
+    for (int i = 1; i < c; ++i) {
+      // layer i as a 2 x len matrix: column j_i and its path, through the commitment's opening kernel
+      const int depth = l0 - i - 1;
+      const u64 len = (u64)1 << depth, moved = (u64)k * (16 + 32 * depth);
+      const size_t li = (size_t)(i - 1);
+      SC_TRY(launch_recorded(ctx, {SC_KIND_LIGERO, 2, (int)k, n, moved, moved}, "column_open_kernel", [&] {
+        hipLaunchKernelGGL(sc::column_open_kernel, dim3((unsigned)std::min<size_t>(k, (size_t)8 * ctx->num_cus)), dim3(sc::kBlock), 0, ctx->stream,
+                           (const u64*)fd->layers[li].get(), (const u32*)fd->trees[li].words(), (const u64*)(d_idx + li * chunk), (u32)k, (u64)2,
+                           (u32)len, depth, d_vals + 2 * li * chunk, d_sib + 8 * first * chunk);
+      }));
+      first += (size_t)depth;
+    }
+    SC_HIP(ctx, hipMemcpyAsync(vals.data(), d_vals, 2 * layers * chunk * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+    SC_HIP(ctx, hipMemcpyAsync(hs.data(), d_sib, 32 * P * chunk, hipMemcpyDeviceToHost, ctx->stream));
+    SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    first = 0;
+    for (int i = 1; i < c; ++i) {
+      const int depth = l0 - i - 1;
+      const size_t li = (size_t)(i - 1);
+      for (size_t t = 0; t < k; ++t) {
+        u64* dst = pairs + ((q0 + t) * layers + li) * 2;
+        dst[0] = vals[2 * (li * chunk + t)];
+        dst[1] = vals[2 * (li * chunk + t) + 1];
+      }
+      sc::put_paths(paths + q0 * P * 32, (int)P, (int)first, hs.data() + 8 * first * chunk, k, depth);
+      first += (size_t)depth;
+    }
+  }
+  return SC_OK;
+}
+
+extern "C" int sc_ligero_fold_destroy(sc_ctx* ctx, sc_ligero_fold* fd) {
+  if (!fd) return SC_OK;
+  if (!ctx || fd->ctx != ctx) return SC_ERR_ARG;
+  delete fd;
+  return SC_OK;
+}

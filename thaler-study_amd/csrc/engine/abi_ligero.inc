@@ -100,7 +100,7 @@ int rs_encode_impl(sc_ctx* ctx, const u64* in, int n, int c, int rho, u64* E) {
 }
 
 // lo[i] = w_L^i, i < 2^12, then hi[i] = w_L^(2^12 i), i < 2^(log_len - 12): the twist tables of this context for L = 2^log_len,
-// 2^12 + 2^(log_len - 12) host products at first use
+// log_len >= 12, 2^12 + 2^(log_len - 12) host products at first use
 int rs_twist_tables(sc_ctx* ctx, int log_len, const u64** lo, const u64** hi) {
   const HostField hf(ctx->fp);
   const size_t n_lo = (size_t)1 << sc::kRsTwistLoLog, n_hi = (size_t)1 << (log_len - sc::kRsTwistLoLog);
@@ -181,16 +181,12 @@ extern "C" int sc_ligero_shape(const sc_ligero* lg, size_t* log_rows, size_t* lo
   return SC_OK;
 }
 
-// out[m][k] = sum_i weights[m][i] w[i C + k]: the weights go to a pool buffer, one launch reads the table once (row ranges per
-// block), a second adds the ranges' partial sums
-extern "C" int sc_ligero_combine_rows(sc_ctx* ctx, const sc_ligero* lg, const uint64_t* weights, size_t count, uint64_t* out) {
-  if (!ctx || !lg) return SC_ERR_ARG;
-  SC_TRY(ligero_check(ctx, lg, "sc_ligero_combine_rows"));
-  if (count > (size_t)sc::kLigeroMaxCombine)
-    return fail(ctx, SC_ERR_ARG, "sc_ligero_combine_rows: %zu weight vectors (at most %d per call)", count, sc::kLigeroMaxCombine);
-  if (count == 0) return SC_OK;
-  if (!weights || !out) return fail(ctx, SC_ERR_ARG, "sc_ligero_combine_rows: null array");
-  SC_TRY(set_device(ctx));
+namespace {
+
+// d_out[m][k] = sum_i weights[m][i] w[i C + k], 1 <= count <= kLigeroMaxCombine, left on the device: the weights go to a pool
+// buffer, one launch reads the table once (row ranges per block), a second adds the ranges' partial sums.  Queued on the
+// context's stream: the caller drains it before `weights` (host memory) goes away
+int ligero_combine_device(sc_ctx* ctx, const sc_ligero* lg, const uint64_t* weights, size_t count, PoolBuf* out) {
   const u64 R = (u64)1 << lg->r, C = (u64)1 << lg->c;
   const int V = (lg->c >= 1 && (reinterpret_cast<uintptr_t>(lg->t->d) & 15) == 0) ? 2 : 1;
   const unsigned bx = (unsigned)((C / V + sc::kBlock - 1) / sc::kBlock);
@@ -218,6 +214,24 @@ extern "C" int sc_ligero_combine_rows(sc_ctx* ctx, const sc_ligero* lg, const ui
                         hipLaunchKernelGGL((sc::row_combine_sum_kernel<F>), dim3(strided_grid(ctx, words)), dim3(sc::kBlock), 0, ctx->stream, f,
                                            (const u64*)d_part.get(), (sc::u32)splits, (sc::u32)words, d_out.get()));
     }));
+  *out = std::move(d_out);
+  return SC_OK;
+}
+
+}  // namespace
+
+// out[m][k] = sum_i weights[m][i] w[i C + k]: ligero_combine_device, then the rows to the host
+extern "C" int sc_ligero_combine_rows(sc_ctx* ctx, const sc_ligero* lg, const uint64_t* weights, size_t count, uint64_t* out) {
+  if (!ctx || !lg) return SC_ERR_ARG;
+  SC_TRY(ligero_check(ctx, lg, "sc_ligero_combine_rows"));
+  if (count > (size_t)sc::kLigeroMaxCombine)
+    return fail(ctx, SC_ERR_ARG, "sc_ligero_combine_rows: %zu weight vectors (at most %d per call)", count, sc::kLigeroMaxCombine);
+  if (count == 0) return SC_OK;
+  if (!weights || !out) return fail(ctx, SC_ERR_ARG, "sc_ligero_combine_rows: null array");
+  SC_TRY(set_device(ctx));
+  PoolBuf d_out;
+  SC_TRY(ligero_combine_device(ctx, lg, weights, count, &d_out));
+  const size_t words = count << lg->c;
   SC_HIP(ctx, hipMemcpyAsync(out, d_out, words * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
   SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SC_OK;

@@ -263,6 +263,7 @@ __device__ __forceinline__ void transpose_to_pieces(ull2* __restrict__ lds, ull2
 #include "kernels/row_code.hpp"
 #include "kernels/ligero.hpp"
 #include "kernels/ligero_long.hpp"
+#include "kernels/rs_fold.hpp"
 #include "kernels/expander.hpp"
 #include "kernels/expander_long.hpp"
 #include "kernels/peer.hpp"

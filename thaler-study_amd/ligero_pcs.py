@@ -32,14 +32,21 @@ without two-adicity such as 2^64 - 59: any p > 63, log_cols <= 13.  Everything a
 entry j of expander_code.encode(u).  The distance of that code is not proved.  xc_encode_rows_long and
 Prover.commit_long(code="expander") (sc_xc_encode_rows_long, sc_ligero_commit_code_long) serve
 log_cols up to expander_code.LONG_MAX_LOG_COLS = 23; the Verifier's host encoding of the two combined rows then costs seconds
-at log_cols 14 - 15 and far more above."""
+at log_cols 14 - 15 and far more above.
+
+Folded openings (kernels/rs_fold.hpp states the contract): Prover.fold_begin, FoldVerifier and
+open_folded prove the combined row m = u_z + beta u_gamma instead of sending u_gamma and u_z - log_cols rounds of the product
+sumcheck over (m, eq(z[:c])) interleaved with log_cols folds of Enc(m) (sc_ligero_fold_*, one rs_fold_kernel launch per round),
+the folded layers committed with the same leaf and tree.  The opening no longer grows with 2^log_cols and the verifier does
+2 * 2^log_rows + log_cols products per query: fold_opening_bytes and fold_log_cols give its size and the shape that makes it
+smallest.  Reed-Solomon commitments with log_cols >= 1 only; the plain opening stays the default.  No security level is claimed."""
 import ctypes
 import hashlib
 
 import numpy as np
 
 from . import expander_code
-from ._lib import size_t, voidp
+from ._lib import DRAW_FOLD_FN, size_t, u64, voidp
 from .dense_mle import DenseMultilinearExtension, _u64p, _words
 from .relaxed_pcs import Error, EvalMismatch, MerkleMismatch, Path, _draw, node_digest
 
@@ -104,6 +111,22 @@ def opening_bytes(num_vars, log_cols, log_blowup, queries):
 def long_log_cols(num_vars, log_blowup, queries, max_log_len=LONG_MAX_LOG_LEN):
     """the log_cols in 0 .. min(num_vars, max_log_len - log_blowup) with the smallest opening (ties: the smaller)"""
     return min(range(min(num_vars, max_log_len - log_blowup) + 1), key=lambda c: (opening_bytes(num_vars, c, log_blowup, queries), c))
+
+
+def fold_opening_bytes(num_vars, log_cols, log_blowup, queries):
+    """bytes of a folded opening: per query two columns of 2^(n - c) words with their paths of c + log_blowup digests and, for
+    every layer i = 1 .. c - 1, a pair of words with a path of c + log_blowup - i - 1 digests; once, the c - 1 layer roots, the c
+    round polynomials of three words, and v, v_gamma and the final value"""
+    if log_cols < 1:
+        raise ValueError("a folded opening needs log_cols >= 1")
+    l0 = log_cols + log_blowup
+    per_query = 2 * (8 * (1 << (num_vars - log_cols)) + 32 * l0) + sum(16 + 32 * (l0 - i - 1) for i in range(1, log_cols))
+    return queries * per_query + 32 * (log_cols - 1) + 24 * log_cols + 24
+
+
+def fold_log_cols(num_vars, log_blowup, queries, max_log_len=LONG_MAX_LOG_LEN):
+    """the log_cols in 1 .. min(num_vars, max_log_len - log_blowup) with the smallest folded opening (ties: the smaller)"""
+    return min(range(1, min(num_vars, max_log_len - log_blowup) + 1), key=lambda c: (fold_opening_bytes(num_vars, c, log_blowup, queries), c))
 
 
 # ---- hashing (host) --------------------------------------------------------------------------------------------------
@@ -229,9 +252,94 @@ class Prover:
             out.append((int(idx[q]), [int(v) for v in values[q * R:(q + 1) * R]], ColumnPath(int(idx[q]), sib, self.field)))
         return out
 
+    def fold_begin(self, point, gamma):
+        """sc_ligero_fold_begin: a folded opening at `point` under the verifier's gamma; its .claims are (v, v_gamma)"""
+        if len(point) != self.num_vars:
+            raise ValueError("the point has %d coordinates, the polynomial %d variables" % (len(point), self.num_vars))
+        if len(gamma) != 1 << self.log_rows:
+            raise ValueError("gamma must have 2^log_rows = %d words" % (1 << self.log_rows))
+        z, g = _words(point), _words(gamma)
+        claims = np.zeros(2, dtype=np.uint64)
+        h = voidp()
+        self.ctx.check(self.ctx.lib.sc_ligero_fold_begin(self.ctx.h, self.h, _u64p(z), _u64p(g), _u64p(claims), ctypes.byref(h)))
+        return FoldOpening(self, h, (int(claims[0]), int(claims[1])))
+
     def close(self):
         if self.h and self.ctx.h:
             self.ctx.lib.sc_ligero_destroy(self.ctx.h, self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def rs_fold(ctx, table, alpha):
+    """sc_rs_fold: one fold of a codeword of 2^l words (2 <= l <= 24) with alpha, a device table of half the length"""
+    h = voidp()
+    ctx.check(ctx.lib.sc_rs_fold(ctx.h, table.h, int(alpha), ctypes.byref(h)))
+    return DenseMultilinearExtension(ctx, h)
+
+
+class FoldOpening:
+    """sc_ligero_fold_*: the prover's side of one folded opening (Prover.fold_begin): .claims, then prove, then query"""
+
+    def __init__(self, prover, handle, claims):
+        self.prover, self.ctx, self.h, self.claims = prover, prover.ctx, handle, claims
+        self.log_cols, self.log_len = prover.log_cols, prover.log_cols + prover.log_blowup
+
+    def prove(self, beta, draw):
+        """the log_cols rounds: draw(round, [H(0), H(1), H(2)], root_i or None) returns alpha_i.  Returns (rounds, roots,
+        challenges, final value): rounds[i] the three sums, roots[i - 1] = root_i for i = 1 .. log_cols - 1"""
+        c = self.log_cols
+        failure = []
+
+        def cb(_user, i, e, root):
+            try:
+                return int(draw(i, [int(e[0]), int(e[1]), int(e[2])], ctypes.string_at(root, 32) if root else None))
+            except BaseException as exc:   # (an exception must not cross the C frames: the call ends and it is raised again below)
+                failure.append(exc)
+                return self.ctx.field.p
+        evals, challenges = np.zeros(3 * c, dtype=np.uint64), np.zeros(c, dtype=np.uint64)
+        roots = (ctypes.c_uint8 * max(1, 32 * (c - 1)))()
+        final = u64()
+        rc = self.ctx.lib.sc_ligero_fold_prove(self.ctx.h, self.h, int(beta), DRAW_FOLD_FN(cb), None, _u64p(evals), roots, _u64p(challenges),
+                                               ctypes.byref(final))
+        if failure:
+            raise failure[0]
+        self.ctx.check(rc)
+        raw = bytes(roots)
+        return ([[int(x) for x in evals[3 * i:3 * i + 3]] for i in range(c)], [raw[32 * i:32 * i + 32] for i in range(c - 1)],
+                [int(x) for x in challenges], int(final.value))
+
+    def query(self, indices):
+        """[(q, column q, column q + L / 2, layers)] for every index q < L / 2: the columns as Prover.open_columns gives them,
+        layers[i - 1] = ((U_i[j_i], U_i[j_i + M_i / 2]), siblings) for i = 1 .. log_cols - 1"""
+        idx = _words(indices)
+        count, c, l0 = idx.size, self.log_cols, self.log_len
+        depths = [l0 - i - 1 for i in range(1, c)]
+        P = sum(depths)
+        pairs = np.zeros(max(1, count * (c - 1) * 2), dtype=np.uint64)
+        paths = (ctypes.c_uint8 * max(1, count * P * 32))()
+        self.ctx.check(self.ctx.lib.sc_ligero_fold_query(self.ctx.h, self.h, _u64p(idx) if count else None, count, _u64p(pairs), paths))
+        half = 1 << (l0 - 1)
+        cols = self.prover.open_columns([int(q) for q in idx] + [int(q) + half for q in idx])
+        raw = bytes(paths)
+        out = []
+        for k in range(count):
+            layers, at = [], k * P
+            for i, depth in enumerate(depths):
+                pair = (int(pairs[(k * (c - 1) + i) * 2]), int(pairs[(k * (c - 1) + i) * 2 + 1]))
+                layers.append((pair, [raw[(at + l) * 32:(at + l + 1) * 32] for l in range(depth)]))
+                at += depth
+            out.append((int(idx[k]), cols[k], cols[count + k], layers))
+        return out
+
+    def close(self):
+        if self.h and self.ctx.h:
+            self.ctx.lib.sc_ligero_fold_destroy(self.ctx.h, self.h)
         self.h = None
 
     def __del__(self):
@@ -327,3 +435,181 @@ class Verifier:
         for a, b in zip(self.u_z, eq_weights(F, list(point)[:self.log_cols])):
             value = F.add(value, F.mul(a, b))
         return value
+
+
+# ---- the verifier of a folded opening --------------------------------------------------------------------------------
+
+class FoldMismatch(Error):
+    """two opened layers disagree: the fold of a layer's pair is not the next layer's word, or the last fold is not the final value"""
+
+    def __init__(self, query, layer, folded, found):
+        super().__init__("Query %d: layer %d folds to %d, the next layer holds %d" % (query, layer, folded, found))
+        self.query, self.layer, self.folded, self.found = query, layer, folded, found
+
+
+class RoundMismatch(Error):
+    """H(0) + H(1) of a round polynomial is not the running claim of the sumcheck"""
+
+    def __init__(self, round_index, claim, total):
+        super().__init__("Round %d: H(0) + H(1) is %d, the claim is %d" % (round_index, total, claim))
+        self.round, self.claim, self.total = round_index, claim, total
+
+
+def pair_digest(field, pair):
+    """the leaf of a layer: the column leaf of its two words"""
+    return column_digest(field, pair)
+
+
+class FoldVerifier:
+    """The verifier of one folded opening.  Pure host code: draw_gamma, receive_claims, draw_beta, round (once per round, in
+    order), receive_final, draw_queries, verify - in that order."""
+
+    def __init__(self, field, num_vars, log_cols, log_blowup, root, queries):
+        if not 1 <= log_cols <= num_vars or log_blowup not in (1, 2):
+            raise ValueError("log_cols must be in 1..num_vars (log_cols = 0: the plain opening) and log_blowup 1 or 2")
+        self.field, self.num_vars, self.log_cols, self.log_blowup = field, num_vars, log_cols, log_blowup
+        self.log_rows = num_vars - log_cols
+        self.log_len = log_cols + log_blowup
+        self.root, self.queries = bytes(root), int(queries)
+        self.omega = root_of_unity(field, self.log_len)
+        self.half = field.inv(field.add(field.one, field.one))
+        self.gamma = self.claims = self.beta = self.claim = self.final = self.indices = None
+        self.rounds, self.roots, self.alphas = [], [], []
+
+    def draw_gamma(self, rng):
+        self.gamma = [_draw(self.field, rng) for _ in range(1 << self.log_rows)]
+        return list(self.gamma)
+
+    def receive_claims(self, v, v_gamma):
+        if self.gamma is None:
+            raise Error("receive_claims before draw_gamma")
+        self.claims = (int(v), int(v_gamma))
+
+    def draw_beta(self, rng):
+        if self.claims is None:
+            raise Error("draw_beta before receive_claims: beta must be drawn after the prover has sent v and v_gamma")
+        F = self.field
+        self.beta = _draw(F, rng)
+        self.claim = F.add(self.claims[0], F.mul(self.beta, self.claims[1]))
+        return self.beta
+
+    def _at(self, evals, x):
+        """the quadratic through (0, e0), (1, e1), (2, e2) at x"""
+        F = self.field
+        e0, e1, e2 = evals
+        two = F.add(F.one, F.one)
+        xm1, xm2 = F.sub(x, F.one), F.sub(x, two)
+        l0 = F.mul(F.mul(xm1, xm2), self.half)
+        l1 = F.neg(F.mul(x, xm2))
+        l2 = F.mul(F.mul(x, xm1), self.half)
+        return F.add(F.add(F.mul(e0, l0), F.mul(e1, l1)), F.mul(e2, l2))
+
+    def round(self, i, evals, root, rng):
+        """round i's message: the three sums and, for i >= 1, root_i.  Returns alpha_i"""
+        F = self.field
+        if self.beta is None or i != len(self.rounds) or i >= self.log_cols:
+            raise Error("round %d out of order" % i)
+        if (root is None) != (i == 0):
+            raise Error("round 0 carries no root, every later round one")
+        evals = [int(x) for x in evals]
+        total = F.add(evals[0], evals[1])
+        if total != self.claim:
+            raise RoundMismatch(i, self.claim, total)
+        alpha = _draw(F, rng)
+        self.claim = self._at(evals, alpha)
+        self.rounds.append(evals)
+        if i:
+            self.roots.append(bytes(root))
+        self.alphas.append(alpha)
+        return alpha
+
+    def receive_final(self, final):
+        if len(self.rounds) != self.log_cols:
+            raise Error("receive_final before the last round")
+        self.final = int(final)
+
+    def draw_queries(self, rng):
+        """`queries` indices in [0, L / 2), with replacement; only after the prover is bound to every layer and the final value"""
+        if self.final is None:
+            raise Error("draw_queries before receive_final: the indices must be drawn after the prover has sent every root and the final value")
+        half = 1 << (self.log_len - 1)
+        self.indices = [rng.randrange(half) if hasattr(rng, "randrange") else self.field.to_int(rng.draw()) % half for _ in range(self.queries)]
+        return list(self.indices)
+
+    def _fold(self, pair, alpha, layer, j):
+        """the fold of layer `layer`'s pair at x = w_(l0 - layer)^j"""
+        F = self.field
+        L = 1 << self.log_len
+        xinv = F.from_int(pow(F.to_int(self.omega), (L - (j << layer)) % L, F.p))
+        even = F.mul(F.add(pair[0], pair[1]), self.half)
+        odd = F.mul(F.mul(F.sub(pair[0], pair[1]), self.half), xinv)
+        return F.add(even, F.mul(alpha, F.sub(odd, even)))
+
+    def verify(self, point, openings):
+        """check the last round against the final value and every query's openings; returns v, the value of the committed
+        polynomial at `point`"""
+        F = self.field
+        c, l0 = self.log_cols, self.log_len
+        if self.indices is None:
+            raise Error("verify before draw_queries")
+        if len(point) != self.num_vars:
+            raise Error("the point has %d coordinates, the polynomial %d variables" % (len(point), self.num_vars))
+        if len(openings) != len(self.indices):
+            raise MerkleMismatch("%d openings for %d drawn indices" % (len(openings), len(self.indices)))
+        # H_(c-1)(alpha_(c-1)) = final * eq(z_lo, alpha)
+        eq = F.one
+        for z, a in zip(list(point)[:c], self.alphas):
+            za = F.mul(z, a)
+            eq = F.mul(eq, F.add(F.sub(F.sub(F.one, z), a), F.add(za, za)))
+        if F.mul(self.final, eq) != self.claim:
+            raise EvalMismatch(F.mul(self.final, eq), self.claim)
+        weights = [F.add(e, F.mul(self.beta, g)) for e, g in zip(eq_weights(F, list(point)[c:]), self.gamma)]
+        half = 1 << (l0 - 1)
+        for k, (want, opening) in enumerate(zip(self.indices, openings)):
+            q, col_lo, col_hi, layers = opening
+            if q != want or len(layers) != c - 1:
+                raise MerkleMismatch("the opening is of index %d, the drawn index is %d" % (q, want))
+            pair = []
+            for index, (j, values, path) in ((want, col_lo), (want + half, col_hi)):
+                if j != index or path.index != index:
+                    raise MerkleMismatch("the opening is of column %d, the drawn column is %d" % (j, index))
+                if len(values) != 1 << self.log_rows or len(path.siblings) != l0:
+                    raise MerkleMismatch("an opening of the wrong shape")
+                if not ColumnPath(index, path.siblings, F).verify_column(self.root, values):
+                    raise MerkleMismatch("the opening of column %d does not lead to the committed root" % index)
+                u = 0
+                for wt, val in zip(weights, values):
+                    u = F.add(u, F.mul(wt, int(val)))
+                pair.append(u)                                    # U_0[index]
+            for i in range(c):
+                j = want % (1 << (l0 - i - 1))                    # layer i's pair sits at (j, j + M_i / 2)
+                folded = self._fold(pair, self.alphas[i], i, j)
+                if i == c - 1:
+                    if folded != self.final:
+                        raise FoldMismatch(k, i, folded, self.final)
+                    break
+                nxt, siblings = layers[i]
+                nxt = (int(nxt[0]), int(nxt[1]))
+                depth = l0 - i - 2
+                jn = want % (1 << depth)
+                if len(siblings) != depth or Path(jn, siblings).root_from_digest(pair_digest(F, nxt)) != self.roots[i]:
+                    raise MerkleMismatch("query %d: the opening of layer %d does not lead to its root" % (k, i + 1))
+                found = nxt[0] if j < (1 << depth) else nxt[1]
+                if folded != found:
+                    raise FoldMismatch(k, i, folded, found)
+                pair = nxt
+        return self.claims[0]
+
+
+def open_folded(prover, verifier, point, rng):
+    """the whole exchange of a folded opening between a Prover and a FoldVerifier; returns what verify returns"""
+    gamma = verifier.draw_gamma(rng)
+    opening = prover.fold_begin(point, gamma)
+    try:
+        verifier.receive_claims(*opening.claims)
+        beta = verifier.draw_beta(rng)
+        _, _, _, final = opening.prove(beta, lambda i, evals, root: verifier.round(i, evals, root, rng))
+        verifier.receive_final(final)
+        return verifier.verify(point, opening.query(verifier.draw_queries(rng)))
+    finally:
+        opening.close()

@@ -35,6 +35,12 @@ integers: Goldilocks products do not fit int64), at (20, 10, 1) only.
         the device time of every launch, the gathers per second of the level launches, their sum against xc_encode_rows_kernel,
         column_leaf_kernel at both widths, the commit's wall time, and the wall time and size of a 64-column opening at both
         widths; writes <out>/expander_long_timing.json and <out>/expander_long_summary.md.
+  python tools/ligero_timing.py --fold [--reps 5]
+        folded openings (sc_ligero_fold_*) at (n, rho) = (24, 1), (26, 1), (28, 1) with the shape
+        fold_log_cols picks for 128 queries, Goldilocks, in ONE child process: the device time of every rs_fold_kernel launch
+        and its rate on the record's bytes against the 6.29 TB/s copy rate, the wall time of begin, prove and query against the
+        wall time of the plain opening (sc_ligero_combine_rows + sc_ligero_open_columns) of the same commitment, and the wall
+        time of FoldVerifier.verify; writes <out>/ligero_fold_timing.json and <out>/ligero_fold_summary.md.
 """
 import argparse
 import glob
@@ -58,6 +64,8 @@ LONG_SHAPES = ((24, 16, 1), (26, 17, 1), (26, 16, 2), (28, 17, 1))
 XC_LONG_SHAPES = ((24, 16), (26, 17), (28, 17))
 XC_LONG_KERNELS = {0: "copy", 1: "down", 2: "inner", 3: "up"}
 P59 = 2**64 - 59
+FOLD_SHAPES = ((24, 1), (26, 1), (28, 1))
+FOLD_QUERIES = 128
 
 
 def _timed(ctx, fn, reps):
@@ -233,6 +241,118 @@ def run_xc_long(reps):
     return out
 
 
+def run_fold(reps):
+    """--fold: per shape the folded opening beside the plain opening of the same commitment"""
+    import ctypes
+    import random
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    from __graft_entry__ import load_package
+    pkg = load_package()
+    lp = pkg.ligero_pcs
+    ctx = pkg.Context(pkg.Field(pkg.GOLDILOCKS), device=0)
+    F = ctx.field
+    out = {"step": "fold", "queries": FOLD_QUERIES, "shapes": {}}
+    for n, rho in FOLD_SHAPES:
+        c = lp.fold_log_cols(n, rho, FOLD_QUERIES)
+        t = pkg.DenseMultilinearExtension.generate(ctx, 0x11CE0000 + n, n)
+        prover = lp.Prover.commit_long(ctx, t, c, rho)
+        rng = random.Random(n)
+        point = [F.rand(rng) for _ in range(n)]
+        gamma = [F.rand(rng) for _ in range(1 << (n - c))]
+        alphas = [F.rand(rng) for _ in range(c)]
+        beta = F.rand(rng)
+        indices = [rng.randrange(1 << (c + rho - 1)) for _ in range(FOLD_QUERIES)]
+        # the plain opening: the two combined rows to the host (the C call: no Python lists of 2^c words), 128 columns
+        weights = np.ascontiguousarray(np.array([gamma, lp.eq_weights(F, point[c:])], dtype=np.uint64).reshape(-1))
+        rows = np.zeros(2 << c, dtype=np.uint64)
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        cols = [rng.randrange(1 << (c + rho)) for _ in range(FOLD_QUERIES)]
+
+        def plain():
+            ctx.check(ctx.lib.sc_ligero_combine_rows(ctx.h, prover.h, weights.ctypes.data_as(u64p), 2, rows.ctypes.data_as(u64p)))
+            prover.open_columns(cols)
+        walls = {"begin": [], "prove": [], "query": [], "plain": []}
+        log = []
+        for rep in range(reps + 3):             # two warm-up runs, `reps` timed ones, one with the launch log on
+            timed, logged = 2 <= rep < reps + 2, rep == reps + 2
+            t0 = time.perf_counter()
+            opening = prover.fold_begin(point, gamma)
+            t1 = time.perf_counter()
+            if logged:
+                ctx.set_option("time_kernels", 1)
+                ctx.launch_log()
+            opening.prove(beta, lambda i, e, root: alphas[i])
+            t2 = time.perf_counter()
+            if logged:
+                log = ctx.launch_log()
+                ctx.set_option("time_kernels", 0)
+            opened = opening.query(indices)
+            t3 = time.perf_counter()
+            opening.close()
+            plain()
+            t4 = time.perf_counter()
+            if timed:
+                for key, a, b in (("begin", t0, t1), ("prove", t1, t2), ("query", t2, t3), ("plain", t3, t4)):
+                    walls[key].append(b - a)
+        # the verifier, on the device prover's messages
+        v = lp.FoldVerifier(F, n, c, rho, prover.root(), FOLD_QUERIES)
+        opening = prover.fold_begin(point, v.draw_gamma(rng))
+        v.receive_claims(*opening.claims)
+        final = opening.prove(v.draw_beta(rng), lambda i, e, root: v.round(i, e, root, rng))[3]
+        v.receive_final(final)
+        opened = opening.query(v.draw_queries(rng))
+        t0 = time.perf_counter()
+        value = v.verify(point, opened)
+        verify_s = time.perf_counter() - t0
+        opening.close()
+        assert value == t.evaluate(point), "the folded opening was accepted with a wrong value"
+        prover.close()
+        folds = [r for r in log if r["kind"] == "rs_fold"]
+        out["shapes"]["%d,%d,%d" % (n, c, rho)] = {
+            "log_cols": c, "fold_opening_bytes": lp.fold_opening_bytes(n, c, rho, FOLD_QUERIES),
+            "plain_opening_bytes_same_shape": lp.opening_bytes(n, c, rho, FOLD_QUERIES),
+            "plain_opening_bytes_best_shape": lp.opening_bytes(n, lp.long_log_cols(n, rho, FOLD_QUERIES), rho, FOLD_QUERIES),
+            "launches": [{"kf": r["kf"], "ks": r["ks"], "ms": r["ms"], "bytes": r["bytes_read"] + r["bytes_written"]} for r in folds],
+            "fold_device_ms": sum(r["ms"] for r in folds),
+            "prove_device_ms": {k: sum(r["ms"] for r in log if r["kind"] == k) for k in sorted({r["kind"] for r in log})},
+            "wall_ms": {k: statistics.median(w) * 1e3 for k, w in walls.items()}, "verify_wall_ms": verify_s * 1e3}
+        del t
+    return out
+
+
+def fold_summary(res):
+    step = res["steps"]["fold"]
+    lines = ["# Folded Ligero openings on one MI355X: rs_fold_kernel, the prover's three calls, the host verifier", "",
+             "Measured by `python tools/ligero_timing.py --fold --reps %d`: every figure comes from ONE process.  Goldilocks, tables from "
+             "`sc_table_generate`, %d queries, the shape `fold_log_cols` picks.  Device times: HIP events of the launch log, option "
+             "`time_kernels`, one instrumented run; wall times: medians after two warm-up runs, Python wrappers included.  A fold of "
+             "M words reads 8 M bytes and writes 4 M, plus 8 M of digests where it hashes (every launch but the last of an opening); "
+             "the yardstick is the chip's measured copy rate, 6.29 TB/s." % (res["reps"], step["queries"]), "",
+             "## Every rs_fold_kernel launch of one opening", "",
+             "| (n, c, rho) | log2 M | hashed | device ms | bytes read + written | TB/s | of the 6.29 TB/s copy rate |", "|---|---|---|---|---|---|---|"]
+    for key, row in step["shapes"].items():
+        for r in row["launches"]:
+            bps = r["bytes"] / (r["ms"] * 1e-3) if r["ms"] > 0 else float("nan")
+            lines.append("| (%s) | %d | %s | %.4f | %d | %.3f | %.1f %% |" % (key.replace(",", ", "), r["ks"], "yes" if r["kf"] else "no", r["ms"],
+                                                                         r["bytes"], bps / 1e12, 100 * bps / COPY_BPS))
+    lines += ["", "## The opening: folded against plain, same commitment", "",
+              "| (n, c, rho) | begin wall ms | prove wall ms | query wall ms | folded total ms | plain (combine + open_columns) wall ms | "
+              "all rs_fold launches device ms | FoldVerifier.verify wall ms | folded opening bytes | plain bytes at this shape | plain bytes at its best shape |",
+              "|---|---|---|---|---|---|---|---|---|---|---|"]
+    for key, row in step["shapes"].items():
+        w = row["wall_ms"]
+        lines.append("| (%s) | %.2f | %.2f | %.2f | %.2f | %.2f | %.3f | %.1f | %d | %d | %d |" % (
+            key.replace(",", ", "), w["begin"], w["prove"], w["query"], w["begin"] + w["prove"] + w["query"], w["plain"], row["fold_device_ms"],
+            row["verify_wall_ms"], row["fold_opening_bytes"], row["plain_opening_bytes_same_shape"], row["plain_opening_bytes_best_shape"]))
+    lines += ["", "## Device time of one prove call, by launch kind (ms)", ""]
+    for key, row in step["shapes"].items():
+        lines.append("- (%s): " % key.replace(",", ", ") + ", ".join("%s %.3f" % (k, v) for k, v in row["prove_device_ms"].items()))
+    if res.get("notes"):
+        lines += ["", "## What binds", ""] + res["notes"]
+    return "\n".join(lines) + "\n"
+
+
 def xc_long_summary(res):
     fields = (("gold", "Goldilocks"), ("p59", "2^64 - 59"))
     lines = ["# Expander-code rows longer than the LDS on one MI355X: levels through global memory beside the in-LDS encoder", "",
@@ -382,7 +502,8 @@ def summary(res):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--step", choices=("encode", "commit", "expander", "long", "xc_long"))
+    ap.add_argument("--step", choices=("encode", "commit", "expander", "long", "xc_long", "fold"))
+    ap.add_argument("--fold", action="store_true", help="folded openings beside the plain opening (ligero_fold_summary.md)")
     ap.add_argument("--long", action="store_true", help="rows longer than the LDS beside the in-LDS encoder (ligero_long_summary.md)")
     ap.add_argument("--code", choices=("rs", "expander"), default="rs", help="expander: the expander code beside Reed-Solomon (expander_summary.md)")
     ap.add_argument("--reps", type=int, default=10)
@@ -395,8 +516,10 @@ def main():
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
     path = os.path.join(args.out, "ligero_timing.json")
-    if args.long and not args.step:
+    if (args.long or args.fold) and not args.step:
         step, stem, render = ("xc_long", "expander_long", xc_long_summary) if args.code == "expander" else ("long", "ligero_long", long_summary)
+        if args.fold:
+            step, stem, render = "fold", "ligero_fold", fold_summary
         long_path = os.path.join(args.out, stem + "_timing.json")
         if args.summary_only:
             with open(long_path) as fh:
@@ -412,6 +535,10 @@ def main():
                 json.dump(res, fh, indent=1)
         with open(os.path.join(args.out, stem + "_summary.md"), "w") as fh:
             fh.write(render(res))
+        if args.fold:
+            print(json.dumps({k: {"fold_device_ms": round(row["fold_device_ms"], 3), **{t: round(v, 2) for t, v in row["wall_ms"].items()}}
+                              for k, row in res["steps"][step]["shapes"].items()}))
+            return
         print(json.dumps({k: {t: round(v["encode_device_ms"], 3) for t, v in row.items()} for k, row in res["steps"][step]["shapes"].items()}))
         return
     if args.summary_only or args.cpu_only:
@@ -425,7 +552,7 @@ def main():
             fh.write(summary(res))
         return
     if args.step:
-        runs = {"expander": run_expander, "long": run_long, "xc_long": run_xc_long}
+        runs = {"expander": run_expander, "long": run_long, "xc_long": run_xc_long, "fold": run_fold}
         print(json.dumps(runs[args.step](args.reps) if args.step in runs else run_step(args.step, args.reps)))
         return
     if args.code == "expander":
