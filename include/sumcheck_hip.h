@@ -249,6 +249,9 @@ int sc_ctx_kernel_time(sc_ctx* ctx, double out[2], int reset);
 #define SC_KIND_RS_FOLD 24     /* rs_fold_kernel: one fold of a Reed-Solomon codeword of M = 2^ks words (sc_rs_fold, sc_ligero_fold_prove), one launch; kf = 1 if
                                 * it also hashed the leaves of the folded codeword's tree, else 0; log_in = n (sc_rs_fold: ks); it reads 8 * M bytes
                                 * and writes 4 * M, plus 8 * M of digests with kf = 1.  The tree levels above the leaves are SC_KIND_MERKLE records */
+#define SC_KIND_RS_FOLD_MANY 25 /* rs_fold_many_kernel: A = kf successive folds of a Reed-Solomon codeword of M = 2^ks words in one launch (sc_rs_fold_many,
+                                * sc_ligero_fold_prove on an opening begun with a schedule); log_in = n (sc_rs_fold_many: ks); it reads 8 * M bytes and
+                                * writes 8 * M / 2^A, plus 32 bytes per leaf of the next stage's tree when it hashed them */
 typedef struct sc_launch_record {
   int32_t kind;           /* SC_KIND_* */
   int32_t kf, ks;         /* variables folded / rounds served (meaning per kind above) */
@@ -639,6 +642,27 @@ int sc_ligero_fold_prove(sc_ctx* ctx, sc_ligero_fold* fd, uint64_t beta, sc_draw
  * paths[q][P][32], P = sum_{i=1}^{c-1} (l0 - i - 1): the layers in order, each path bottom up.  c = 1: nothing is written. */
 int sc_ligero_fold_query(sc_ctx* ctx, const sc_ligero_fold* fd, const uint64_t* q, size_t count, uint64_t* pairs, uint8_t* paths);
 int sc_ligero_fold_destroy(sc_ctx* ctx, sc_ligero_fold* fd);
+
+/* ---- staged folded openings: up to three variables folded per committed layer ---------------
+ * A schedule a_0 .. a_(S-1), 1 <= a_s <= 3, sum a_s = c: stage s starts at round i_s = a_0 + .. + a_(s-1) and owns the layer
+ * U_(i_s) of M_s = 2^(l0 - i_s) words; the tree of a stage s >= 1 has M_s / 2^(a_s) leaves, leaf j = the column leaf of the words
+ * U[j + t M_s / 2^(a_s)], t < 2^(a_s); a stage's fold is a_s successive folds of the opening above, bit for bit, in one launch
+ * (SC_KIND_RS_FOLD_MANY).  kernels/rs_fold.hpp states the contract.  No security level is claimed, and the number of queries an
+ * arity needs is not analysed.  On a handle begun with a schedule:
+ *   sc_ligero_fold_prove  `draw` gets a non-NULL root exactly at the rounds i_s, s >= 1; roots = 32 (S - 1) bytes; one fold launch
+ *                         and one tree per stage.
+ *   sc_ligero_fold_query  q < L / 2^(a_0); pairs[q][W], W = sum_{s>=1} 2^(a_s): the words of leaf j_s = q mod (M_s / 2^(a_s)) of every
+ *                         stage s >= 1 in order; paths[q][P][32], P = sum_{s>=1} (l0 - i_s - a_s).  The 2^(a_0) columns
+ *                         q + t L / 2^(a_0) come from sc_ligero_open_columns.
+ * sc_ligero_fold_begin is the schedule of c ones.  SC_ERR_ARG besides the above: a null or empty schedule, an entry outside
+ * 1 .. 3, a sum other than c; sc_rs_fold_many: count outside 1 .. 3, fewer than 2^(count + 1) words, an unreduced alpha. */
+
+/* count = 1 .. 3 successive folds in one launch: u holds M = 2^l words, count + 1 <= l <= min(24, s); *out = a new table of
+ * M / 2^count words, word for word what `count` calls of sc_rs_fold give. */
+int sc_rs_fold_many(sc_ctx* ctx, const sc_table* u, const uint64_t* alphas, size_t count, sc_table** out);
+/* sc_ligero_fold_begin with the schedule arities[0 .. stages) stored in the opening */
+int sc_ligero_fold_begin_staged(sc_ctx* ctx, const sc_ligero* lg, const uint64_t* point, const uint64_t* gamma, const int32_t* arities,
+                                size_t stages, uint64_t claims[2], sc_ligero_fold** out);
 
 /* ---- gkr_protocol::circuit::Circuit on the device, and the whole GKR prover over it ----------------------------------
  * A circuit lives on ONE context of one device and one rank: sharded contexts (world > 1) and multi-device handles get

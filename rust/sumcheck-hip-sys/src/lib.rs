@@ -530,6 +530,8 @@ extern "C" {
     ) -> c_int;
     /// one fold of a Reed-Solomon codeword of 2^l words (2 <= l <= 24) with alpha: one launch, SC_KIND_RS_FOLD (24)
     pub fn sc_rs_fold(ctx: *mut sc_ctx, u: *const sc_table, alpha: u64, out: *mut *mut sc_table) -> c_int;
+    /// `count` = 1 .. 3 successive folds of a codeword of 2^l words (count + 1 <= l <= 24) in one launch, SC_KIND_RS_FOLD_MANY (25)
+    pub fn sc_rs_fold_many(ctx: *mut sc_ctx, u: *const sc_table, alphas: *const u64, count: usize, out: *mut *mut sc_table) -> c_int;
     /// a folded opening of a Reed-Solomon commitment at `point`: claims = (v, v_gamma); the combined rows stay on the device
     pub fn sc_ligero_fold_begin(
         ctx: *mut sc_ctx,
@@ -539,7 +541,18 @@ extern "C" {
         claims: *mut u64,
         out: *mut *mut sc_ligero_fold,
     ) -> c_int;
-    /// the c sumcheck rounds with a fold and a layer tree between them: evals 3 c words, roots 32 (c - 1) bytes, challenges c words or null
+    /// `sc_ligero_fold_begin` with a schedule: `stages` arities in 1 ..= 3 that sum to log_cols; prove and query then work per stage
+    pub fn sc_ligero_fold_begin_staged(
+        ctx: *mut sc_ctx,
+        lg: *const sc_ligero,
+        point: *const u64,
+        gamma: *const u64,
+        arities: *const i32,
+        stages: usize,
+        claims: *mut u64,
+        out: *mut *mut sc_ligero_fold,
+    ) -> c_int;
+    /// the c sumcheck rounds with a fold and a layer tree per stage: evals 3 c words, roots 32 (S - 1) bytes, challenges c words or null
     pub fn sc_ligero_fold_prove(
         ctx: *mut sc_ctx,
         fd: *mut sc_ligero_fold,
@@ -551,7 +564,7 @@ extern "C" {
         challenges: *mut u64,
         final_value: *mut u64,
     ) -> c_int;
-    /// the opened layer pairs of `count` indices below L / 2: pairs count x (c - 1) x 2 words, paths count x P x 32 bytes
+    /// the opened leaves of `count` indices below L / 2^a_0: pairs count x sum_(s>=1) 2^a_s words, paths count x P x 32 bytes
     pub fn sc_ligero_fold_query(
         ctx: *mut sc_ctx,
         fd: *const sc_ligero_fold,

@@ -50,7 +50,7 @@ class ScLaunchRecord(ctypes.Structure):
 
 
 KIND_NAMES = {0: "pass", 2: "evaluate", 3: "fold", 4: "fix_low", 5: "fold_be", 6: "coldot", 7: "gkr", 8: "matsq", 10: "grid_pass", 11: "gram_pass", 13: "wfold_pass", 14: "circuit", 15: "matmul", 16: "batch_pass",
-              17: "grid_extend", 18: "merkle", 19: "rs_encode", 20: "ligero", 21: "xc_encode", 22: "rs_long", 23: "xc_long", 24: "rs_fold"}
+              17: "grid_extend", 18: "merkle", 19: "rs_encode", 20: "ligero", 21: "xc_encode", 22: "rs_long", 23: "xc_long", 24: "rs_fold", 25: "rs_fold_many"}
 # SC_KIND_LIGERO records: kf -> the kernel that ran
 LIGERO_KERNELS = {0: "column_leaf_kernel", 1: "row_combine_kernel", 2: "column_open_kernel"}
 # SC_KIND_MERKLE records: kf -> the kernel that ran
@@ -156,7 +156,9 @@ SIGNATURES = {
     "sc_xc_encode_rows_long": (ctypes.c_int, [voidp, voidp, size_t, ctypes.POINTER(voidp)]),
     "sc_ligero_commit_code_long": (ctypes.c_int, [voidp, voidp, size_t, size_t, ctypes.c_int, ctypes.POINTER(voidp)]),
     "sc_rs_fold": (ctypes.c_int, [voidp, voidp, u64, ctypes.POINTER(voidp)]),
+    "sc_rs_fold_many": (ctypes.c_int, [voidp, voidp, u64p, size_t, ctypes.POINTER(voidp)]),
     "sc_ligero_fold_begin": (ctypes.c_int, [voidp, voidp, u64p, u64p, u64p, ctypes.POINTER(voidp)]),
+    "sc_ligero_fold_begin_staged": (ctypes.c_int, [voidp, voidp, u64p, u64p, ctypes.POINTER(ctypes.c_int32), size_t, u64p, ctypes.POINTER(voidp)]),
     "sc_ligero_fold_prove": (ctypes.c_int, [voidp, voidp, u64, DRAW_FOLD_FN, voidp, u64p, ctypes.POINTER(ctypes.c_uint8), u64p, u64p]),
     "sc_ligero_fold_query": (ctypes.c_int, [voidp, voidp, u64p, size_t, u64p, ctypes.POINTER(ctypes.c_uint8)]),
     "sc_ligero_fold_destroy": (ctypes.c_int, [voidp, voidp]),

@@ -39,7 +39,13 @@ open_folded prove the combined row m = u_z + beta u_gamma instead of sending u_g
 sumcheck over (m, eq(z[:c])) interleaved with log_cols folds of Enc(m) (sc_ligero_fold_*, one rs_fold_kernel launch per round),
 the folded layers committed with the same leaf and tree.  The opening no longer grows with 2^log_cols and the verifier does
 2 * 2^log_rows + log_cols products per query: fold_opening_bytes and fold_log_cols give its size and the shape that makes it
-smallest.  Reed-Solomon commitments with log_cols >= 1 only; the plain opening stays the default.  No security level is claimed."""
+smallest.  Reed-Solomon commitments with log_cols >= 1 only; the plain opening stays the default.  No security level is claimed.
+
+Staged folded openings: a schedule `arities` = (a_0, .., a_(S-1)), 1 <= a_s <= 3, sum = log_cols,
+folds a_s variables between two committed layers - a layer's leaf then holds 2^a_s words and there are S - 1 trees instead of
+log_cols - 1 (sc_ligero_fold_begin_staged, one rs_fold_many_kernel launch per stage).  Prover.fold_begin, FoldVerifier and
+fold_opening_bytes take `arities`; fold_shape gives the (log_cols, schedule) of the smallest opening; rs_fold_many is the fold
+alone.  arities=None is the binary opening above, unchanged.  The number of queries an arity needs is not analysed."""
 import ctypes
 import hashlib
 
@@ -113,20 +119,64 @@ def long_log_cols(num_vars, log_blowup, queries, max_log_len=LONG_MAX_LOG_LEN):
     return min(range(min(num_vars, max_log_len - log_blowup) + 1), key=lambda c: (opening_bytes(num_vars, c, log_blowup, queries), c))
 
 
-def fold_opening_bytes(num_vars, log_cols, log_blowup, queries):
-    """bytes of a folded opening: per query two columns of 2^(n - c) words with their paths of c + log_blowup digests and, for
-    every layer i = 1 .. c - 1, a pair of words with a path of c + log_blowup - i - 1 digests; once, the c - 1 layer roots, the c
-    round polynomials of three words, and v, v_gamma and the final value"""
+def _schedule(log_cols, arities):
+    """the schedule as a tuple of ints (None: log_cols ones), checked"""
+    if arities is None:
+        return (1,) * log_cols
+    arities = tuple(int(a) for a in arities)
+    if not arities or any(not 1 <= a <= 3 for a in arities) or sum(arities) != log_cols:
+        raise ValueError("a schedule is a non-empty list of arities in 1..3 that sum to log_cols = %d, not %r" % (log_cols, arities))
+    return arities
+
+
+def _stage_starts(arities):
+    """i_s = a_0 + .. + a_(s-1) for every stage s"""
+    starts, i = [], 0
+    for a in arities:
+        starts.append(i)
+        i += a
+    return starts
+
+
+def fold_opening_bytes(num_vars, log_cols, log_blowup, queries, arities=None):
+    """bytes of a folded opening: per query 2^a_0 columns of 2^(n - c) words with their paths of c + log_blowup digests and, for
+    every stage s >= 1, a leaf of 2^a_s words with a path of c + log_blowup - i_s - a_s digests; once, the S - 1 stage roots, the c
+    round polynomials of three words, and v, v_gamma and the final value.  arities=None: every a_s = 1, a pair per layer"""
     if log_cols < 1:
         raise ValueError("a folded opening needs log_cols >= 1")
+    arities = _schedule(log_cols, arities)
     l0 = log_cols + log_blowup
-    per_query = 2 * (8 * (1 << (num_vars - log_cols)) + 32 * l0) + sum(16 + 32 * (l0 - i - 1) for i in range(1, log_cols))
-    return queries * per_query + 32 * (log_cols - 1) + 24 * log_cols + 24
+    per_query = (1 << arities[0]) * (8 * (1 << (num_vars - log_cols)) + 32 * l0)
+    per_query += sum(8 * (1 << a) + 32 * (l0 - i - a) for i, a in list(zip(_stage_starts(arities), arities))[1:])
+    return queries * per_query + 32 * (len(arities) - 1) + 24 * log_cols + 24
 
 
 def fold_log_cols(num_vars, log_blowup, queries, max_log_len=LONG_MAX_LOG_LEN):
     """the log_cols in 1 .. min(num_vars, max_log_len - log_blowup) with the smallest folded opening (ties: the smaller)"""
     return min(range(1, min(num_vars, max_log_len - log_blowup) + 1), key=lambda c: (fold_opening_bytes(num_vars, c, log_blowup, queries), c))
+
+
+def fold_shape(num_vars, log_blowup, queries, max_arity=3, max_log_len=LONG_MAX_LOG_LEN):
+    """(log_cols, arities) of the smallest staged folded opening with arities up to max_arity: the fewest bytes, then the smaller
+    log_cols, then the lexicographically smallest schedule.  A dynamic programme over the round index, from the last round back"""
+    if not 1 <= max_arity <= 3:
+        raise ValueError("max_arity must be 1, 2 or 3")
+    best = None
+    for c in range(1, min(num_vars, max_log_len - log_blowup) + 1):
+        l0 = c + log_blowup
+        tail = [0] * (c + 1)                    # tail[i]: the fewest bytes of the stages >= 1 that start at round i or later
+        for i in range(c - 1, 0, -1):
+            tail[i] = min(queries * (8 * (1 << a) + 32 * (l0 - i - a)) + 32 + tail[i + a] for a in range(1, min(max_arity, c - i) + 1))
+        column = 8 * (1 << (num_vars - c)) + 32 * l0
+        total, a0 = min((queries * (1 << a) * column + tail[a] + 24 * c + 24, a) for a in range(1, min(max_arity, c) + 1))
+        if best is None or total < best[0]:
+            arities, i = [a0], a0
+            while i < c:                         # the smallest arity that still reaches tail[i], stage by stage
+                a = next(a for a in range(1, min(max_arity, c - i) + 1) if queries * (8 * (1 << a) + 32 * (l0 - i - a)) + 32 + tail[i + a] == tail[i])
+                arities.append(a)
+                i += a
+            best = (total, c, tuple(arities))
+    return best[1], best[2]
 
 
 # ---- hashing (host) --------------------------------------------------------------------------------------------------
@@ -252,8 +302,9 @@ class Prover:
             out.append((int(idx[q]), [int(v) for v in values[q * R:(q + 1) * R]], ColumnPath(int(idx[q]), sib, self.field)))
         return out
 
-    def fold_begin(self, point, gamma):
-        """sc_ligero_fold_begin: a folded opening at `point` under the verifier's gamma; its .claims are (v, v_gamma)"""
+    def fold_begin(self, point, gamma, arities=None):
+        """sc_ligero_fold_begin: a folded opening at `point` under the verifier's gamma; its .claims are (v, v_gamma).  With a
+        schedule `arities` (sc_ligero_fold_begin_staged) the opening folds a_s variables per committed layer"""
         if len(point) != self.num_vars:
             raise ValueError("the point has %d coordinates, the polynomial %d variables" % (len(point), self.num_vars))
         if len(gamma) != 1 << self.log_rows:
@@ -261,8 +312,14 @@ class Prover:
         z, g = _words(point), _words(gamma)
         claims = np.zeros(2, dtype=np.uint64)
         h = voidp()
-        self.ctx.check(self.ctx.lib.sc_ligero_fold_begin(self.ctx.h, self.h, _u64p(z), _u64p(g), _u64p(claims), ctypes.byref(h)))
-        return FoldOpening(self, h, (int(claims[0]), int(claims[1])))
+        if arities is None:
+            self.ctx.check(self.ctx.lib.sc_ligero_fold_begin(self.ctx.h, self.h, _u64p(z), _u64p(g), _u64p(claims), ctypes.byref(h)))
+        else:
+            ar = np.ascontiguousarray(np.array([int(a) for a in arities], dtype=np.int32))
+            self.ctx.check(self.ctx.lib.sc_ligero_fold_begin_staged(self.ctx.h, self.h, _u64p(z), _u64p(g),
+                                                                    ar.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if ar.size else None, ar.size,
+                                                                    _u64p(claims), ctypes.byref(h)))
+        return FoldOpening(self, h, (int(claims[0]), int(claims[1])), None if arities is None else tuple(int(a) for a in arities))
 
     def close(self):
         if self.h and self.ctx.h:
@@ -283,17 +340,29 @@ def rs_fold(ctx, table, alpha):
     return DenseMultilinearExtension(ctx, h)
 
 
-class FoldOpening:
-    """sc_ligero_fold_*: the prover's side of one folded opening (Prover.fold_begin): .claims, then prove, then query"""
+def rs_fold_many(ctx, table, alphas):
+    """sc_rs_fold_many: len(alphas) = 1 .. 3 successive folds of a codeword of 2^l words (len(alphas) + 1 <= l <= 24) in one launch,
+    a device table of 2^(l - len(alphas)) words"""
+    a = _words(alphas)
+    h = voidp()
+    ctx.check(ctx.lib.sc_rs_fold_many(ctx.h, table.h, _u64p(a) if a.size else None, a.size, ctypes.byref(h)))
+    return DenseMultilinearExtension(ctx, h)
 
-    def __init__(self, prover, handle, claims):
-        self.prover, self.ctx, self.h, self.claims = prover, prover.ctx, handle, claims
+
+class FoldOpening:
+    """sc_ligero_fold_*: the prover's side of one folded opening (Prover.fold_begin): .claims, then prove, then query.
+    .arities is the schedule the opening was begun with, None for the binary opening"""
+
+    def __init__(self, prover, handle, claims, arities=None):
+        self.prover, self.ctx, self.h, self.claims, self.arities = prover, prover.ctx, handle, claims, arities
         self.log_cols, self.log_len = prover.log_cols, prover.log_cols + prover.log_blowup
+        self.schedule = _schedule(self.log_cols, arities)
 
     def prove(self, beta, draw):
-        """the log_cols rounds: draw(round, [H(0), H(1), H(2)], root_i or None) returns alpha_i.  Returns (rounds, roots,
-        challenges, final value): rounds[i] the three sums, roots[i - 1] = root_i for i = 1 .. log_cols - 1"""
-        c = self.log_cols
+        """the log_cols rounds: draw(round, [H(0), H(1), H(2)], root or None) returns alpha_i; the root is that of stage s >= 1 at
+        its first round i_s (the binary opening: root_i at every round i >= 1).  Returns (rounds, roots, challenges, final value):
+        rounds[i] the three sums, roots[s - 1] the root of stage s = 1 .. S - 1"""
+        c, S = self.log_cols, len(self.schedule)
         failure = []
 
         def cb(_user, i, e, root):
@@ -303,7 +372,7 @@ class FoldOpening:
                 failure.append(exc)
                 return self.ctx.field.p
         evals, challenges = np.zeros(3 * c, dtype=np.uint64), np.zeros(c, dtype=np.uint64)
-        roots = (ctypes.c_uint8 * max(1, 32 * (c - 1)))()
+        roots = (ctypes.c_uint8 * max(1, 32 * (S - 1)))()
         final = u64()
         rc = self.ctx.lib.sc_ligero_fold_prove(self.ctx.h, self.h, int(beta), DRAW_FOLD_FN(cb), None, _u64p(evals), roots, _u64p(challenges),
                                                ctypes.byref(final))
@@ -311,30 +380,36 @@ class FoldOpening:
             raise failure[0]
         self.ctx.check(rc)
         raw = bytes(roots)
-        return ([[int(x) for x in evals[3 * i:3 * i + 3]] for i in range(c)], [raw[32 * i:32 * i + 32] for i in range(c - 1)],
+        return ([[int(x) for x in evals[3 * i:3 * i + 3]] for i in range(c)], [raw[32 * i:32 * i + 32] for i in range(S - 1)],
                 [int(x) for x in challenges], int(final.value))
 
     def query(self, indices):
-        """[(q, column q, column q + L / 2, layers)] for every index q < L / 2: the columns as Prover.open_columns gives them,
-        layers[i - 1] = ((U_i[j_i], U_i[j_i + M_i / 2]), siblings) for i = 1 .. log_cols - 1"""
+        """the binary opening: [(q, column q, column q + L / 2, layers)] for every index q < L / 2: the columns as
+        Prover.open_columns gives them, layers[i - 1] = ((U_i[j_i], U_i[j_i + M_i / 2]), siblings) for i = 1 .. log_cols - 1.
+        With a schedule: [(q, [the 2^a_0 columns q + t L / 2^a_0], stages)] for every q < L / 2^a_0, stages[s - 1] = (the 2^a_s words
+        of leaf j_s, siblings) for s = 1 .. S - 1"""
         idx = _words(indices)
-        count, c, l0 = idx.size, self.log_cols, self.log_len
-        depths = [l0 - i - 1 for i in range(1, c)]
-        P = sum(depths)
-        pairs = np.zeros(max(1, count * (c - 1) * 2), dtype=np.uint64)
+        count, l0, ar = idx.size, self.log_len, self.schedule
+        depths = [l0 - i - a for i, a in list(zip(_stage_starts(ar), ar))[1:]]
+        P, W = sum(depths), sum(1 << a for a in ar[1:])
+        pairs = np.zeros(max(1, count * W), dtype=np.uint64)
         paths = (ctypes.c_uint8 * max(1, count * P * 32))()
         self.ctx.check(self.ctx.lib.sc_ligero_fold_query(self.ctx.h, self.h, _u64p(idx) if count else None, count, _u64p(pairs), paths))
-        half = 1 << (l0 - 1)
-        cols = self.prover.open_columns([int(q) for q in idx] + [int(q) + half for q in idx])
+        stride, parts = 1 << (l0 - ar[0]), 1 << ar[0]
+        cols = self.prover.open_columns([int(q) + t * stride for t in range(parts) for q in idx])
         raw = bytes(paths)
         out = []
         for k in range(count):
-            layers, at = [], k * P
-            for i, depth in enumerate(depths):
-                pair = (int(pairs[(k * (c - 1) + i) * 2]), int(pairs[(k * (c - 1) + i) * 2 + 1]))
-                layers.append((pair, [raw[(at + l) * 32:(at + l + 1) * 32] for l in range(depth)]))
+            stages, at, word = [], k * P, k * W
+            for a, depth in zip(ar[1:], depths):
+                words = tuple(int(x) for x in pairs[word:word + (1 << a)])
+                stages.append((words, [raw[(at + l) * 32:(at + l + 1) * 32] for l in range(depth)]))
                 at += depth
-            out.append((int(idx[k]), cols[k], cols[count + k], layers))
+                word += 1 << a
+            if self.arities is None:
+                out.append((int(idx[k]), cols[k], cols[count + k], stages))
+            else:
+                out.append((int(idx[k]), [cols[t * count + k] for t in range(parts)], stages))
         return out
 
     def close(self):
@@ -464,9 +539,12 @@ class FoldVerifier:
     """The verifier of one folded opening.  Pure host code: draw_gamma, receive_claims, draw_beta, round (once per round, in
     order), receive_final, draw_queries, verify - in that order."""
 
-    def __init__(self, field, num_vars, log_cols, log_blowup, root, queries):
+    def __init__(self, field, num_vars, log_cols, log_blowup, root, queries, arities=None):
         if not 1 <= log_cols <= num_vars or log_blowup not in (1, 2):
             raise ValueError("log_cols must be in 1..num_vars (log_cols = 0: the plain opening) and log_blowup 1 or 2")
+        self.arities = None if arities is None else _schedule(log_cols, arities)      # None: the binary opening and its tuple shapes
+        self.schedule = _schedule(log_cols, arities)
+        self.starts = _stage_starts(self.schedule)
         self.field, self.num_vars, self.log_cols, self.log_blowup = field, num_vars, log_cols, log_blowup
         self.log_rows = num_vars - log_cols
         self.log_len = log_cols + log_blowup
@@ -505,12 +583,14 @@ class FoldVerifier:
         return F.add(F.add(F.mul(e0, l0), F.mul(e1, l1)), F.mul(e2, l2))
 
     def round(self, i, evals, root, rng):
-        """round i's message: the three sums and, for i >= 1, root_i.  Returns alpha_i"""
+        """round i's message: the three sums and, where i starts a stage s >= 1 (the binary opening: every i >= 1), the stage's
+        root.  Returns alpha_i"""
         F = self.field
         if self.beta is None or i != len(self.rounds) or i >= self.log_cols:
             raise Error("round %d out of order" % i)
-        if (root is None) != (i == 0):
-            raise Error("round 0 carries no root, every later round one")
+        if (root is None) != (i == 0 or i not in self.starts):
+            raise Error("round 0 carries no root, every later round one" if self.arities is None else
+                        "round %d: a root comes with the first round of every stage after the first, and with no other" % i)
         evals = [int(x) for x in evals]
         total = F.add(evals[0], evals[1])
         if total != self.claim:
@@ -518,7 +598,7 @@ class FoldVerifier:
         alpha = _draw(F, rng)
         self.claim = self._at(evals, alpha)
         self.rounds.append(evals)
-        if i:
+        if root is not None:
             self.roots.append(bytes(root))
         self.alphas.append(alpha)
         return alpha
@@ -529,10 +609,10 @@ class FoldVerifier:
         self.final = int(final)
 
     def draw_queries(self, rng):
-        """`queries` indices in [0, L / 2), with replacement; only after the prover is bound to every layer and the final value"""
+        """`queries` indices in [0, L / 2^a_0), with replacement; only after the prover is bound to every layer and the final value"""
         if self.final is None:
             raise Error("draw_queries before receive_final: the indices must be drawn after the prover has sent every root and the final value")
-        half = 1 << (self.log_len - 1)
+        half = 1 << (self.log_len - self.schedule[0])
         self.indices = [rng.randrange(half) if hasattr(rng, "randrange") else self.field.to_int(rng.draw()) % half for _ in range(self.queries)]
         return list(self.indices)
 
@@ -564,13 +644,20 @@ class FoldVerifier:
         if F.mul(self.final, eq) != self.claim:
             raise EvalMismatch(F.mul(self.final, eq), self.claim)
         weights = [F.add(e, F.mul(self.beta, g)) for e, g in zip(eq_weights(F, list(point)[c:]), self.gamma)]
-        half = 1 << (l0 - 1)
+        ar, starts = self.schedule, self.starts
+        S = len(ar)
+        stride0 = 1 << (l0 - ar[0])
         for k, (want, opening) in enumerate(zip(self.indices, openings)):
-            q, col_lo, col_hi, layers = opening
-            if q != want or len(layers) != c - 1:
+            if self.arities is None:
+                q, col_lo, col_hi, stages = opening
+                cols = [col_lo, col_hi]
+            else:
+                q, cols, stages = opening
+            if q != want or len(stages) != S - 1 or len(cols) != 1 << ar[0]:
                 raise MerkleMismatch("the opening is of index %d, the drawn index is %d" % (q, want))
-            pair = []
-            for index, (j, values, path) in ((want, col_lo), (want + half, col_hi)):
+            words = []
+            for t, (j, values, path) in enumerate(cols):
+                index = want + t * stride0
                 if j != index or path.index != index:
                     raise MerkleMismatch("the opening is of column %d, the drawn column is %d" % (j, index))
                 if len(values) != 1 << self.log_rows or len(path.siblings) != l0:
@@ -580,31 +667,39 @@ class FoldVerifier:
                 u = 0
                 for wt, val in zip(weights, values):
                     u = F.add(u, F.mul(wt, int(val)))
-                pair.append(u)                                    # U_0[index]
-            for i in range(c):
-                j = want % (1 << (l0 - i - 1))                    # layer i's pair sits at (j, j + M_i / 2)
-                folded = self._fold(pair, self.alphas[i], i, j)
-                if i == c - 1:
+                words.append(u)                                   # U_0[index]
+            for s in range(S):
+                i, a = starts[s], ar[s]
+                stride = 1 << (l0 - i - a)                        # stage s's words sit at j + t stride, t < 2^a
+                j = want % stride
+                for l in range(a):                                # a successive folds: the words t and t + 2^(a-1-l) at level l
+                    h = 1 << (a - 1 - l)
+                    words = [self._fold((words[t], words[t + h]), self.alphas[i + l], i + l, j + t * stride) for t in range(h)]
+                folded = words[0]
+                if s == S - 1:
                     if folded != self.final:
                         raise FoldMismatch(k, i, folded, self.final)
                     break
-                nxt, siblings = layers[i]
-                nxt = (int(nxt[0]), int(nxt[1]))
-                depth = l0 - i - 2
+                nxt, siblings = stages[s]
+                nxt = [int(x) for x in nxt]
+                an = ar[s + 1]
+                depth = l0 - starts[s + 1] - an
                 jn = want % (1 << depth)
-                if len(siblings) != depth or Path(jn, siblings).root_from_digest(pair_digest(F, nxt)) != self.roots[i]:
-                    raise MerkleMismatch("query %d: the opening of layer %d does not lead to its root" % (k, i + 1))
-                found = nxt[0] if j < (1 << depth) else nxt[1]
+                if len(nxt) != 1 << an or len(siblings) != depth or \
+                        Path(jn, siblings).root_from_digest(column_digest(F, nxt)) != self.roots[s]:
+                    raise MerkleMismatch("query %d: the opening of layer %d does not lead to its root" % (k, starts[s + 1]))
+                found = nxt[j >> depth]
                 if folded != found:
                     raise FoldMismatch(k, i, folded, found)
-                pair = nxt
+                words = nxt
         return self.claims[0]
 
 
 def open_folded(prover, verifier, point, rng):
-    """the whole exchange of a folded opening between a Prover and a FoldVerifier; returns what verify returns"""
+    """the whole exchange of a folded opening between a Prover and a FoldVerifier, under the verifier's schedule if it has one;
+    returns what verify returns"""
     gamma = verifier.draw_gamma(rng)
-    opening = prover.fold_begin(point, gamma)
+    opening = prover.fold_begin(point, gamma, verifier.arities)
     try:
         verifier.receive_claims(*opening.claims)
         beta = verifier.draw_beta(rng)

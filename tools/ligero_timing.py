@@ -41,6 +41,11 @@ integers: Goldilocks products do not fit int64), at (20, 10, 1) only.
         and its rate on the record's bytes against the 6.29 TB/s copy rate, the wall time of begin, prove and query against the
         wall time of the plain opening (sc_ligero_combine_rows + sc_ligero_open_columns) of the same commitment, and the wall
         time of FoldVerifier.verify; writes <out>/ligero_fold_timing.json and <out>/ligero_fold_summary.md.
+  python tools/ligero_timing.py --fold-staged [--reps 5]
+        staged folded openings (sc_ligero_fold_begin_staged) at the shapes of --fold: the (log_cols,
+        schedule) fold_shape picks beside the binary folded opening at fold_log_cols' shape, in ONE child process: every fold
+        launch, the wall time of begin, prove and query, the merkle device time, the wall time of FoldVerifier.verify and the
+        bytes; writes <out>/ligero_fold_staged_timing.json and <out>/ligero_fold_staged_summary.md.
 """
 import argparse
 import glob
@@ -321,6 +326,117 @@ def run_fold(reps):
     return out
 
 
+def run_fold_staged(reps):
+    """--fold-staged: per (n, rho) the staged opening at fold_shape's shape beside the binary folded opening at fold_log_cols' shape"""
+    import random
+    sys.path.insert(0, ROOT)
+    from __graft_entry__ import load_package
+    pkg = load_package()
+    lp = pkg.ligero_pcs
+    ctx = pkg.Context(pkg.Field(pkg.GOLDILOCKS), device=0)
+    F = ctx.field
+    out = {"step": "fold_staged", "queries": FOLD_QUERIES, "shapes": {}}
+    for n, rho in FOLD_SHAPES:
+        t = pkg.DenseMultilinearExtension.generate(ctx, 0x11CE0000 + n, n)
+        c_staged, schedule = lp.fold_shape(n, rho, FOLD_QUERIES)
+        row = {}
+        for name, c, arities in (("binary", lp.fold_log_cols(n, rho, FOLD_QUERIES), None), ("staged", c_staged, schedule)):
+            prover = lp.Prover.commit_long(ctx, t, c, rho)
+            rng = random.Random(n)
+            point = [F.rand(rng) for _ in range(n)]
+            gamma = [F.rand(rng) for _ in range(1 << (n - c))]
+            alphas = [F.rand(rng) for _ in range(c)]
+            beta = F.rand(rng)
+            indices = [rng.randrange(1 << (c + rho - (arities[0] if arities else 1))) for _ in range(FOLD_QUERIES)]
+            walls = {"begin": [], "prove": [], "query": []}
+            log, qlog = [], []
+            for rep in range(reps + 3):             # two warm-up runs, `reps` timed ones, one with the launch log on
+                timed, logged = 2 <= rep < reps + 2, rep == reps + 2
+                t0 = time.perf_counter()
+                opening = prover.fold_begin(point, gamma, arities)
+                t1 = time.perf_counter()
+                if logged:
+                    ctx.set_option("time_kernels", 1)
+                    ctx.launch_log()
+                opening.prove(beta, lambda i, e, root: alphas[i])
+                t2 = time.perf_counter()
+                if logged:
+                    log = ctx.launch_log()
+                opening.query(indices)
+                t3 = time.perf_counter()
+                if logged:
+                    qlog = ctx.launch_log()
+                    ctx.set_option("time_kernels", 0)
+                opening.close()
+                if timed:
+                    for key, a, b in (("begin", t0, t1), ("prove", t1, t2), ("query", t2, t3)):
+                        walls[key].append(b - a)
+            # the verifier, on the device prover's messages
+            v = lp.FoldVerifier(F, n, c, rho, prover.root(), FOLD_QUERIES, arities=arities)
+            opening = prover.fold_begin(point, v.draw_gamma(rng), arities)
+            v.receive_claims(*opening.claims)
+            final = opening.prove(v.draw_beta(rng), lambda i, e, root: v.round(i, e, root, rng))[3]
+            v.receive_final(final)
+            opened = opening.query(v.draw_queries(rng))
+            t0 = time.perf_counter()
+            value = v.verify(point, opened)
+            verify_s = time.perf_counter() - t0
+            opening.close()
+            assert value == t.evaluate(point), "the folded opening was accepted with a wrong value"
+            prover.close()
+            folds = [r for r in log if r["kind"] in ("rs_fold", "rs_fold_many")]
+            row[name] = {
+                "log_cols": c, "arities": list(arities) if arities else [1] * c, "trees": (len(arities) if arities else c) - 1,
+                "opening_bytes": lp.fold_opening_bytes(n, c, rho, FOLD_QUERIES, arities=arities),
+                "launches": [{"kind": r["kind"], "kf": r["kf"], "ks": r["ks"], "ms": r["ms"], "bytes": r["bytes_read"] + r["bytes_written"]} for r in folds],
+                "fold_device_ms": sum(r["ms"] for r in folds), "merkle_device_ms": sum(r["ms"] for r in log if r["kind"] == "merkle"),
+                "query_gather_launches": len([r for r in qlog if r["kind"] == "ligero" and r["kf"] == 2]),
+                "prove_device_ms": {k: sum(r["ms"] for r in log if r["kind"] == k) for k in sorted({r["kind"] for r in log})},
+                "wall_ms": {k: statistics.median(w) * 1e3 for k, w in walls.items()}, "verify_wall_ms": verify_s * 1e3}
+        row["plain_opening_bytes_best_shape"] = lp.opening_bytes(n, lp.long_log_cols(n, rho, FOLD_QUERIES), rho, FOLD_QUERIES)
+        out["shapes"]["%d,%d" % (n, rho)] = row
+        del t
+    return out
+
+
+def fold_staged_summary(res):
+    step = res["steps"]["fold_staged"]
+    lines = ["# Staged folded Ligero openings on one MI355X: up to three variables per committed layer beside the binary fold", "",
+             "Measured by `python tools/ligero_timing.py --fold-staged --reps %d`: every figure comes from ONE process.  Goldilocks, tables "
+             "from `sc_table_generate`, %d queries; `staged` is the (log_cols, schedule) `fold_shape` picks, `binary` the folded opening of "
+             "DESIGN.md section 9 item 13 at the shape `fold_log_cols` picks - two commitments of the same table.  Device times: HIP "
+             "events of the launch log, option `time_kernels`, one instrumented run; wall times: medians after two warm-up runs, Python "
+             "wrappers included.  There is no threshold on speed here: the deliverable is the smaller opening and the fewer trees." %
+             (res["reps"], step["queries"]), "",
+             "## The opening", "",
+             "| (n, rho) | opening | log_cols | schedule | trees | opening bytes | begin wall ms | prove wall ms | query wall ms | total ms | "
+             "fold launches device ms | merkle device ms | gather launches per query batch | FoldVerifier.verify wall ms |",
+             "|---|---|---|---|---|---|---|---|---|---|---|---|---|---|"]
+    for key, row in step["shapes"].items():
+        for name in ("binary", "staged"):
+            r, w = row[name], row[name]["wall_ms"]
+            sched = "all ones" if name == "binary" else "(%s)" % ", ".join(str(a) for a in r["arities"])
+            lines.append("| (%s) | %s | %d | %s | %d | %d | %.2f | %.2f | %.2f | %.2f | %.3f | %.3f | %d | %.1f |" % (
+                key.replace(",", ", "), name, r["log_cols"], sched, r["trees"], r["opening_bytes"], w["begin"], w["prove"], w["query"],
+                w["begin"] + w["prove"] + w["query"], r["fold_device_ms"], r["merkle_device_ms"], r["query_gather_launches"], r["verify_wall_ms"]))
+    lines += ["", "The plain opening at its best shape, for scale: " +
+              ", ".join("(%s) %d bytes" % (k.replace(",", ", "), row["plain_opening_bytes_best_shape"]) for k, row in step["shapes"].items()) + ".",
+              "", "## Every fold launch of one staged opening", "",
+              "| (n, rho) | log2 M | variables folded | device ms | bytes read + written | TB/s | of the 6.29 TB/s copy rate |", "|---|---|---|---|---|---|---|"]
+    for key, row in step["shapes"].items():
+        for r in row["staged"]["launches"]:
+            bps = r["bytes"] / (r["ms"] * 1e-3) if r["ms"] > 0 else float("nan")
+            lines.append("| (%s) | %d | %d | %.4f | %d | %.3f | %.1f %% |" % (key.replace(",", ", "), r["ks"], r["kf"], r["ms"], r["bytes"], bps / 1e12,
+                                                                       100 * bps / COPY_BPS))
+    lines += ["", "## Device time of one prove call, by launch kind (ms)", ""]
+    for key, row in step["shapes"].items():
+        for name in ("binary", "staged"):
+            lines.append("- (%s) %s: " % (key.replace(",", ", "), name) + ", ".join("%s %.3f" % (k, v) for k, v in row[name]["prove_device_ms"].items()))
+    if res.get("notes"):
+        lines += ["", "## What the figures say", ""] + res["notes"]
+    return "\n".join(lines) + "\n"
+
+
 def fold_summary(res):
     step = res["steps"]["fold"]
     lines = ["# Folded Ligero openings on one MI355X: rs_fold_kernel, the prover's three calls, the host verifier", "",
@@ -502,8 +618,9 @@ def summary(res):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--step", choices=("encode", "commit", "expander", "long", "xc_long", "fold"))
+    ap.add_argument("--step", choices=("encode", "commit", "expander", "long", "xc_long", "fold", "fold_staged"))
     ap.add_argument("--fold", action="store_true", help="folded openings beside the plain opening (ligero_fold_summary.md)")
+    ap.add_argument("--fold-staged", action="store_true", help="staged folded openings beside the binary fold (ligero_fold_staged_summary.md)")
     ap.add_argument("--long", action="store_true", help="rows longer than the LDS beside the in-LDS encoder (ligero_long_summary.md)")
     ap.add_argument("--code", choices=("rs", "expander"), default="rs", help="expander: the expander code beside Reed-Solomon (expander_summary.md)")
     ap.add_argument("--reps", type=int, default=10)
@@ -516,10 +633,12 @@ def main():
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
     path = os.path.join(args.out, "ligero_timing.json")
-    if (args.long or args.fold) and not args.step:
+    if (args.long or args.fold or args.fold_staged) and not args.step:
         step, stem, render = ("xc_long", "expander_long", xc_long_summary) if args.code == "expander" else ("long", "ligero_long", long_summary)
         if args.fold:
             step, stem, render = "fold", "ligero_fold", fold_summary
+        if args.fold_staged:
+            step, stem, render = "fold_staged", "ligero_fold_staged", fold_staged_summary
         long_path = os.path.join(args.out, stem + "_timing.json")
         if args.summary_only:
             with open(long_path) as fh:
@@ -535,6 +654,11 @@ def main():
                 json.dump(res, fh, indent=1)
         with open(os.path.join(args.out, stem + "_summary.md"), "w") as fh:
             fh.write(render(res))
+        if args.fold_staged:
+            print(json.dumps({k: {name: {"bytes": row[name]["opening_bytes"], "fold_device_ms": round(row[name]["fold_device_ms"], 3),
+                                         **{t: round(v, 2) for t, v in row[name]["wall_ms"].items()}} for name in ("binary", "staged")}
+                              for k, row in res["steps"][step]["shapes"].items()}))
+            return
         if args.fold:
             print(json.dumps({k: {"fold_device_ms": round(row["fold_device_ms"], 3), **{t: round(v, 2) for t, v in row["wall_ms"].items()}}
                               for k, row in res["steps"][step]["shapes"].items()}))
@@ -552,7 +676,7 @@ def main():
             fh.write(summary(res))
         return
     if args.step:
-        runs = {"expander": run_expander, "long": run_long, "xc_long": run_xc_long, "fold": run_fold}
+        runs = {"expander": run_expander, "long": run_long, "xc_long": run_xc_long, "fold": run_fold, "fold_staged": run_fold_staged}
         print(json.dumps(runs[args.step](args.reps) if args.step in runs else run_step(args.step, args.reps)))
         return
     if args.code == "expander":
