@@ -50,13 +50,15 @@ def test_a_stage_is_successive_folds_and_needs_its_leaf_alone(p):
         assert V == [ref.mle_eval(m, alphas, p)] * 2
 
 
-def run_staged_protocol(pkg, p, n, c, rho, arities, queries, seed, tamper=None):
-    """the reference prover against the package's FoldVerifier under a schedule; `tamper` names the message to corrupt.  Returns
-    (value, expected, reference prover)"""
+def run_staged_protocol(pkg, p, n, c, rho, arities, queries, seed, tamper=None, table=None, rng=None):
+    """the reference prover against the package's FoldVerifier under a schedule; `tamper` names the message to corrupt.  `table`
+    (canonical values) and `rng` (what draws for the verifier) replace the seeded ones (tests/test_ligero_fold_limits_cpu.py).
+    Returns (value, expected, reference prover)"""
     lp = pkg.ligero_pcs
     F = pkg.Field(p)
-    rng = random.Random(seed)
-    table = [rng.randrange(p) for _ in range(1 << n)]
+    rng = rng or random.Random(seed)
+    if table is None:
+        table = [rng.randrange(p) for _ in range(1 << n)]
     corrupt = None
     if tamper == "layer":
         corrupt = lambda s, U: [(x + k % 2) % p for k, x in enumerate(U)] if s == 1 else U   # noqa: E731 (wrong odd words of stage 1's layer, hashed as they are: the final value does not depend on them)
