@@ -2,7 +2,8 @@
 FoldVerifier (thaler-study_amd/ligero_pcs.py) against the reference prover - honest transcripts are accepted with the right value,
 every tampered message is refused with its own error - the opening-size helpers against the counted bytes of the reference's
 messages, and the per-item code of rs_fold_kernel, compiled for the host (tests/cpp/rs_fold_host_harness.cpp), against the
-reference bit for bit."""
+reference bit for bit - and, on long layer-0 tables with a shift (2^14 .. 2^24 words), that code and rs_fold_many_kernel's against the
+compiled textbook fold of tests/rs_plain.py."""
 import ctypes
 import hashlib
 import os
@@ -14,7 +15,9 @@ import pytest
 
 import ligero_fold_ref as fref
 import ligero_ref as ref
+import rs_plain
 from conftest import ROOT
+from test_ligero_fold_staged_cpu import rfm  # noqa: F401 (the fixture that builds tests/cpp/rs_fold_many_host_harness.cpp)
 
 GOLD = ref.GOLD
 SHAPES = [(3, 3, 1), (5, 1, 1), (6, 3, 1), (7, 2, 2)]   # (n, c, rho): R = 1; no trees; the ordinary case; two blow-up bits
@@ -220,6 +223,58 @@ def test_host_item_serves_every_layer_from_the_layer_0_tables(rf, p):
     # the exponent of 1 / x: L - j 2^shift mod L
     for log_len0, shift, j in ((12, 0, 0), (12, 0, 1), (12, 3, 255), (5, 2, 3), (24, 0, (1 << 23) - 1), (24, 10, 8191)):
         assert rf.rf_exp(log_len0, shift, j) == ((1 << log_len0) - (j << shift)) % (1 << log_len0)
+
+
+# ---- long layer-0 tables: the only place a shift above 0 meets them word for word (sc_rs_fold always folds with shift 0) ----
+
+LONG_LAYERS = [(14, 0), (14, 1), (16, 3), (20, 6), (24, 0), (24, 1), (24, 10), (24, 20)]      # (l0, shift): M = 2^(l0 - shift) words
+LONG_STAGES = [(16, 3), (24, 10), (24, 0)]      # (24, 0) with one alpha and no tree: the one item whose j runs up to 2^23
+
+
+def long_layer(p, log_len0, shift):
+    """(the raw words of a layer of 2^(l0 - shift) words: worst-case words in its first 4096, uniform residues behind them; the
+    canonical w_M = w_l0^(2^shift); a uniform canonical alpha)"""
+    M = 1 << (log_len0 - shift)
+    rng = np.random.default_rng([p % 1000, log_len0, shift])
+    words = rng.integers(0, p, size=M, dtype=np.uint64)
+    head = min(M, 4096)
+    words[:head] = worst_case_words(p, head, random.Random(log_len0 + shift))
+    return words, pow(ref.omega(p, log_len0), 1 << shift, p), int(rng.integers(0, p, dtype=np.uint64))
+
+
+@pytest.mark.parametrize("log_len0,shift", LONG_LAYERS)
+@pytest.mark.parametrize("p", [GOLD, ref.P64S34], ids=["gold", "p64s34"])
+def test_host_item_on_long_tables_equals_the_plain_fold(rf, p, log_len0, shift):
+    words, omega_m, alpha = long_layer(p, log_len0, shift)
+    out = np.zeros(words.size // 2, dtype=np.uint64)
+    u64p = ctypes.POINTER(ctypes.c_uint64)
+    for a in (alpha, p - 1):
+        rf.rf_fold(p, int(p == GOLD), ref.mont(p, [ref.omega(p, log_len0)])[0], log_len0, shift, ref.mont(p, [a])[0],
+                   words.ctypes.data_as(u64p), out.ctypes.data_as(u64p), None)
+        want = rs_plain.fold(p, words, a, omega_m)
+        assert np.array_equal(out, want), (p, log_len0, shift, a, int(np.flatnonzero(out != want)[0]))
+    # the exponent of 1 / x over the whole layer: L - j 2^shift mod L
+    top = words.size // 2
+    for j in (0, 1, top // 2 - 1, top // 2, top // 2 + 1, top - 1):
+        assert rf.rf_exp(log_len0, shift, j) == ((1 << log_len0) - (j << shift)) % (1 << log_len0)
+
+
+@pytest.mark.parametrize("count", [1, 2, 3])
+@pytest.mark.parametrize("log_len0,shift", LONG_STAGES)
+@pytest.mark.parametrize("p", [GOLD, ref.P64S34], ids=["gold", "p64s34"])
+def test_host_stage_on_long_tables_equals_successive_plain_folds(rfm, p, log_len0, shift, count):  # noqa: F811
+    words, omega_m, alpha = long_layer(p, log_len0, shift)
+    alphas = np.array(ref.mont(p, [alpha, p - 1, 1][:count]), dtype=np.uint64)
+    want = words
+    for k, a in enumerate([alpha, p - 1, 1][:count]):
+        want = rs_plain.fold(p, want, a, pow(omega_m, 1 << k, p))
+    u64p = ctypes.POINTER(ctypes.c_uint64)
+    for an in (0, 3):
+        out = np.zeros(words.size >> count, dtype=np.uint64)
+        dig = (ctypes.c_uint8 * (32 * (words.size >> (count + an)) if an else 1))()
+        rfm.rfm_fold(p, int(p == GOLD), ref.mont(p, [ref.omega(p, log_len0)])[0], log_len0, shift, alphas.ctypes.data_as(u64p), count, an,
+                     words.ctypes.data_as(u64p), out.ctypes.data_as(u64p), dig)
+        assert np.array_equal(out, want), (p, log_len0, shift, count, an, int(np.flatnonzero(out != want)[0]))
 
 
 def test_pair_leaf_is_the_column_leaf_of_two_rows():

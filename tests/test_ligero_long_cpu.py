@@ -1,7 +1,8 @@
 """CPU-only: the long-row Reed-Solomon encoder (csrc/kernels/ligero_long.hpp).  The split, the index
 maps and the twist of the two kernels, compiled for the host (tests/cpp/rs_long_host_harness.cpp): the split's bounds, every
 map a bijection on a row, the blocks of the in-place step disjoint, and a replay of both steps - the kernel's own maps and twist
-around a plain radix-2 transform - against tests/ligero_ref.py bit for bit; and the opening-size helpers of ligero_pcs."""
+around a plain radix-2 transform - against tests/ligero_ref.py bit for bit, and from 2^19 words up to the limit 2^24 against the
+compiled textbook encoder of tests/rs_plain.py; and the opening-size helpers of ligero_pcs."""
 import ctypes
 import os
 import random
@@ -11,6 +12,7 @@ import numpy as np
 import pytest
 
 import ligero_ref as ref
+import rs_plain
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = ref.GOLD
@@ -48,52 +50,75 @@ def block_map(rl, which, log_len, rho, blk):
 def test_the_split(rl):
     for log_len in range(15, 25):
         a, b, tile_log = split(rl, log_len)
-        assert a + b == log_len and 2 <= a <= 14 and b <= 14, (log_len, a, b)       # rho <= 2 <= a
+        assert a + b == log_len and a <= 14 and b <= 14, (log_len, a, b)
+        assert all(rho <= a for rho in (1, 2)), (log_len, a)                          # step 0 runs a - rho >= 0 levels of its own
         assert max(a, b) <= tile_log <= 14                                            # a tile holds whole transforms
         assert rl.rl_blocks(log_len, log_len + 3) == 8 << (log_len - tile_log)
 
 
-@pytest.mark.parametrize("log_len", [15, 16, 17])
+def covers(addresses, start, stop):
+    """the addresses are [start, stop), each once: as many as the range has, all inside it, none missing"""
+    if addresses.size != stop - start or int(addresses.min()) < start or int(addresses.max()) >= stop:
+        return False
+    seen = np.zeros(stop - start, dtype=bool)
+    seen[(addresses - np.uint64(start)).astype(np.int64)] = True
+    return bool(seen.all())
+
+
+@pytest.mark.parametrize("log_len", range(15, 25))
 def test_the_maps_cover_a_row_exactly_once(rl, log_len):
-    rho = 1
-    c = log_len - rho
+    """every length the encoder serves - each has its own split (a, b) from (8, 7) to (12, 12) - at rho = 1 and 2.  From 2^21
+    words on only the second matrix row, which still carries the row offset"""
     a, b, tile_log = split(rl, log_len)
     per_row = rl.rl_blocks(log_len, log_len)
-    for row in (0, 1):                                       # the second matrix row: everything moves by one row
-        blocks = range(row * per_row, (row + 1) * per_row)
-        src = np.concatenate([block_map(rl, 0, log_len, rho, blk) for blk in blocks])
-        assert np.array_equal(np.sort(src), np.arange(row << c, (row + 1) << c, dtype=np.uint64))
-        dst = np.concatenate([block_map(rl, 1, log_len, rho, blk) for blk in blocks])
-        assert np.array_equal(np.sort(dst), np.arange(row << log_len, (row + 1) << log_len, dtype=np.uint64))
-        per_block = [block_map(rl, 2, log_len, rho, blk) for blk in blocks]
-        assert np.array_equal(np.sort(np.concatenate(per_block)), np.arange(row << log_len, (row + 1) << log_len, dtype=np.uint64))
-        # (a bijection on the row from blocks of 2^tile_log items each: the sets of distinct blocks are disjoint)
-        assert all(np.unique(m).size == 1 << tile_log for m in per_block)
-    # inside the tile: step 0 fills every 2^rho-th position once, step 1 every position once, in and out
-    pos0 = block_map(rl, 3, log_len, rho, 1)
-    assert np.array_equal(np.sort(pos0), np.arange(0, 1 << tile_log, 1 << rho, dtype=np.uint64))
-    for which in (4, 5):
-        assert np.array_equal(np.sort(block_map(rl, which, log_len, rho, 1)), np.arange(1 << tile_log, dtype=np.uint64))
-    # the twist exponent of T[j1 + L1 k2] is j1 k2
-    for blk in (0, per_row - 1, per_row):
-        addr = block_map(rl, 1, log_len, rho, blk) % np.uint64(1 << log_len)
-        j1, k2 = addr % np.uint64(1 << a), addr >> np.uint64(a)
-        assert np.array_equal(block_map(rl, 6, log_len, rho, blk), j1 * k2)
+    for rho in (1, 2):
+        c = log_len - rho
+        for row in ((0, 1) if log_len < 21 else (1,)):       # the second matrix row: everything moves by one row
+            blocks = range(row * per_row, (row + 1) * per_row)
+            src = np.concatenate([block_map(rl, 0, log_len, rho, blk) for blk in blocks])
+            assert covers(src, row << c, (row + 1) << c)
+            dst = np.concatenate([block_map(rl, 1, log_len, rho, blk) for blk in blocks])
+            assert covers(dst, row << log_len, (row + 1) << log_len)
+            per_block = [block_map(rl, 2, log_len, rho, blk) for blk in blocks]
+            assert covers(np.concatenate(per_block), row << log_len, (row + 1) << log_len)
+            # (a bijection on the row from blocks of 2^tile_log items each: the sets of distinct blocks are disjoint)
+            assert all(np.unique(m).size == 1 << tile_log for m in per_block)
+        # inside the tile: step 0 fills every 2^rho-th position once, step 1 every position once, in and out
+        pos0 = block_map(rl, 3, log_len, rho, 1)
+        assert np.array_equal(np.sort(pos0), np.arange(0, 1 << tile_log, 1 << rho, dtype=np.uint64))
+        for which in (4, 5):
+            assert np.array_equal(np.sort(block_map(rl, which, log_len, rho, 1)), np.arange(1 << tile_log, dtype=np.uint64))
+        # the twist exponent of T[j1 + L1 k2] is j1 k2
+        for blk in (0, per_row - 1, per_row, 2 * per_row - 1):
+            addr = block_map(rl, 1, log_len, rho, blk) % np.uint64(1 << log_len)
+            j1, k2 = addr % np.uint64(1 << a), addr >> np.uint64(a)
+            assert np.array_equal(block_map(rl, 6, log_len, rho, blk), j1 * k2)
+            assert int((j1 * k2).max()) < 1 << log_len                    # inside the two twist tables
 
 
 REPLAY = ([(GOLD, 1, log_len, rho, r) for log_len in (15, 16, 17) for rho in (1, 2) for r in (0, 1)]
           + [(ref.P64S18, 0, 15, 1, 0), (ref.P64S18, 0, 18, 1, 0), (65537, 0, 16, 1, 0)])
+# .. and the lengths only the compiled reference follows: raw uniform words in (both sides are linear in them), one row
+LONG_REPLAY = ([(GOLD, 1, log_len, 1, 0) for log_len in range(19, 25)] + [(GOLD, 1, 21, 2, 0), (GOLD, 1, 23, 2, 0)]
+               + [(ref.P64S34, 0, 21, 1, 0), (ref.P64S34, 0, 24, 1, 0)])
 
 
-@pytest.mark.parametrize("p,gold,log_len,rho,r", REPLAY, ids=lambda v: str(v))
+@pytest.mark.parametrize("p,gold,log_len,rho,r", REPLAY + LONG_REPLAY, ids=lambda v: str(v))
 def test_host_replay_equals_the_reference(rl, p, gold, log_len, rho, r):
     c = log_len - rho
     n = r + c
+    omega = ref.omega(p, log_len) * ref.R64 % p
+    if (p, gold, log_len, rho, r) in LONG_REPLAY:
+        w = np.random.default_rng([p % 1000, log_len, rho]).integers(0, p, size=1 << n, dtype=np.uint64)
+        E = np.zeros(1 << (n + rho), dtype=np.uint64)
+        rl.rl_encode(p, gold, omega, w.ctypes.data_as(u64p), n, c, rho, E.ctypes.data_as(u64p))
+        want = rs_plain.encode(p, w, c, rho)
+        assert np.array_equal(E, want), (p, log_len, rho, r, int(np.flatnonzero(E != want)[0]))
+        return
     rng = random.Random(100 * log_len + 10 * rho + r)
     table = [rng.randrange(p) for _ in range(1 << n)]
     w = np.array(ref.mont(p, table), dtype=np.uint64)
     E = np.zeros(1 << (n + rho), dtype=np.uint64)
-    omega = ref.omega(p, log_len) * ref.R64 % p
     rl.rl_encode(p, gold, omega, w.ctypes.data_as(u64p), n, c, rho, E.ctypes.data_as(u64p))
     want = np.array(ref.mont(p, [x for row in ref.encode(table, c, rho, p) for x in row]), dtype=np.uint64)
     assert np.array_equal(E, want), (p, log_len, rho, r, int(np.flatnonzero(E != want)[0]))
