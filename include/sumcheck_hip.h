@@ -252,6 +252,12 @@ int sc_ctx_kernel_time(sc_ctx* ctx, double out[2], int reset);
 #define SC_KIND_RS_FOLD_MANY 25 /* rs_fold_many_kernel: A = kf successive folds of a Reed-Solomon codeword of M = 2^ks words in one launch (sc_rs_fold_many,
                                 * sc_ligero_fold_prove on an opening begun with a schedule); log_in = n (sc_rs_fold_many: ks); it reads 8 * M bytes and
                                 * writes 8 * M / 2^A, plus 32 bytes per leaf of the next stage's tree when it hashed them */
+#define SC_KIND_SPMV 26        /* a sparse product of sc_r1cs_mul / sc_r1cs_bind_rows over nnz entries in B = ceil(nnz / 2048) blocks: kf = 0 spmv_kernel
+                                * (with the zeroing of its output; reads 24 * nnz bytes - row, col, val and the gathered word - and writes 8 * 2^log_in
+                                * + 24 * B), kf = 1 spmv_carry_kernel (reads 24 * B, writes 8 * min(2 B, 2^log_in)); ks = 1 if transposed (bind_rows);
+                                * log_in = log2 of the output length */
+#define SC_KIND_ZEROCHECK 27   /* zc_pass_kernel: one round of sc_zerocheck_prove; kf = 1 if it folded the previous challenge, ks = 1, log_in = log2 of
+                                * the tables it read: 4 * 8 * 2^log_in bytes read, and 4 * 8 * 2^(log_in - 1) written with kf = 1 */
 typedef struct sc_launch_record {
   int32_t kind;           /* SC_KIND_* */
   int32_t kf, ks;         /* variables folded / rounds served (meaning per kind above) */
@@ -663,6 +669,35 @@ int sc_rs_fold_many(sc_ctx* ctx, const sc_table* u, const uint64_t* alphas, size
 /* sc_ligero_fold_begin with the schedule arities[0 .. stages) stored in the opening */
 int sc_ligero_fold_begin_staged(sc_ctx* ctx, const sc_ligero* lg, const uint64_t* point, const uint64_t* gamma, const int32_t* arities,
                                 size_t stages, uint64_t claims[2], sc_ligero_fold** out);
+
+/* ---- rank-1 constraint systems: the sparse products and the cubic sumcheck behind an argument for (A z) o (B z) = C z with a
+ * committed witness (kernels/r1cs.hpp states the protocol) --------------------------------------
+ * A, B, C are 2^log_rows x 2^log_cols, each a list of nnz[k] triples (row[k][e], col[k][e], val[k][e]); val is a Montgomery word
+ * below p; triples with the same (row, col) add.  Limits: 1 <= log_rows <= 26, 2 <= log_cols <= 26, every nnz[k] < 2^31; one
+ * device and one rank (SC_ERR_UNSUPPORTED on a sharded context or a multi-device handle, before anything else is looked at).
+ * SC_ERR_ARG: a NULL argument, a shape outside the limits, a triple outside the matrix or with val >= p, a table of another
+ * length, a word of tau, rho or rx that is not below p.  No security level and no zero knowledge are claimed. */
+typedef struct sc_r1cs sc_r1cs;
+/* Checks every triple on the host, sorts the row-major images of A, B, C and the one of [A^T | B^T | C^T] there (stable: the
+ * entries of a row keep their order) and copies them into pool blocks; the host arrays may be freed on return. */
+int sc_r1cs_create(sc_ctx* ctx, size_t log_rows, size_t log_cols, const uint32_t* const row[3], const uint32_t* const col[3],
+                   const uint64_t* const val[3], const size_t nnz[3], sc_r1cs** out);
+int sc_r1cs_destroy(sc_ctx* ctx, sc_r1cs* r);
+/* az, bz, cz = A z, B z, C z: new tables of 2^log_rows words; z has 2^log_cols.  Per matrix the output is zeroed and two launches
+ * follow on the stream (SC_KIND_SPMV: the product, kf = 0, then its carries, kf = 1; none for an empty matrix). */
+int sc_r1cs_mul(sc_ctx* ctx, const sc_r1cs* r, const sc_table* z, sc_table** az, sc_table** bz, sc_table** cz);
+/* out[y] = sum_k rho[k] sum_i eq(rx, i) M_k[i][y]: a new table of 2^log_cols words; rx has log_rows words.  One product over the
+ * three transposed images side by side against the vector (rho_A eq, rho_B eq, rho_C eq), and its carries (ks = 1). */
+int sc_r1cs_bind_rows(sc_ctx* ctx, const sc_r1cs* r, const uint64_t* rx, const uint64_t rho[3], sc_table** out);
+/* The cubic sumcheck over sum_x eq(tau, x) (a(x) b(x) - c(x)) for three tables of equal length 2^s >= 2, variable 0 first: one
+ * launch per round (SC_KIND_ZEROCHECK).  *c1 = H_0(0) + H_0(1) - whatever it is: refusing c1 != 0 is the verifier's part.
+ * evals (4 s words, may be NULL): every round's H(0), H(1), H(2), H(3); challenges (s words, may be NULL); finals = the three
+ * tables folded by every challenge.  draw(user, round, evals) returns the round's challenge, a word below p; draw == NULL: the
+ * synthetic challenger of sc_prove over seed_r.  The tables are not modified.  SC_ERR_UNSUPPORTED: p <= 3 (the cubic through
+ * 0, 1, 2, 3 needs 2 and 3 invertible). */
+typedef uint64_t (*sc_draw4_fn)(void* user, size_t round, const uint64_t evals[4]);
+int sc_zerocheck_prove(sc_ctx* ctx, const sc_table* a, const sc_table* b, const sc_table* c, const uint64_t* tau, sc_draw4_fn draw,
+                       void* user, uint64_t seed_r, uint64_t* c1, uint64_t* evals, uint64_t* challenges, uint64_t finals[3]);
 
 /* ---- gkr_protocol::circuit::Circuit on the device, and the whole GKR prover over it ----------------------------------
  * A circuit lives on ONE context of one device and one rank: sharded contexts (world > 1) and multi-device handles get

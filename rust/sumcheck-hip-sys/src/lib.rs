@@ -105,12 +105,20 @@ pub struct sc_ligero_fold {
     _private: [u8; 0],
 }
 
+/// a rank-1 constraint system on the device (`sc_r1cs_create`)
+#[repr(C)]
+pub struct sc_r1cs {
+    _private: [u8; 0],
+}
+
 pub type sc_allreduce_fn = Option<unsafe extern "C" fn(user: *mut c_void, buf: *mut u64, count: usize) -> c_int>;
 pub type sc_allgather_fn =
     Option<unsafe extern "C" fn(user: *mut c_void, send: *const u64, recv: *mut u64, count: usize) -> c_int>;
 pub type sc_draw_fn = Option<unsafe extern "C" fn(user: *mut c_void, round: usize, evals: *const u64) -> u64>;
 /// `sc_ligero_fold_prove`: the verifier's alpha of a round; `root` = the round's layer root (32 bytes), null at round 0.
 pub type sc_draw_fold_fn = Option<unsafe extern "C" fn(user: *mut c_void, round: usize, evals: *const u64, root: *const u8) -> u64>;
+/// `sc_zerocheck_prove`: the verifier's challenge of a round; `evals` = the round's H(0), H(1), H(2), H(3).
+pub type sc_draw4_fn = Option<unsafe extern "C" fn(user: *mut c_void, round: usize, evals: *const u64) -> u64>;
 /// `sc_prove_batch`: called round by round, within a round in instance order.
 pub type sc_draw_batch_fn = Option<unsafe extern "C" fn(user: *mut c_void, instance: usize, round: usize, evals: *const u64) -> u64>;
 
@@ -574,4 +582,42 @@ extern "C" {
         paths: *mut u8,
     ) -> c_int;
     pub fn sc_ligero_fold_destroy(ctx: *mut sc_ctx, fd: *mut sc_ligero_fold) -> c_int;
+    /// A, B, C of 2^log_rows x 2^log_cols as three lists of (row, col, val) triples: checked and sorted on the host, copied to the device
+    pub fn sc_r1cs_create(
+        ctx: *mut sc_ctx,
+        log_rows: usize,
+        log_cols: usize,
+        row: *const *const u32,
+        col: *const *const u32,
+        val: *const *const u64,
+        nnz: *const usize,
+        out: *mut *mut sc_r1cs,
+    ) -> c_int;
+    pub fn sc_r1cs_destroy(ctx: *mut sc_ctx, r: *mut sc_r1cs) -> c_int;
+    /// A z, B z, C z as new tables: per matrix a product and a carry launch, SC_KIND_SPMV (26)
+    pub fn sc_r1cs_mul(
+        ctx: *mut sc_ctx,
+        r: *const sc_r1cs,
+        z: *const sc_table,
+        az: *mut *mut sc_table,
+        bz: *mut *mut sc_table,
+        cz: *mut *mut sc_table,
+    ) -> c_int;
+    /// out[y] = sum_k rho[k] sum_i eq(rx, i) M_k[i][y]: one transposed product over the three matrices
+    pub fn sc_r1cs_bind_rows(ctx: *mut sc_ctx, r: *const sc_r1cs, rx: *const u64, rho: *const u64, out: *mut *mut sc_table) -> c_int;
+    /// the cubic sumcheck over eq(tau, x) (a(x) b(x) - c(x)): one launch per round, SC_KIND_ZEROCHECK (27); evals 4 s words or null
+    pub fn sc_zerocheck_prove(
+        ctx: *mut sc_ctx,
+        a: *const sc_table,
+        b: *const sc_table,
+        c: *const sc_table,
+        tau: *const u64,
+        draw: sc_draw4_fn,
+        user: *mut c_void,
+        seed_r: u64,
+        c1: *mut u64,
+        evals: *mut u64,
+        challenges: *mut u64,
+        finals: *mut u64,
+    ) -> c_int;
 }

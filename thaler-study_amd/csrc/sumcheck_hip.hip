@@ -24,6 +24,7 @@
 #include <condition_variable>
 #include <functional>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <set>
@@ -604,4 +605,5 @@ static int multi_prod2_fold_and_sums(sc_ctx* m, const sc_table* a, const sc_tabl
 #include "engine/abi_expander.inc"   // the expander row code
 #include "engine/abi_row_code.inc"   // the table of both, and the entry points that encode and commit through it
 #include "engine/abi_fold.inc"       // folded openings of a Reed-Solomon commitment
+#include "engine/abi_r1cs.inc"       // rank-1 constraint systems: sparse products and the cubic sumcheck
 #include "engine/abi_multi.inc"
