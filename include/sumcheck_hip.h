@@ -246,10 +246,10 @@ int sc_ctx_kernel_time(sc_ctx* ctx, double out[2], int reset);
                                 * message (reads 8 * R * 2^lm, writes 8 * R * 2^(lm-2), R = 2^(n - log_cols) rows); kf = 2 xc_long_inner_kernel, the
                                 * code below them in LDS (ks = lm_i = 12 or 13; reads and writes 8 * R * 2^lm_i); kf = 3 xc_long_up_kernel, one per
                                 * global level (reads and writes 8 * R * 2^(lm-1)); log_in = n */
-#define SC_KIND_RS_FOLD 24     /* rs_fold_kernel: one fold of a Reed-Solomon codeword of M = 2^ks words (sc_rs_fold, sc_ligero_fold_prove), one launch; kf = 1 if
+#define SC_KIND_RS_FOLD 24     /* rs_fold_kernel<F, 1, kf>: one fold of a Reed-Solomon codeword of M = 2^ks words (sc_rs_fold, sc_ligero_fold_prove), one launch; kf = 1 if
                                 * it also hashed the leaves of the folded codeword's tree, else 0; log_in = n (sc_rs_fold: ks); it reads 8 * M bytes
                                 * and writes 4 * M, plus 8 * M of digests with kf = 1.  The tree levels above the leaves are SC_KIND_MERKLE records */
-#define SC_KIND_RS_FOLD_MANY 25 /* rs_fold_many_kernel: A = kf successive folds of a Reed-Solomon codeword of M = 2^ks words in one launch (sc_rs_fold_many,
+#define SC_KIND_RS_FOLD_MANY 25 /* rs_fold_kernel<F, A, AN>: A = kf successive folds of a Reed-Solomon codeword of M = 2^ks words in one launch (sc_rs_fold_many,
                                 * sc_ligero_fold_prove on an opening begun with a schedule); log_in = n (sc_rs_fold_many: ks); it reads 8 * M bytes and
                                 * writes 8 * M / 2^A, plus 32 bytes per leaf of the next stage's tree when it hashed them */
 #define SC_KIND_SPMV 26        /* a sparse product of sc_r1cs_mul / sc_r1cs_bind_rows over nnz entries in B = ceil(nnz / 2048) blocks: kf = 0 spmv_kernel
@@ -629,7 +629,7 @@ int sc_ligero_commit_code_long(sc_ctx* ctx, const sc_table* t, size_t log_cols, 
  * multi-device handle.  SC_ERR_STATE: sc_ligero_fold_prove called twice, sc_ligero_fold_query before it. */
 
 /* one fold alone: u holds M = 2^l words, 2 <= l <= min(24, s), a codeword in the contract's order; *out = its fold with alpha
- * at x = w_l^j, a new table of M / 2 words.  One launch (SC_KIND_RS_FOLD, kf = 0). */
+ * at x = w_l^j, a new table of M / 2 words.  One launch of rs_fold_kernel<F, 1, 0> (SC_KIND_RS_FOLD, kf = 0). */
 int sc_rs_fold(sc_ctx* ctx, const sc_table* u, uint64_t alpha, sc_table** out);
 typedef struct sc_ligero_fold sc_ligero_fold;
 /* the verifier's alpha_i for round i, called with the round's three sums and, for round >= 1, root_i (32 bytes; NULL at round 0) */
@@ -640,7 +640,7 @@ int sc_ligero_fold_begin(sc_ctx* ctx, const sc_ligero* lg, const uint64_t* point
                          sc_ligero_fold** out);
 /* steps 4 - 7, once per opening: evals = 3 c words (every round's H(0), H(1), H(2)), roots = 32 (c - 1) bytes (root_1 ..
  * root_(c-1); may be NULL for c = 1), challenges = c words or NULL, *final_value = the word of U_c; `draw` is required and is
- * called once per round, in order.  One rs_fold_kernel launch per round; U_0 is encoded by the row encoder and not kept. */
+ * called once per round, in order.  One rs_fold_kernel<F, 1, 0 / 1> launch per round (SC_KIND_RS_FOLD); U_0 is encoded by the row encoder and not kept. */
 int sc_ligero_fold_prove(sc_ctx* ctx, sc_ligero_fold* fd, uint64_t beta, sc_draw_fold_fn draw, void* user, uint64_t* evals,
                          uint8_t* roots, uint64_t* challenges, uint64_t* final_value);
 /* step 9's layer openings for `count` indices q < L / 2 (the columns q and q + L / 2 come from sc_ligero_open_columns):

@@ -536,9 +536,9 @@ extern "C" {
         code: c_int,
         out: *mut *mut sc_ligero,
     ) -> c_int;
-    /// one fold of a Reed-Solomon codeword of 2^l words (2 <= l <= 24) with alpha: one launch, SC_KIND_RS_FOLD (24)
+    /// one fold of a Reed-Solomon codeword of 2^l words (2 <= l <= 24) with alpha: one launch of the fold kernel at arity one, recorded as SC_KIND_RS_FOLD (24)
     pub fn sc_rs_fold(ctx: *mut sc_ctx, u: *const sc_table, alpha: u64, out: *mut *mut sc_table) -> c_int;
-    /// `count` = 1 .. 3 successive folds of a codeword of 2^l words (count + 1 <= l <= 24) in one launch, SC_KIND_RS_FOLD_MANY (25)
+    /// `count` = 1 .. 3 successive folds of a codeword of 2^l words (count + 1 <= l <= 24) in one launch of the same kernel, recorded as SC_KIND_RS_FOLD_MANY (25)
     pub fn sc_rs_fold_many(ctx: *mut sc_ctx, u: *const sc_table, alphas: *const u64, count: usize, out: *mut *mut sc_table) -> c_int;
     /// a folded opening of a Reed-Solomon commitment at `point`: claims = (v, v_gamma); the combined rows stay on the device
     pub fn sc_ligero_fold_begin(

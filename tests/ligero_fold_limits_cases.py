@@ -1,5 +1,5 @@
 """What tests/test_gpu_ligero_fold_limits.py and tests/test_ligero_fold_limits_cpu.py share: the fields, the four shapes whose
-schedules launch every rs_fold_many_kernel<F, A, AN>, and the worst-case inputs of a folded opening - all RAW (Montgomery) words,
+schedules launch every rs_fold_kernel<F, A, AN>, and the worst-case inputs of a folded opening - all RAW (Montgomery) words,
 as the device takes them; a reference gets ligero_ref.canon of them.  Nothing here imports the package."""
 import random
 
@@ -15,7 +15,7 @@ IDS = {GOLD: "gold", BABYBEAR: "babybear", ref.P64S18: "p64s18", ref.P64S34: "p6
 # (n, c, rho, schedule): l0 = 8; l0 = 11, the last length on the single table, rho = 2; l0 = 12, the first on the twist tables;
 # l0 = 13, rho = 2.  Every stage after the first folds a layer of 2^(l0 - i_s) words with the tables of length 2^l0 (shift = i_s)
 SHAPES = [(9, 7, 1, (2, 2, 3)), (11, 9, 2, (2, 3, 1, 1, 2)), (12, 11, 1, (3, 3, 2, 2, 1)), (13, 11, 2, (1, 3, 1, 2, 2, 2))]
-BINARY_SHAPES = [SHAPES[0], SHAPES[2]]          # also opened without a schedule: rs_fold_kernel<F, true / false>
+BINARY_SHAPES = [SHAPES[0], SHAPES[2]]          # also opened without a schedule: rs_fold_kernel<F, 1, 1 / 0>, recorded as rs_fold
 VERIFIER_SHAPES = [SHAPES[1], SHAPES[2]]        # l0 = 11 and l0 = 12
 RANDOM_SHAPE = SHAPES[2]
 ALL_PAIRS = {(a, an) for a in (1, 2, 3) for an in (0, 1, 2, 3)}

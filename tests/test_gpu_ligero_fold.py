@@ -331,6 +331,24 @@ def test_launch_log(pkg):
     prover.close()
 
 
+@pytest.mark.parametrize("log_m", [2, 12, 13])
+@pytest.mark.parametrize("p", [GOLD, BABYBEAR], ids=_id)
+def test_rs_fold_is_the_one_challenge_fold_under_its_own_record(pkg, p, log_m):
+    """sc_rs_fold at the smallest codeword and on either side of the twist tables' first length: one launch, recorded as rs_fold
+    with kf = 0, and word for word what sc_rs_fold_many gives with that one challenge"""
+    ctx, F = ctx_of(pkg, p), pkg.Field(p)
+    M = 1 << log_m
+    t = pkg.DenseMultilinearExtension.from_evaluations_vec(ctx, log_m, random_words(p, log_m))
+    alpha = F.rand(random.Random(p + log_m))
+    ctx.set_option("time_kernels", 1)
+    ctx.launch_log()
+    got = pkg.ligero_pcs.rs_fold(ctx, t, alpha)
+    log = ctx.launch_log()
+    ctx.set_option("time_kernels", 0)
+    assert [(x["kind"], x["kf"], x["ks"], x["bytes_read"], x["bytes_written"]) for x in log] == [("rs_fold", 0, log_m, 8 * M, 4 * M)], log
+    assert np.array_equal(got.to_evaluations(), pkg.ligero_pcs.rs_fold_many(ctx, t, [alpha]).to_evaluations())
+
+
 @pytest.mark.parametrize("p", [GOLD, BABYBEAR], ids=_id)
 def test_pool_balance(pkg, p):
     lp = pkg.ligero_pcs

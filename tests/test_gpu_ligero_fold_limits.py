@@ -3,7 +3,7 @@
 
   a. whole transcripts over seven fields - Goldilocks, BabyBear and the five full-width generic primes - on tables that put
      every add / sub corner class on the pairs (U[j], U[j + M/2]), with edge-word points and gammas, beta = p - 1 and 0 and
-     degenerate challenges, under four schedules that between them launch all twelve rs_fold_many_kernel<F, A, AN>, at layer-0
+     degenerate challenges, under four schedules that between them launch all twelve rs_fold_kernel<F, A, AN>, at layer-0
      lengths on both sides of the fold's table switch with a shift, and the binary opening on two of the shapes;
   b. which instantiations ran, read from the launch log;
   c. the whole protocol with the host FoldVerifier on those tables;

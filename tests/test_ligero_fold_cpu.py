@@ -1,9 +1,9 @@
 """CPU-only: the folded opening's reference (tests/ligero_fold_ref.py) against the identity it rests on, the package's host
 FoldVerifier (thaler-study_amd/ligero_pcs.py) against the reference prover - honest transcripts are accepted with the right value,
 every tampered message is refused with its own error - the opening-size helpers against the counted bytes of the reference's
-messages, and the per-item code of rs_fold_kernel, compiled for the host (tests/cpp/rs_fold_host_harness.cpp), against the
-reference bit for bit - and, on long layer-0 tables with a shift (2^14 .. 2^24 words), that code and rs_fold_many_kernel's against the
-compiled textbook fold of tests/rs_plain.py."""
+messages, and the per-item code of rs_fold_kernel<F, 1, 0 / 1>, compiled for the host (tests/cpp/rs_fold_host_harness.cpp),
+against the reference bit for bit - and, on long layer-0 tables with a shift (2^14 .. 2^24 words), that code at every arity
+against the compiled textbook fold of tests/rs_plain.py."""
 import ctypes
 import hashlib
 import os
@@ -17,7 +17,7 @@ import ligero_fold_ref as fref
 import ligero_ref as ref
 import rs_plain
 from conftest import ROOT
-from test_ligero_fold_staged_cpu import rfm  # noqa: F401 (the fixture that builds tests/cpp/rs_fold_many_host_harness.cpp)
+from test_ligero_fold_staged_cpu import rfm  # noqa: F401 (the same harness's rfm_fold)
 
 GOLD = ref.GOLD
 SHAPES = [(3, 3, 1), (5, 1, 1), (6, 3, 1), (7, 2, 2)]   # (n, c, rho): R = 1; no trees; the ordinary case; two blow-up bits
@@ -181,7 +181,7 @@ def rf(tmp_path_factory):
 
 
 def host_fold(rf, p, log_len0, shift, alpha, U, leaves=True):
-    """rs_fold_kernel's items over the canonical codeword U of 2^(log_len0 - shift) words: (folded canonical words, leaf digests)"""
+    """rs_fold_kernel<F, 1, 0 / 1>'s items over the canonical codeword U of 2^(log_len0 - shift) words: (folded canonical words, leaf digests)"""
     M = len(U)
     u = np.array(ref.mont(p, U), dtype=np.uint64)
     out = np.zeros(M // 2, dtype=np.uint64)

@@ -1,8 +1,8 @@
 """CPU-only, with tests/test_gpu_ligero_fold_limits.py: that the inputs of that file cover what it says they cover - its four
-shapes launch all twelve rs_fold_many_kernel<F, A, AN>, its fold tables carry every add / sub corner class that exists for the
+shapes launch all twelve rs_fold_kernel<F, A, AN>, its fold tables carry every add / sub corner class that exists for the
 field, its challenges contain 0, the field's one and p - 1 - and, on those same inputs, the two host-side pieces the GPU file
 leans on: the package's FoldVerifier over full-width fields (accepted with the value, tampering refused) and the per-item code of
-rs_fold_many_kernel compiled for the host, for every (A, AN), against tests/ligero_fold_staged_ref.py."""
+rs_fold_kernel compiled for the host, for every (A, AN), against tests/ligero_fold_staged_ref.py."""
 import pytest
 
 import ligero_fold_staged_ref as sref

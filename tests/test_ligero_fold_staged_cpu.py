@@ -2,8 +2,8 @@
 fold is successive single folds, and word j of it needs the 2^a words of leaf j alone), the package's host FoldVerifier with a
 schedule (thaler-study_amd/ligero_pcs.py) against the reference prover - honest transcripts are accepted with the right value,
 every tampered message is refused with its own error, an all-ones schedule gives the binary opening's messages - the size
-helpers and fold_shape against counted bytes and brute force, and the per-item code of rs_fold_many_kernel, compiled for the
-host (tests/cpp/rs_fold_many_host_harness.cpp), against the reference bit for bit."""
+helpers and fold_shape against counted bytes and brute force, and the per-item code of rs_fold_kernel, compiled for the
+host (tests/cpp/rs_fold_host_harness.cpp), against the reference bit for bit."""
 import ctypes
 import os
 import random
@@ -230,7 +230,7 @@ def test_fold_shape_equals_brute_force(pkg, rho):
 @pytest.fixture(scope="module")
 def rfm(tmp_path_factory):
     out = tmp_path_factory.mktemp("rfm") / "librs_fold_many_host.so"
-    src = os.path.join(ROOT, "tests", "cpp", "rs_fold_many_host_harness.cpp")
+    src = os.path.join(ROOT, "tests", "cpp", "rs_fold_host_harness.cpp")
     subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", str(out), src])
     lib = ctypes.CDLL(str(out))
     u64p = ctypes.POINTER(ctypes.c_uint64)
@@ -241,7 +241,7 @@ def rfm(tmp_path_factory):
 
 
 def host_stage(rfm, p, log_len0, shift, alphas, an, words):
-    """rs_fold_many_kernel<F, len(alphas), an>'s items over the RAW words of a layer of 2^(log_len0 - shift) words: (folded
+    """rs_fold_kernel<F, len(alphas), an>'s items over the RAW words of a layer of 2^(log_len0 - shift) words: (folded
     canonical words, leaf digests)"""
     a, M = len(alphas), len(words)
     u = np.ascontiguousarray(words, dtype=np.uint64)

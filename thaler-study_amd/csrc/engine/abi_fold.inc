@@ -1,16 +1,15 @@
 // Part of sumcheck_hip.hip (included there, in order, after abi_row_code.inc): C ABI: the folded opening of a Reed-Solomon
-// sc_ligero (kernels/rs_fold.hpp states the contract) - one fold of a codeword (sc_rs_fold), and the prover of an opening: the
-// two claims (begin), the sumcheck rounds with the folds and the layer trees between them (prove), and the opened layer pairs
-// (query).  The rows are combined by engine/abi_ligero.inc, encoded by the row code's encoder, the rounds are sc_prover_round's
-// and the trees engine/merkle.inc's; what is new is rs_fold_kernel and, for an opening with a schedule
-// (sc_ligero_fold_begin_staged: up to three variables folded per committed layer), rs_fold_many_kernel.
+// sc_ligero (kernels/rs_fold.hpp states the contract) - one launch of folds of a codeword (sc_rs_fold, sc_rs_fold_many), and
+// the prover of an opening: the two claims (begin), the sumcheck rounds with the folds and the layer trees between them
+// (prove), and the opened layer leaves (query).  The rows are combined by engine/abi_ligero.inc, encoded by the row code's
+// encoder, the rounds are sc_prover_round's and the trees engine/merkle.inc's; what is new is rs_fold_kernel.
 
 // An opening in progress: the two combined rows until prove has run, then the layers of the stages 1 .. S-1 and their trees.
 struct sc_ligero_fold {
   const sc_ctx* ctx = nullptr;
   const sc_ligero* lg = nullptr;   // borrowed: must outlive the opening
   bool proved = false;
-  bool staged = false;             // begun with a schedule: rs_fold_many_kernel and SC_KIND_RS_FOLD_MANY records
+  int kind = SC_KIND_RS_FOLD;      // of its fold records; begun with a schedule: SC_KIND_RS_FOLD_MANY
   std::vector<int> arities;        // a_0 .. a_(S-1); sc_ligero_fold_begin: c ones
   std::vector<u64> z_lo;
   PoolBuf rows;                    // u_z, then u_gamma: C words each
@@ -20,55 +19,20 @@ struct sc_ligero_fold {
 
 namespace {
 
-// out = the fold of the 2^log_m words of U with alpha, as layer l0 - log_m of an opening whose layer 0 has 2^log_len0 words;
-// leaves != null: the digests of out's leaves go there too.  One launch
-int rs_fold_launch(sc_ctx* ctx, const u64* U, int log_m, int log_len0, u64 alpha, int log_in, u64* out, u32* leaves) {
+// out = the 2^log_m words of U folded `a` times with alphas[0 .. a), 2^(log_m - a) >= 2 words; an != 0: the digests of out's
+// leaves of 2^an words go to `leaves`.  As layer l0 - log_m of an opening whose layer 0 has 2^log_len0 words.  One launch,
+// recorded as `kind`: SC_KIND_RS_FOLD (a = 1, an <= 1; kf = 1 if hashed) or SC_KIND_RS_FOLD_MANY (kf = a)
+int rs_fold_launch(sc_ctx* ctx, const u64* U, int log_m, int log_len0, const u64* alphas, int a, int an, int log_in, u64* out, u32* leaves,
+                   int kind) {
   const HostField hf(ctx->fp);
   const TwoAdicRoot root = two_adic_root(ctx);
-  sc::RsFoldArgs a;
-  const u64 half = hf.inv(hf.add(hf.one(), hf.one()));
-  a.c1 = hf.mul(half, alpha);
-  a.c0 = hf.sub(half, a.c1);
-  a.inv_w4 = hf.neg(hf.pow(root.w_max, (u64)1 << (root.s - 2)));   // 1 / i = -i
-  a.log_len0 = log_len0;
-  a.shift = log_len0 - log_m;
-  a.hi = nullptr;
-  if (log_len0 >= sc::kRsFoldTwistMinLog) {
-    SC_TRY(rs_twist_tables(ctx, log_len0, &a.lo, &a.hi));
-  } else {
-    sc::RsRoots unused;
-    SC_TRY(rs_twiddles(ctx, log_len0, &a.lo, &unused));
-  }
-  const u64 M = (u64)1 << log_m;
-  const u32 quarter = (u32)(M / 4);
-  return launch_recorded(ctx, {SC_KIND_RS_FOLD, leaves ? 1 : 0, log_m, log_in, 8 * M, 4 * M + (leaves ? 8 * M : 0)}, "rs_fold_kernel", [&] {
-    SC_DISPATCH_FIELD(ctx, F, f, with_bool(leaves != nullptr, [&](auto H) {
-                        hipLaunchKernelGGL((sc::rs_fold_kernel<F, H>), dim3(strided_grid(ctx, quarter)), dim3(sc::kBlock), 0, ctx->stream, f, U,
-                                           out, a, quarter, leaves);
-                      }));
-  });
-}
-
-// out = the 2^log_m words of U folded `a` times with alphas[0 .. a); an != 0: the digests of out's leaves of 2^an words go to
-// `leaves`.  As layer l0 - log_m of an opening whose layer 0 has 2^log_len0 words.  One launch
-int rs_fold_many_launch(sc_ctx* ctx, const u64* U, int log_m, int log_len0, const u64* alphas, int a, int an, int log_in, u64* out, u32* leaves) {
-  const HostField hf(ctx->fp);
-  const TwoAdicRoot root = two_adic_root(ctx);
-  sc::RsFoldManyArgs k = {};
-  const u64 half = hf.inv(hf.add(hf.one(), hf.one()));
-  // zeta = w_M^(-M/2^a) and eta = w_M^(-M/2^(a+an)): the inverses of the contract's roots of those orders
-  const u64 zeta = hf.inv(hf.pow(root.w_max, (u64)1 << (root.s - a))), eta = hf.inv(hf.pow(root.w_max, (u64)1 << (root.s - a - an)));
-  for (int l = 0; l < a; ++l) {
-    const u64 c1 = hf.mul(half, alphas[l]), step = hf.pow(zeta, (u64)1 << l);
-    k.c0[l] = hf.sub(half, c1);
-    u64 z = hf.one();
-    for (int t = 0; t < 1 << (a - 1 - l); ++t, z = hf.mul(z, step)) k.c1z[(1 << a) - (1 << (a - l)) + t] = hf.mul(c1, z);
-  }
-  k.eta[0] = hf.one();
-  for (int t = 1; t < 1 << an; ++t) k.eta[t] = hf.mul(k.eta[t - 1], eta);
+  sc::RsFoldArgs k = {};
+  // zeta = w_M^(-M/2^a) and eta = w_M^(-M/2^(a+w)): the inverses of the contract's roots of those orders
+  const int w = sc::rs_fold_item_log(an);
+  sc::rs_fold_constants(hf, hf.inv(hf.add(hf.one(), hf.one())), hf.inv(hf.pow(root.w_max, (u64)1 << (root.s - a))),
+                        hf.inv(hf.pow(root.w_max, (u64)1 << (root.s - a - w))), alphas, a, w, &k);
   k.log_len0 = log_len0;
   k.shift = log_len0 - log_m;
-  k.hi = nullptr;
   if (log_len0 >= sc::kRsFoldTwistMinLog) {
     SC_TRY(rs_twist_tables(ctx, log_len0, &k.lo, &k.hi));
   } else {
@@ -76,12 +40,13 @@ int rs_fold_many_launch(sc_ctx* ctx, const u64* U, int log_m, int log_len0, cons
     SC_TRY(rs_twiddles(ctx, log_len0, &k.lo, &unused));
   }
   const u64 M = (u64)1 << log_m;
-  const u32 n_leaves = (u32)(M >> (a + an));
-  return launch_recorded(ctx, {SC_KIND_RS_FOLD_MANY, a, log_m, log_in, 8 * M, (8 * M >> a) + (an ? 32 * (u64)n_leaves : 0)}, "rs_fold_many_kernel", [&] {
+  const u32 items = (u32)(M >> (a + w));
+  const int kf = kind == SC_KIND_RS_FOLD ? (an ? 1 : 0) : a;
+  return launch_recorded(ctx, {kind, kf, log_m, log_in, 8 * M, (8 * M >> a) + (an ? 32 * (u64)items : 0)}, "rs_fold_kernel", [&] {
     SC_DISPATCH_FIELD(ctx, F, f, with_const<1, 2, 3>(a, [&](auto A) {
                         with_const<0, 1, 2, 3>(an, [&](auto AN) {
-                          hipLaunchKernelGGL((sc::rs_fold_many_kernel<F, A, AN>), dim3(strided_grid(ctx, n_leaves)), dim3(sc::kBlock), 0, ctx->stream,
-                                             f, U, out, k, n_leaves, leaves);
+                          hipLaunchKernelGGL((sc::rs_fold_kernel<F, A, AN>), dim3(strided_grid(ctx, items)), dim3(sc::kBlock), 0, ctx->stream, f,
+                                             U, out, k, items, leaves);
                         });
                       }));
   });
@@ -101,50 +66,43 @@ struct FoldGuard {
   ~FoldGuard() { delete p; }
 };
 
-}  // namespace
-
-extern "C" int sc_rs_fold(sc_ctx* ctx, const sc_table* u, uint64_t alpha, sc_table** out) {
+// sc_rs_fold (one == true: a single challenge, and the messages say so) and sc_rs_fold_many
+int rs_fold_table(sc_ctx* ctx, const sc_table* u, const u64* alphas, size_t count, bool one, sc_table** out) {
+  const char* what = one ? "sc_rs_fold" : "sc_rs_fold_many";
   if (!ctx || !out) return SC_ERR_ARG;
   *out = nullptr;
-  SC_TRY(one_device_only(ctx, "sc_rs_fold"));
-  SC_TRY(check_table(ctx, u, "sc_rs_fold"));
-  if (u->len < 4) return fail(ctx, SC_ERR_ARG, "sc_rs_fold: a codeword of %zu words (at least 4)", u->len);
-  const int log_m = log2_of(u->len), s = two_adic_root(ctx).s;
-  if (log_m > sc::kRsLongMaxLog)
-    return fail(ctx, SC_ERR_UNSUPPORTED, "sc_rs_fold: a codeword of 2^%d words is longer than 2^%d", log_m, sc::kRsLongMaxLog);
-  if (log_m > s)
-    return fail(ctx, SC_ERR_UNSUPPORTED, "sc_rs_fold: p = %llu has 2-adicity %d: no root of unity of order 2^%d", (unsigned long long)ctx->fp.p,
-                s, log_m);
-  if (alpha >= ctx->fp.p) return fail(ctx, SC_ERR_ARG, "sc_rs_fold: alpha is not reduced");
-  SC_TRY(set_device(ctx));
-  TableBuf t;
-  SC_TRY(t.alloc(ctx, u->len / 2));
-  SC_TRY(rs_fold_launch(ctx, u->d, log_m, log_m, alpha, log_m, t->d, nullptr));
-  return table_done(ctx, t, hipSuccess, "sc_rs_fold", out);
-}
-
-extern "C" int sc_rs_fold_many(sc_ctx* ctx, const sc_table* u, const uint64_t* alphas, size_t count, sc_table** out) {
-  if (!ctx || !out) return SC_ERR_ARG;
-  *out = nullptr;
-  SC_TRY(one_device_only(ctx, "sc_rs_fold_many"));
-  SC_TRY(check_table(ctx, u, "sc_rs_fold_many"));
-  if (count < 1 || count > 3) return fail(ctx, SC_ERR_ARG, "sc_rs_fold_many: %zu challenges (1 .. 3 fold in one launch)", count);
-  if (!alphas) return fail(ctx, SC_ERR_ARG, "sc_rs_fold_many: null pointer");
-  if (u->len < (size_t)2 << count)
+  SC_TRY(one_device_only(ctx, what));
+  SC_TRY(check_table(ctx, u, what));
+  if (!one) {
+    if (count < 1 || count > 3) return fail(ctx, SC_ERR_ARG, "sc_rs_fold_many: %zu challenges (1 .. 3 fold in one launch)", count);
+    if (!alphas) return fail(ctx, SC_ERR_ARG, "sc_rs_fold_many: null pointer");
+  }
+  if (u->len < (size_t)2 << count) {
+    if (one) return fail(ctx, SC_ERR_ARG, "sc_rs_fold: a codeword of %zu words (at least 4)", u->len);
     return fail(ctx, SC_ERR_ARG, "sc_rs_fold_many: a codeword of %zu words (at least %zu for %zu folds)", u->len, (size_t)2 << count, count);
+  }
   const int log_m = log2_of(u->len), s = two_adic_root(ctx).s;
   if (log_m > sc::kRsLongMaxLog)
-    return fail(ctx, SC_ERR_UNSUPPORTED, "sc_rs_fold_many: a codeword of 2^%d words is longer than 2^%d", log_m, sc::kRsLongMaxLog);
+    return fail(ctx, SC_ERR_UNSUPPORTED, "%s: a codeword of 2^%d words is longer than 2^%d", what, log_m, sc::kRsLongMaxLog);
   if (log_m > s)
-    return fail(ctx, SC_ERR_UNSUPPORTED, "sc_rs_fold_many: p = %llu has 2-adicity %d: no root of unity of order 2^%d",
-                (unsigned long long)ctx->fp.p, s, log_m);
+    return fail(ctx, SC_ERR_UNSUPPORTED, "%s: p = %llu has 2-adicity %d: no root of unity of order 2^%d", what, (unsigned long long)ctx->fp.p, s,
+                log_m);
   for (size_t k = 0; k < count; ++k)
-    if (alphas[k] >= ctx->fp.p) return fail(ctx, SC_ERR_ARG, "sc_rs_fold_many: alpha %zu is not reduced", k);
+    if (alphas[k] >= ctx->fp.p)
+      return one ? fail(ctx, SC_ERR_ARG, "sc_rs_fold: alpha is not reduced") : fail(ctx, SC_ERR_ARG, "sc_rs_fold_many: alpha %zu is not reduced", k);
   SC_TRY(set_device(ctx));
   TableBuf t;
   SC_TRY(t.alloc(ctx, u->len >> count));
-  SC_TRY(rs_fold_many_launch(ctx, u->d, log_m, log_m, alphas, (int)count, 0, log_m, t->d, nullptr));
-  return table_done(ctx, t, hipSuccess, "sc_rs_fold_many", out);
+  SC_TRY(rs_fold_launch(ctx, u->d, log_m, log_m, alphas, (int)count, 0, log_m, t->d, nullptr, one ? SC_KIND_RS_FOLD : SC_KIND_RS_FOLD_MANY));
+  return table_done(ctx, t, hipSuccess, what, out);
+}
+
+}  // namespace
+
+extern "C" int sc_rs_fold(sc_ctx* ctx, const sc_table* u, uint64_t alpha, sc_table** out) { return rs_fold_table(ctx, u, &alpha, 1, true, out); }
+
+extern "C" int sc_rs_fold_many(sc_ctx* ctx, const sc_table* u, const uint64_t* alphas, size_t count, sc_table** out) {
+  return rs_fold_table(ctx, u, alphas, count, false, out);
 }
 
 namespace {
@@ -179,7 +137,7 @@ int fold_begin(sc_ctx* ctx, const sc_ligero* lg, const uint64_t* point, const ui
   fd->ctx = ctx;
   fd->lg = lg;
   fd->z_lo.assign(point, point + lg->c);
-  fd->staged = arities != nullptr;
+  if (arities) fd->kind = SC_KIND_RS_FOLD_MANY;
   if (arities) fd->arities.assign(arities, arities + stages);
   else fd->arities.assign((size_t)lg->c, 1);
   // the weights of u_z - eq(z_hi, i), LE - then gamma
@@ -284,8 +242,7 @@ extern "C" int sc_ligero_fold_prove(sc_ctx* ctx, sc_ligero_fold* fd, uint64_t be
     MerkleLevels t;
     if (an) SC_TRY(t.alloc(ctx, log_m - a - an));
     u32* leaves = an ? t.words() : nullptr;
-    if (fd->staged) SC_TRY(rs_fold_many_launch(ctx, cur, log_m, l0, alphas, a, an, n, next, leaves));
-    else SC_TRY(rs_fold_launch(ctx, cur, log_m, l0, alpha, n, next, leaves));
+    SC_TRY(rs_fold_launch(ctx, cur, log_m, l0, alphas, a, an, n, next, leaves, fd->kind));
     if (an) {
       SC_TRY(merkle_finish(ctx, &t, 0, n));
       u0.reset();   // (U_0 goes back to the pool once it is folded; a layer stays with `layers`)

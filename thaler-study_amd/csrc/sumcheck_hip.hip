@@ -259,7 +259,7 @@ struct sc_ctx {
   u64 rs_w_max = 0;
   u64* d_rs_twiddles[15] = {};
   // sc_rs_encode_rows_long / sc_ligero_commit_long: the two twist tables of w_L (kernels/ligero_long.hpp), one run per codeword
-  // length 2^15 .. 2^24 used so far; rs_fold_kernel (kernels/rs_fold.hpp) reads the same tables, from length 2^12 on
+  // length 2^15 .. 2^24 used so far; rs_fold_kernel<F, A, AN> (kernels/rs_fold.hpp) reads the same tables, from length 2^12 on
   u64* d_rs_twist[25] = {};
   // the row encoders whose dynamic LDS above 64 KiB has been requested, by kernel (engine/merkle.inc, allow_dynamic_lds)
   std::set<const void*> lds_allowed;

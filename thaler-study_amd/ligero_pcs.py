@@ -36,14 +36,14 @@ at log_cols 14 - 15 and far more above.
 
 Folded openings (kernels/rs_fold.hpp states the contract): Prover.fold_begin, FoldVerifier and
 open_folded prove the combined row m = u_z + beta u_gamma instead of sending u_gamma and u_z - log_cols rounds of the product
-sumcheck over (m, eq(z[:c])) interleaved with log_cols folds of Enc(m) (sc_ligero_fold_*, one rs_fold_kernel launch per round),
+sumcheck over (m, eq(z[:c])) interleaved with log_cols folds of Enc(m) (sc_ligero_fold_*, one rs_fold_kernel launch per round, the kernel at arity one),
 the folded layers committed with the same leaf and tree.  The opening no longer grows with 2^log_cols and the verifier does
 2 * 2^log_rows + log_cols products per query: fold_opening_bytes and fold_log_cols give its size and the shape that makes it
 smallest.  Reed-Solomon commitments with log_cols >= 1 only; the plain opening stays the default.  No security level is claimed.
 
 Staged folded openings: a schedule `arities` = (a_0, .., a_(S-1)), 1 <= a_s <= 3, sum = log_cols,
 folds a_s variables between two committed layers - a layer's leaf then holds 2^a_s words and there are S - 1 trees instead of
-log_cols - 1 (sc_ligero_fold_begin_staged, one rs_fold_many_kernel launch per stage).  Prover.fold_begin, FoldVerifier and
+log_cols - 1 (sc_ligero_fold_begin_staged, one rs_fold_kernel launch per stage).  Prover.fold_begin, FoldVerifier and
 fold_opening_bytes take `arities`; fold_shape gives the (log_cols, schedule) of the smallest opening; rs_fold_many is the fold
 alone.  arities=None is the binary opening above, unchanged.  The number of queries an arity needs is not analysed."""
 import ctypes

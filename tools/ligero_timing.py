@@ -37,10 +37,13 @@ integers: Goldilocks products do not fit int64), at (20, 10, 1) only.
         widths; writes <out>/expander_long_timing.json and <out>/expander_long_summary.md.
   python tools/ligero_timing.py --fold [--reps 5]
         folded openings (sc_ligero_fold_*) at (n, rho) = (24, 1), (26, 1), (28, 1) with the shape
-        fold_log_cols picks for 128 queries, Goldilocks, in ONE child process: the device time of every rs_fold_kernel launch
+        fold_log_cols picks for 128 queries, Goldilocks, in ONE child process: the device time of every fold launch
         and its rate on the record's bytes against the 6.29 TB/s copy rate, the wall time of begin, prove and query against the
-        wall time of the plain opening (sc_ligero_combine_rows + sc_ligero_open_columns) of the same commitment, and the wall
-        time of FoldVerifier.verify; writes <out>/ligero_fold_timing.json and <out>/ligero_fold_summary.md.
+        wall time of the plain opening (sc_ligero_combine_rows + sc_ligero_open_columns) of the same commitment, the wall
+        time of FoldVerifier.verify, and one sc_rs_fold alone (no tree) at M = 2^16, 2^20, 2^24; writes
+        <out>/ligero_fold_timing.json and <out>/ligero_fold_summary.md.
+  python tools/ligero_timing.py --fold --summary-only --parent A.json B.json
+        adds two --fold runs of the parent commit to ligero_fold_timing.json and their launch-by-launch table to the summary.
   python tools/ligero_timing.py --fold-staged [--reps 5]
         staged folded openings (sc_ligero_fold_begin_staged) at the shapes of --fold: the (log_cols,
         schedule) fold_shape picks beside the binary folded opening at fold_log_cols' shape, in ONE child process: every fold
@@ -71,6 +74,7 @@ XC_LONG_KERNELS = {0: "copy", 1: "down", 2: "inner", 3: "up"}
 P59 = 2**64 - 59
 FOLD_SHAPES = ((24, 1), (26, 1), (28, 1))
 FOLD_QUERIES = 128
+FOLD_ALONE_LOGS = (16, 20, 24)
 
 
 def _timed(ctx, fn, reps):
@@ -278,9 +282,9 @@ def run_fold(reps):
             ctx.check(ctx.lib.sc_ligero_combine_rows(ctx.h, prover.h, weights.ctypes.data_as(u64p), 2, rows.ctypes.data_as(u64p)))
             prover.open_columns(cols)
         walls = {"begin": [], "prove": [], "query": [], "plain": []}
-        log = []
-        for rep in range(reps + 3):             # two warm-up runs, `reps` timed ones, one with the launch log on
-            timed, logged = 2 <= rep < reps + 2, rep == reps + 2
+        logs = []
+        for rep in range(2 * reps + 2):         # two warm-up runs, `reps` timed ones, `reps` with the launch log on
+            timed, logged = 2 <= rep < reps + 2, rep >= reps + 2
             t0 = time.perf_counter()
             opening = prover.fold_begin(point, gamma)
             t1 = time.perf_counter()
@@ -290,7 +294,7 @@ def run_fold(reps):
             opening.prove(beta, lambda i, e, root: alphas[i])
             t2 = time.perf_counter()
             if logged:
-                log = ctx.launch_log()
+                logs.append(ctx.launch_log())
                 ctx.set_option("time_kernels", 0)
             opened = opening.query(indices)
             t3 = time.perf_counter()
@@ -313,16 +317,35 @@ def run_fold(reps):
         opening.close()
         assert value == t.evaluate(point), "the folded opening was accepted with a wrong value"
         prover.close()
+        # a launch's device time: the median over the logged runs, which all queue the same launches in the same order
+        log = [dict(r, ms=statistics.median(x[k]["ms"] for x in logs), ms_all=[x[k]["ms"] for x in logs]) for k, r in enumerate(logs[0])]
         folds = [r for r in log if r["kind"] == "rs_fold"]
         out["shapes"]["%d,%d,%d" % (n, c, rho)] = {
             "log_cols": c, "fold_opening_bytes": lp.fold_opening_bytes(n, c, rho, FOLD_QUERIES),
             "plain_opening_bytes_same_shape": lp.opening_bytes(n, c, rho, FOLD_QUERIES),
             "plain_opening_bytes_best_shape": lp.opening_bytes(n, lp.long_log_cols(n, rho, FOLD_QUERIES), rho, FOLD_QUERIES),
-            "launches": [{"kf": r["kf"], "ks": r["ks"], "ms": r["ms"], "bytes": r["bytes_read"] + r["bytes_written"]} for r in folds],
+            "launches": [{"kf": r["kf"], "ks": r["ks"], "ms": r["ms"], "ms_all": r["ms_all"], "bytes": r["bytes_read"] + r["bytes_written"]} for r in folds],
             "fold_device_ms": sum(r["ms"] for r in folds),
             "prove_device_ms": {k: sum(r["ms"] for r in log if r["kind"] == k) for k in sorted({r["kind"] for r in log})},
             "wall_ms": {k: statistics.median(w) * 1e3 for k, w in walls.items()}, "verify_wall_ms": verify_s * 1e3}
         del t
+    # one stand-alone sc_rs_fold per length: the fold without a tree, which no launch of an opening above M = 4 is
+    out["standalone"] = []
+    for log_m in FOLD_ALONE_LOGS:
+        u = pkg.DenseMultilinearExtension.generate(ctx, 0x11CE0000 + log_m, log_m)
+        alpha = F.rand(random.Random(log_m))
+        for _ in range(2):
+            lp.rs_fold(ctx, u, alpha)
+        ctx.set_option("time_kernels", 1)
+        ctx.launch_log()
+        for _ in range(reps):
+            lp.rs_fold(ctx, u, alpha)
+        ctx.synchronize()
+        recs = [r for r in ctx.launch_log() if r["kind"] == "rs_fold"]
+        ctx.set_option("time_kernels", 0)
+        out["standalone"].append({"kf": recs[0]["kf"], "ks": log_m, "ms": statistics.median(r["ms"] for r in recs), "ms_all": [r["ms"] for r in recs],
+                                  "bytes": recs[0]["bytes_read"] + recs[0]["bytes_written"]})
+        del u
     return out
 
 
@@ -437,21 +460,54 @@ def fold_staged_summary(res):
     return "\n".join(lines) + "\n"
 
 
+def fold_against_parents(step, parents):
+    """the fold launches of this run beside the same launches of two runs of the parent commit (--parent): the margin of a
+    launch is the difference between the two parent runs, and `over` is what this run exceeds the slower parent run plus it by"""
+    lines = ["", "## Against the parent commit: device ms of every fold launch", "",
+             "Two runs of the same command on the parent commit, same machine, same session.  margin = |parent run 1 - parent run 2|; "
+             "over = this run - (max of the parent runs + margin), shown where positive.", "",
+             "| launch | log2 M | hashed | parent run 1 | parent run 2 | margin | this run | over |", "|---|---|---|---|---|---|---|---|"]
+
+    def row(label, ks, hashed, a, b, x):
+        over = x - (max(a, b) + abs(a - b))
+        return "| %s | %s | %s | %.4f | %.4f | %.4f | %.4f | %s |" % (label, ks, hashed, a, b, abs(a - b), x, "%.4f" % over if over > 0 else "-")
+    for key, cur in step["shapes"].items():
+        label = "(%s)" % key.replace(",", ", ")
+        pa, pb = (p["shapes"][key] for p in parents)
+        for r, a, b in zip(cur["launches"], pa["launches"], pb["launches"]):
+            lines.append(row(label, r["ks"], "yes" if r["kf"] else "no", a["ms"], b["ms"], r["ms"]))
+        lines.append(row(label, "sum", "", pa["fold_device_ms"], pb["fold_device_ms"], cur["fold_device_ms"]))
+    for r, a, b in zip(step.get("standalone", []), *(p.get("standalone", []) for p in parents)):
+        lines.append(row("sc_rs_fold alone", r["ks"], "yes" if r["kf"] else "no", a["ms"], b["ms"], r["ms"]))
+    return lines
+
+
 def fold_summary(res):
     step = res["steps"]["fold"]
-    lines = ["# Folded Ligero openings on one MI355X: rs_fold_kernel, the prover's three calls, the host verifier", "",
+    lines = ["# Folded Ligero openings on one MI355X: the fold launches, the prover's three calls, the host verifier", "",
              "Measured by `python tools/ligero_timing.py --fold --reps %d`: every figure comes from ONE process.  Goldilocks, tables from "
              "`sc_table_generate`, %d queries, the shape `fold_log_cols` picks.  Device times: HIP events of the launch log, option "
-             "`time_kernels`, one instrumented run; wall times: medians after two warm-up runs, Python wrappers included.  A fold of "
+             "`time_kernels`, each launch's median over as many instrumented runs as timed ones; wall times: medians after two warm-up "
+             "runs, Python wrappers included.  A fold of "
              "M words reads 8 M bytes and writes 4 M, plus 8 M of digests where it hashes (every launch but the last of an opening); "
              "the yardstick is the chip's measured copy rate, 6.29 TB/s." % (res["reps"], step["queries"]), "",
-             "## Every rs_fold_kernel launch of one opening", "",
+             "## Every fold launch of one opening", "",
              "| (n, c, rho) | log2 M | hashed | device ms | bytes read + written | TB/s | of the 6.29 TB/s copy rate |", "|---|---|---|---|---|---|---|"]
     for key, row in step["shapes"].items():
         for r in row["launches"]:
             bps = r["bytes"] / (r["ms"] * 1e-3) if r["ms"] > 0 else float("nan")
             lines.append("| (%s) | %d | %s | %.4f | %d | %.3f | %.1f %% |" % (key.replace(",", ", "), r["ks"], "yes" if r["kf"] else "no", r["ms"],
                                                                          r["bytes"], bps / 1e12, 100 * bps / COPY_BPS))
+    if step.get("standalone"):
+        lines += ["", "## One sc_rs_fold alone: the fold without a tree", "",
+                  "Median device time of %d launches after two warm-up calls." % res["reps"], "",
+                  "| log2 M | hashed | device ms | bytes read + written | TB/s | of the 6.29 TB/s copy rate |", "|---|---|---|---|---|---|"]
+        for r in step["standalone"]:
+            bps = r["bytes"] / (r["ms"] * 1e-3)
+            lines.append("| %d | %s | %.4f | %d | %.3f | %.1f %% |" % (r["ks"], "yes" if r["kf"] else "no", r["ms"], r["bytes"], bps / 1e12,
+                                                                  100 * bps / COPY_BPS))
+    if res.get("parents"):
+        lines += fold_against_parents(step, [p["steps"]["fold"] for p in res["parents"]])
     lines += ["", "## The opening: folded against plain, same commitment", "",
               "| (n, c, rho) | begin wall ms | prove wall ms | query wall ms | folded total ms | plain (combine + open_columns) wall ms | "
               "all rs_fold launches device ms | FoldVerifier.verify wall ms | folded opening bytes | plain bytes at this shape | plain bytes at its best shape |",
@@ -630,6 +686,7 @@ def main():
     ap.add_argument("--skip-cpu", action="store_true", help="leave the CPU row out (add it later with --cpu-only)")
     ap.add_argument("--cpu-only", action="store_true", help="measure the CPU row alone (no GPU needed), add it to ligero_timing.json, rewrite the summary")
     ap.add_argument("--summary-only", action="store_true", help="rewrite ligero_summary.md from ligero_timing.json")
+    ap.add_argument("--parent", nargs=2, metavar="JSON", help="with --fold --summary-only: two ligero_fold_timing.json of the parent commit to set this run against")
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
     path = os.path.join(args.out, "ligero_timing.json")
@@ -643,6 +700,10 @@ def main():
         if args.summary_only:
             with open(long_path) as fh:
                 res = json.load(fh)
+            if args.parent:
+                res["parents"] = [json.load(open(f)) for f in args.parent]
+                with open(long_path, "w") as fh:
+                    json.dump(res, fh, indent=1)
         else:
             cmd = [sys.executable, os.path.abspath(__file__), "--step", step, "--reps", str(args.reps)]
             p = subprocess.run(cmd, capture_output=True, text=True, timeout=args.limit)
