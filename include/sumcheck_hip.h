@@ -140,6 +140,11 @@ const char* sc_last_error(const sc_ctx* ctx);
  *                      to unsharded provers (incl. a sharded one after its gather) and to multi-device handles; five-round
  *                      passes (and any pass with <= 32 outputs) hand over, 0 = off (a multi-device handle then hands
  *                      over once a shard holds <= 32 entries, as in round 4)
+ *   "gp_host_log"      (default 10; 0..12) sc_gp_prove: the layers of <= 2^gp_host_log entries are proven on the host from one copy
+ *                      of the bottom of the tree, and in every larger layer the launch that writes tables of 2^gp_host_log
+ *                      entries is the last one: the host takes them and finishes the layer.  0: every round on the device,
+ *                      the host folds the last two entries.  Same transcript at every value.  "gp_tree_lv" (default 3;
+ *                      1..3): tree layers per launch of sc_gp_create above its one-block tail.  DESIGN.md section 9 item 16
  *   "grid_pass"        the passes whose FOLDED tables have <= 2^"grid_log" (default 20) entries serve up to
  *                      "grid_max_vars" (default 5) rounds each and fold up to five pending challenges at once
  *                      (wgrid_pass_kernel); "grid_blocks" caps the launch (0 = what fits on the chip at once).
@@ -258,6 +263,11 @@ int sc_ctx_kernel_time(sc_ctx* ctx, double out[2], int reset);
                                 * log_in = log2 of the output length */
 #define SC_KIND_ZEROCHECK 27   /* zc_pass_kernel: one round of sc_zerocheck_prove; kf = 1 if it folded the previous challenge, ks = 1, log_in = log2 of
                                 * the tables it read: 4 * 8 * 2^log_in bytes read, and 4 * 8 * 2^(log_in - 1) written with kf = 1 */
+#define SC_KIND_PRODUCT_TREE 28 /* a launch of sc_gp_create from layer m = log_in of the product tree: kf = LV = 1..3, gp_tree_kernel<F, LV>, which reads
+                                * 8 * 2^m bytes and writes the layers m-1 .. m-LV, 8 * (2^m - 2^(m-LV)); kf = 0, gp_tree_tail_kernel, one block from
+                                * a layer of <= 2^12 words down to V_0: 8 * 2^m read, 8 * (2^m - 1) written; ks = 0 */
+#define SC_KIND_PRODUCT_PASS 29 /* gp_pass_kernel: one round of a layer of sc_gp_prove; kf = 1 if it folded the previous challenge, ks = 1, log_in = log2
+                                * of the tables it read: 3 * 8 * 2^log_in bytes read, and 3 * 8 * 2^(log_in - 1) written with kf = 1 */
 typedef struct sc_launch_record {
   int32_t kind;           /* SC_KIND_* */
   int32_t kf, ks;         /* variables folded / rounds served (meaning per kind above) */
@@ -698,6 +708,37 @@ int sc_r1cs_bind_rows(sc_ctx* ctx, const sc_r1cs* r, const uint64_t* rx, const u
 typedef uint64_t (*sc_draw4_fn)(void* user, size_t round, const uint64_t evals[4]);
 int sc_zerocheck_prove(sc_ctx* ctx, const sc_table* a, const sc_table* b, const sc_table* c, const uint64_t* tau, sc_draw4_fn draw,
                        void* user, uint64_t seed_r, uint64_t* c1, uint64_t* evals, uint64_t* challenges, uint64_t finals[3]);
+
+/* ---- the grand product argument: the product of the 2^n entries of a table is P, reduced to one evaluation claim about the
+ * table's multilinear extension (kernels/grand_product.hpp states the protocol) -----------------
+ * Tree: V_n = t, V_k[x] = V_(k+1)[x] V_(k+1)[x + 2^k], x < 2^k; P = V_0[0].  Layer k = 0 .. n-1 of the proof is a cubic sumcheck
+ * of k rounds over sum_x eq(z_k, x) L_k(x) R_k(x) = c_k with L_k, R_k the two halves of V_(k+1), variable 0 first, four values
+ * H(0..3) per round; then the finals l = L~(r), r' = R~(r), the combining challenge rho_k, c_(k+1) = l + rho_k (r' - l) and
+ * z_(k+1) = (r, rho_k).  After layer n-1 the claim is t~(z_n) = c_n: check it with sc_table_evaluate or an opening of a
+ * commitment to t.  Limits: 1 <= n <= 28, one device and one rank (SC_ERR_UNSUPPORTED on a sharded context or a multi-device
+ * handle, before anything else is looked at), p > 3 (SC_ERR_UNSUPPORTED: the cubic through 0, 1, 2, 3 needs 2 and 3
+ * invertible).  SC_ERR_ARG: a NULL argument, a table of fewer than two or more than 2^28 entries, a layer k >= n, a word of a
+ * challenge, alpha or beta that is not below p.  No security level, no zero knowledge and no Fiat-Shamir are claimed. */
+typedef struct sc_gp sc_gp;
+/* Builds the tree (SC_KIND_PRODUCT_TREE launches) into one pool block of 2^n words, layer k at words [2^k, 2^(k+1)); t is
+ * borrowed until sc_gp_destroy and never written. */
+int sc_gp_create(sc_ctx* ctx, const sc_table* t, sc_gp** out);
+int sc_gp_destroy(sc_ctx* ctx, sc_gp* g);
+/* *out = V_0[0] */
+int sc_gp_product(const sc_gp* g, uint64_t* out);
+/* a copy of V_k, 0 <= k < n: a new table of 2^k words */
+int sc_gp_layer(sc_ctx* ctx, const sc_gp* g, size_t k, sc_table** out);
+/* round < layer: msg = H(0..3) of that round, returns r_round; round == layer: msg = (l, r'), returns rho_layer.  A word below p. */
+typedef uint64_t (*sc_draw_gp_fn)(void* user, size_t layer, size_t round, const uint64_t* msg);
+/* The n layers.  evals (4 n (n-1) / 2 words, may be NULL): every round's four values, layer by layer; finals (2 n words):
+ * (l, r') of every layer; challenges (n (n-1) / 2 + n words, may be NULL): in protocol order, the rounds' challenges of a layer
+ * and then its rho; point (n words) = z_n; *claim = c_n.  draw == NULL: the synthetic challenger of sc_prove over seed_r, one
+ * draw per round and one per rho in protocol order.  One launch per round of a layer (SC_KIND_PRODUCT_PASS) down to the
+ * hand-over to the host (option "gp_host_log"). */
+int sc_gp_prove(sc_ctx* ctx, const sc_gp* g, sc_draw_gp_fn draw, void* user, uint64_t seed_r, uint64_t* evals, uint64_t* finals,
+                uint64_t* challenges, uint64_t* point, uint64_t* claim);
+/* out[i] = alpha t[i] + beta: a new table of the length of t (at least two entries) */
+int sc_table_affine(sc_ctx* ctx, const sc_table* t, uint64_t alpha, uint64_t beta, sc_table** out);
 
 /* ---- gkr_protocol::circuit::Circuit on the device, and the whole GKR prover over it ----------------------------------
  * A circuit lives on ONE context of one device and one rank: sharded contexts (world > 1) and multi-device handles get

@@ -111,6 +111,12 @@ pub struct sc_r1cs {
     _private: [u8; 0],
 }
 
+/// a product tree on the device (`sc_gp_create`)
+#[repr(C)]
+pub struct sc_gp {
+    _private: [u8; 0],
+}
+
 pub type sc_allreduce_fn = Option<unsafe extern "C" fn(user: *mut c_void, buf: *mut u64, count: usize) -> c_int>;
 pub type sc_allgather_fn =
     Option<unsafe extern "C" fn(user: *mut c_void, send: *const u64, recv: *mut u64, count: usize) -> c_int>;
@@ -119,6 +125,8 @@ pub type sc_draw_fn = Option<unsafe extern "C" fn(user: *mut c_void, round: usiz
 pub type sc_draw_fold_fn = Option<unsafe extern "C" fn(user: *mut c_void, round: usize, evals: *const u64, root: *const u8) -> u64>;
 /// `sc_zerocheck_prove`: the verifier's challenge of a round; `evals` = the round's H(0), H(1), H(2), H(3).
 pub type sc_draw4_fn = Option<unsafe extern "C" fn(user: *mut c_void, round: usize, evals: *const u64) -> u64>;
+/// `sc_gp_prove`: `round < layer`: `msg` = H(0..3) of that round, returns its challenge; `round == layer`: `msg` = (l, r'), returns rho
+pub type sc_draw_gp_fn = Option<unsafe extern "C" fn(user: *mut c_void, layer: usize, round: usize, msg: *const u64) -> u64>;
 /// `sc_prove_batch`: called round by round, within a round in instance order.
 pub type sc_draw_batch_fn = Option<unsafe extern "C" fn(user: *mut c_void, instance: usize, round: usize, evals: *const u64) -> u64>;
 
@@ -620,4 +628,27 @@ extern "C" {
         challenges: *mut u64,
         finals: *mut u64,
     ) -> c_int;
+    /// the product tree of a table of 2^n entries, 1 <= n <= 28 (SC_KIND_PRODUCT_TREE, 28); `t` is borrowed until `sc_gp_destroy`
+    pub fn sc_gp_create(ctx: *mut sc_ctx, t: *const sc_table, out: *mut *mut sc_gp) -> c_int;
+    pub fn sc_gp_destroy(ctx: *mut sc_ctx, g: *mut sc_gp) -> c_int;
+    /// V_0[0], the product of the table's entries
+    pub fn sc_gp_product(g: *const sc_gp, out: *mut u64) -> c_int;
+    /// a copy of layer k < n of the tree: a new table of 2^k words
+    pub fn sc_gp_layer(ctx: *mut sc_ctx, g: *const sc_gp, k: usize, out: *mut *mut sc_table) -> c_int;
+    /// the n layers of the grand product argument: one launch per device round, SC_KIND_PRODUCT_PASS (29); evals 4 n (n-1) / 2 words or
+    /// null, finals 2 n, challenges n (n-1) / 2 + n or null, point n, claim 1
+    pub fn sc_gp_prove(
+        ctx: *mut sc_ctx,
+        g: *const sc_gp,
+        draw: sc_draw_gp_fn,
+        user: *mut c_void,
+        seed_r: u64,
+        evals: *mut u64,
+        finals: *mut u64,
+        challenges: *mut u64,
+        point: *mut u64,
+        claim: *mut u64,
+    ) -> c_int;
+    /// out[i] = alpha t[i] + beta: a new table
+    pub fn sc_table_affine(ctx: *mut sc_ctx, t: *const sc_table, alpha: u64, beta: u64, out: *mut *mut sc_table) -> c_int;
 }

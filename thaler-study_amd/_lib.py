@@ -51,7 +51,9 @@ class ScLaunchRecord(ctypes.Structure):
 
 KIND_NAMES = {0: "pass", 2: "evaluate", 3: "fold", 4: "fix_low", 5: "fold_be", 6: "coldot", 7: "gkr", 8: "matsq", 10: "grid_pass", 11: "gram_pass", 13: "wfold_pass", 14: "circuit", 15: "matmul", 16: "batch_pass",
               17: "grid_extend", 18: "merkle", 19: "rs_encode", 20: "ligero", 21: "xc_encode", 22: "rs_long", 23: "xc_long", 24: "rs_fold", 25: "rs_fold_many",
-              26: "spmv", 27: "zerocheck"}
+              26: "spmv", 27: "zerocheck", 28: "product_tree", 29: "product_pass"}
+# SC_KIND_PRODUCT_TREE records: kf -> the kernel that ran (kf = LV layers per launch; 0: the one-block tail)
+PRODUCT_TREE_KERNELS = {0: "gp_tree_tail_kernel", 1: "gp_tree_kernel<1>", 2: "gp_tree_kernel<2>", 3: "gp_tree_kernel<3>"}
 # SC_KIND_SPMV records: kf -> the kernel that ran
 SPMV_KERNELS = {0: "spmv_kernel", 1: "spmv_carry_kernel"}
 # SC_KIND_LIGERO records: kf -> the kernel that ran
@@ -67,6 +69,7 @@ ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, voidp, u64p, u64p, size_t)
 DRAW_FN = ctypes.CFUNCTYPE(u64, voidp, size_t, u64p)
 DRAW_BATCH_FN = ctypes.CFUNCTYPE(u64, voidp, size_t, size_t, u64p)
 DRAW4_FN = ctypes.CFUNCTYPE(u64, voidp, size_t, u64p)           # sc_zerocheck_prove: evals = H(0), H(1), H(2), H(3)
+DRAW_GP_FN = ctypes.CFUNCTYPE(u64, voidp, size_t, size_t, u64p)    # sc_gp_prove: msg = H(0..3) of a round, or (l, r') when round == layer
 DRAW_FOLD_FN = ctypes.CFUNCTYPE(u64, voidp, size_t, u64p, voidp)   # root: 32 bytes, NULL at round 0
 
 # name -> (restype, argtypes); every symbol include/sumcheck_hip.h declares
@@ -172,6 +175,12 @@ SIGNATURES = {
     "sc_r1cs_mul": (ctypes.c_int, [voidp, voidp, voidp, ctypes.POINTER(voidp), ctypes.POINTER(voidp), ctypes.POINTER(voidp)]),
     "sc_r1cs_bind_rows": (ctypes.c_int, [voidp, voidp, u64p, u64p, ctypes.POINTER(voidp)]),
     "sc_zerocheck_prove": (ctypes.c_int, [voidp, voidp, voidp, voidp, u64p, DRAW4_FN, voidp, u64, u64p, u64p, u64p, u64p]),
+    "sc_gp_create": (ctypes.c_int, [voidp, voidp, ctypes.POINTER(voidp)]),
+    "sc_gp_destroy": (ctypes.c_int, [voidp, voidp]),
+    "sc_gp_product": (ctypes.c_int, [voidp, u64p]),
+    "sc_gp_layer": (ctypes.c_int, [voidp, voidp, size_t, ctypes.POINTER(voidp)]),
+    "sc_gp_prove": (ctypes.c_int, [voidp, voidp, DRAW_GP_FN, voidp, u64, u64p, u64p, u64p, u64p, u64p]),
+    "sc_table_affine": (ctypes.c_int, [voidp, voidp, u64, u64, ctypes.POINTER(voidp)]),
     "sc_circuit_create": (ctypes.c_int, [voidp, size_t, ctypes.POINTER(size_t), ctypes.POINTER(ctypes.POINTER(ctypes.c_int32)),
                                           ctypes.POINTER(ctypes.POINTER(ctypes.c_uint32)), ctypes.POINTER(ctypes.POINTER(ctypes.c_uint32)),
                                           ctypes.POINTER(voidp)]),

@@ -190,6 +190,8 @@ const OptionSpec kOptions[] = {
     {"wfold_always", &sc_ctx::wfold_always, 0, 1, kOptBool},
     {"matmul_path", &sc_ctx::matmul_path, 0, 2, 0},   // 0 auto, 1 int8 matrix cores, 2 VALU
     {"host_tail_log", &sc_ctx::host_tail_log, 0, kTailLogMax, 0},
+    {"gp_host_log", &sc_ctx::gp_host_log, 0, sc::kGpHostLogMax, 0},
+    {"gp_tree_lv", &sc_ctx::gp_tree_lv, 1, 3, 0},
     {"tail_log", &sc_ctx::tail_log, 0, 40, 0},
     {"max_blocks", &sc_ctx::max_blocks, 1, INT64_MAX, 0},   // (1..partial_rows: sc_ctx_set_option)
     {"time_kernels", &sc_ctx::time_kernels, 0, 1, kOptBool},   // recorded pairs stay in the ring until it fills or the totals are read
