@@ -145,6 +145,11 @@ const char* sc_last_error(const sc_ctx* ctx);
  *                      entries is the last one: the host takes them and finishes the layer.  0: every round on the device,
  *                      the host folds the last two entries.  Same transcript at every value.  "gp_tree_lv" (default 3;
  *                      1..3): tree layers per launch of sc_gp_create above its one-block tail.  DESIGN.md section 9 item 16
+ *   "fr_host_log"      (default 9; 0..12)  sc_frac_prove: what "gp_host_log" is to sc_gp_prove, over the two fraction trees: the layers
+ *                      of <= 2^fr_host_log entries are proven on the host from one copy of the bottom of both trees, and in every
+ *                      larger layer the launch that writes tables of 2^fr_host_log entries is the last one.  Same transcript at
+ *                      every value.  "fr_tree_lv" (default 3; 1..3): tree layers per launch of sc_frac_create above its one-block
+ *                      tail.  DESIGN.md section 9 item 17
  *   "grid_pass"        the passes whose FOLDED tables have <= 2^"grid_log" (default 20) entries serve up to
  *                      "grid_max_vars" (default 5) rounds each and fold up to five pending challenges at once
  *                      (wgrid_pass_kernel); "grid_blocks" caps the launch (0 = what fits on the chip at once).
@@ -268,6 +273,16 @@ int sc_ctx_kernel_time(sc_ctx* ctx, double out[2], int reset);
                                 * a layer of <= 2^12 words down to V_0: 8 * 2^m read, 8 * (2^m - 1) written; ks = 0 */
 #define SC_KIND_PRODUCT_PASS 29 /* gp_pass_kernel: one round of a layer of sc_gp_prove; kf = 1 if it folded the previous challenge, ks = 1, log_in = log2
                                 * of the tables it read: 3 * 8 * 2^log_in bytes read, and 3 * 8 * 2^(log_in - 1) written with kf = 1 */
+#define SC_KIND_FRACTION_TREE 30 /* a launch of sc_frac_create from layer m = log_in of the two fraction trees: kf = LV = 1..3, fr_tree_kernel<F, LV, ONES>;
+                                 * ks = the tables it read: 2, or 1 where the numerator is all ones (m = n); it reads ks * 8 * 2^m bytes and writes
+                                 * the layers m-1 .. m-LV of both trees, 2 * 8 * (2^m - 2^(m-LV)); kf = 0, fr_tree_tail_kernel, one block from a layer
+                                 * of <= 2^11 entries down to the root: 2 * 8 * (2^m - 1) written */
+#define SC_KIND_FRACTION_PASS 31 /* fr_pass_kernel: one round of a layer of sc_frac_prove; kf = 1 if it folded the previous challenge, ks = the tables it
+                                 * read: 5 (E, QL, QR, PL, PR), or 3 in the top layer of an all-ones numerator; log_in = log2 of the tables it read:
+                                 * ks * 8 * 2^log_in bytes read, and ks * 8 * 2^(log_in - 1) written with kf = 1 */
+#define SC_KIND_LOOKUP_COUNT 32  /* sc_lookup_count: kf = 0 lookup_count_kernel (ks = 1: a private histogram per block in LDS, m <= 13; 0: adds to
+                                 * global memory; log_in = n; reads 12 * 2^n bytes of w and idx and gathers 8 * 2^n of t, writes 4 * 2^m of
+                                 * counters), kf = 1 lookup_mont_kernel (log_in = m; reads 4 * 2^m, writes 8 * 2^m) */
 typedef struct sc_launch_record {
   int32_t kind;           /* SC_KIND_* */
   int32_t kf, ks;         /* variables folded / rounds served (meaning per kind above) */
@@ -739,6 +754,43 @@ int sc_gp_prove(sc_ctx* ctx, const sc_gp* g, sc_draw_gp_fn draw, void* user, uin
                 uint64_t* challenges, uint64_t* point, uint64_t* claim);
 /* out[i] = alpha t[i] + beta: a new table of the length of t (at least two entries) */
 int sc_table_affine(sc_ctx* ctx, const sc_table* t, uint64_t alpha, uint64_t beta, sc_table** out);
+
+/* ---- LogUp lookups: the sum of 2^n fractions p_i / q_i is P / Q, reduced to one evaluation claim about p and one about q
+ * (kernels/fraction.hpp states the protocol) -----------------------------------------------------
+ * Trees: layer n = (p, q); p_k[x] = p_(k+1)[x] q_(k+1)[x + 2^k] + p_(k+1)[x + 2^k] q_(k+1)[x], q_k[x] = q_(k+1)[x] q_(k+1)[x + 2^k],
+ * x < 2^k; (P, Q) = (p_0[0], q_0[0]).  Layer k = 0 .. n-1 of the proof: V's lambda_k (k >= 1), a cubic sumcheck of k rounds over
+ * sum_x eq(z_k, x) (PL QR + PR QL + lambda_k QL QR)(x) = a_k + lambda_k b_k with PL, PR, QL, QR the halves of layer k+1, variable 0
+ * first, four values H(0..3) per round; then the finals pl, pr, ql, qr, the combining challenge rho_k, a_(k+1) = pl + rho_k (pr - pl),
+ * b_(k+1) = ql + rho_k (qr - ql) and z_(k+1) = (r, rho_k).  After layer n-1 the claims are p~(z_n) = a_n and q~(z_n) = b_n.
+ * p == NULL: the numerator is all ones (the top layer reads three tables, not five; its finals pl = pr = 1; a_n must be 1).
+ * Limits: 1 <= n <= 28, one device and one rank (SC_ERR_UNSUPPORTED on a sharded context or a multi-device handle, before
+ * anything else is looked at), p > 3 (SC_ERR_UNSUPPORTED).  SC_ERR_ARG: a NULL argument, tables of different lengths, of fewer
+ * than two or more than 2^28 entries, a layer k >= n, a challenge that is not a word below p.  No security level, no zero
+ * knowledge and no Fiat-Shamir are claimed. */
+typedef struct sc_frac sc_frac;
+/* Builds both trees (SC_KIND_FRACTION_TREE launches) into two pool blocks of 2^n words, layer k at words [2^k, 2^(k+1)); p (may be
+ * NULL: all ones) and q are borrowed until sc_frac_destroy and never written. */
+int sc_frac_create(sc_ctx* ctx, const sc_table* p, const sc_table* q, sc_frac** out);
+int sc_frac_destroy(sc_ctx* ctx, sc_frac* g);
+/* out = (P, Q) */
+int sc_frac_root(const sc_frac* g, uint64_t out[2]);
+/* a copy of layer k, 0 <= k < n, of p (which = 0) or q (which = 1): a new table of 2^k words */
+int sc_frac_layer(sc_ctx* ctx, const sc_frac* g, size_t k, int which, sc_table** out);
+/* round < layer: msg = H(0..3) of that round, returns r_round; round == layer: msg = (pl, pr, ql, qr), returns rho_layer;
+ * round == layer + 1: msg = NULL, returns lambda of layer + 1 (not called after the last layer).  A word below p. */
+typedef uint64_t (*sc_draw_frac_fn)(void* user, size_t layer, size_t round, const uint64_t* msg);
+/* The n layers.  evals (4 n (n-1) / 2 words, may be NULL): every round's four values, layer by layer; finals (4 n words):
+ * (pl, pr, ql, qr) of every layer; challenges (n (n-1) / 2 + 2 n - 1 words, may be NULL): as they were drawn - rho_0, then per
+ * layer k >= 1 lambda_k, its rounds' challenges and rho_k; point (n words) = z_n; claims = (a_n, b_n).  draw == NULL: the
+ * synthetic challenger of sc_prove over seed_r, one draw per lambda, per round and per rho in that order.  One launch per round of a
+ * layer (SC_KIND_FRACTION_PASS) down to the hand-over to the host (option "fr_host_log"). */
+int sc_frac_prove(sc_ctx* ctx, const sc_frac* g, sc_draw_frac_fn draw, void* user, uint64_t seed_r, uint64_t* evals, uint64_t* finals,
+                  uint64_t* challenges, uint64_t* point, uint64_t claims[2]);
+/* The multiplicities of a lookup: w (2^n entries), t (2^m entries), idx_host (2^n host words of 32 bits).  Every i with
+ * idx_host[i] < 2^m and w[i] == t[idx_host[i]] adds one to entry idx_host[i] of *mult, a new table of t's length (Montgomery words
+ * of the counts); every other i adds one to *mismatches and is not counted (SC_KIND_LOOKUP_COUNT).  SC_ERR_UNSUPPORTED:
+ * p <= 2^max(n, m) (a count must be a field word). */
+int sc_lookup_count(sc_ctx* ctx, const sc_table* w, const sc_table* t, const uint32_t* idx_host, sc_table** mult, uint64_t* mismatches);
 
 /* ---- gkr_protocol::circuit::Circuit on the device, and the whole GKR prover over it ----------------------------------
  * A circuit lives on ONE context of one device and one rank: sharded contexts (world > 1) and multi-device handles get

@@ -117,6 +117,12 @@ pub struct sc_gp {
     _private: [u8; 0],
 }
 
+/// a pair of fraction-sum trees on the device (`sc_frac_create`)
+#[repr(C)]
+pub struct sc_frac {
+    _private: [u8; 0],
+}
+
 pub type sc_allreduce_fn = Option<unsafe extern "C" fn(user: *mut c_void, buf: *mut u64, count: usize) -> c_int>;
 pub type sc_allgather_fn =
     Option<unsafe extern "C" fn(user: *mut c_void, send: *const u64, recv: *mut u64, count: usize) -> c_int>;
@@ -127,6 +133,9 @@ pub type sc_draw_fold_fn = Option<unsafe extern "C" fn(user: *mut c_void, round:
 pub type sc_draw4_fn = Option<unsafe extern "C" fn(user: *mut c_void, round: usize, evals: *const u64) -> u64>;
 /// `sc_gp_prove`: `round < layer`: `msg` = H(0..3) of that round, returns its challenge; `round == layer`: `msg` = (l, r'), returns rho
 pub type sc_draw_gp_fn = Option<unsafe extern "C" fn(user: *mut c_void, layer: usize, round: usize, msg: *const u64) -> u64>;
+/// `sc_frac_prove`: `round < layer`: `msg` = H(0..3), returns its challenge; `round == layer`: `msg` = (pl, pr, ql, qr), returns rho;
+/// `round == layer + 1`: `msg` is null, returns lambda of the next layer
+pub type sc_draw_frac_fn = Option<unsafe extern "C" fn(user: *mut c_void, layer: usize, round: usize, msg: *const u64) -> u64>;
 /// `sc_prove_batch`: called round by round, within a round in instance order.
 pub type sc_draw_batch_fn = Option<unsafe extern "C" fn(user: *mut c_void, instance: usize, round: usize, evals: *const u64) -> u64>;
 
@@ -651,4 +660,35 @@ extern "C" {
     ) -> c_int;
     /// out[i] = alpha t[i] + beta: a new table
     pub fn sc_table_affine(ctx: *mut sc_ctx, t: *const sc_table, alpha: u64, beta: u64, out: *mut *mut sc_table) -> c_int;
+    /// the fraction-sum trees of (p, q), 2^n entries each, 1 <= n <= 28 (SC_KIND_FRACTION_TREE, 30); `p` null: all ones; both are
+    /// borrowed until `sc_frac_destroy`
+    pub fn sc_frac_create(ctx: *mut sc_ctx, p: *const sc_table, q: *const sc_table, out: *mut *mut sc_frac) -> c_int;
+    pub fn sc_frac_destroy(ctx: *mut sc_ctx, g: *mut sc_frac) -> c_int;
+    /// out[0..2] = (P, Q), the root of the trees
+    pub fn sc_frac_root(g: *const sc_frac, out: *mut u64) -> c_int;
+    /// a copy of layer k < n of p (`which` = 0) or q (1): a new table of 2^k words
+    pub fn sc_frac_layer(ctx: *mut sc_ctx, g: *const sc_frac, k: usize, which: c_int, out: *mut *mut sc_table) -> c_int;
+    /// the n layers of the fractional sumcheck: one launch per device round, SC_KIND_FRACTION_PASS (31); evals 4 n (n-1) / 2 words or
+    /// null, finals 4 n, challenges n (n-1) / 2 + 2 n - 1 or null, point n, claims 2
+    pub fn sc_frac_prove(
+        ctx: *mut sc_ctx,
+        g: *const sc_frac,
+        draw: sc_draw_frac_fn,
+        user: *mut c_void,
+        seed_r: u64,
+        evals: *mut u64,
+        finals: *mut u64,
+        challenges: *mut u64,
+        point: *mut u64,
+        claims: *mut u64,
+    ) -> c_int;
+    /// the multiplicities of a lookup (SC_KIND_LOOKUP_COUNT, 32): `mult` a new table of t's length, `mismatches` the entries left out
+    pub fn sc_lookup_count(
+        ctx: *mut sc_ctx,
+        w: *const sc_table,
+        t: *const sc_table,
+        idx_host: *const u32,
+        mult: *mut *mut sc_table,
+        mismatches: *mut u64,
+    ) -> c_int;
 }

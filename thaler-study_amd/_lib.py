@@ -51,7 +51,11 @@ class ScLaunchRecord(ctypes.Structure):
 
 KIND_NAMES = {0: "pass", 2: "evaluate", 3: "fold", 4: "fix_low", 5: "fold_be", 6: "coldot", 7: "gkr", 8: "matsq", 10: "grid_pass", 11: "gram_pass", 13: "wfold_pass", 14: "circuit", 15: "matmul", 16: "batch_pass",
               17: "grid_extend", 18: "merkle", 19: "rs_encode", 20: "ligero", 21: "xc_encode", 22: "rs_long", 23: "xc_long", 24: "rs_fold", 25: "rs_fold_many",
-              26: "spmv", 27: "zerocheck", 28: "product_tree", 29: "product_pass"}
+              26: "spmv", 27: "zerocheck", 28: "product_tree", 29: "product_pass", 30: "fraction_tree", 31: "fraction_pass", 32: "lookup_count"}
+# SC_KIND_FRACTION_TREE records: kf -> the kernel that ran (kf = LV layers per launch; 0: the one-block tail)
+FRACTION_TREE_KERNELS = {0: "fr_tree_tail_kernel", 1: "fr_tree_kernel<1>", 2: "fr_tree_kernel<2>", 3: "fr_tree_kernel<3>"}
+# SC_KIND_LOOKUP_COUNT records: kf -> the kernel that ran
+LOOKUP_COUNT_KERNELS = {0: "lookup_count_kernel", 1: "lookup_mont_kernel"}
 # SC_KIND_PRODUCT_TREE records: kf -> the kernel that ran (kf = LV layers per launch; 0: the one-block tail)
 PRODUCT_TREE_KERNELS = {0: "gp_tree_tail_kernel", 1: "gp_tree_kernel<1>", 2: "gp_tree_kernel<2>", 3: "gp_tree_kernel<3>"}
 # SC_KIND_SPMV records: kf -> the kernel that ran
@@ -70,6 +74,7 @@ DRAW_FN = ctypes.CFUNCTYPE(u64, voidp, size_t, u64p)
 DRAW_BATCH_FN = ctypes.CFUNCTYPE(u64, voidp, size_t, size_t, u64p)
 DRAW4_FN = ctypes.CFUNCTYPE(u64, voidp, size_t, u64p)           # sc_zerocheck_prove: evals = H(0), H(1), H(2), H(3)
 DRAW_GP_FN = ctypes.CFUNCTYPE(u64, voidp, size_t, size_t, u64p)    # sc_gp_prove: msg = H(0..3) of a round, or (l, r') when round == layer
+DRAW_FRAC_FN = ctypes.CFUNCTYPE(u64, voidp, size_t, size_t, u64p)  # sc_frac_prove: msg = H(0..3), (pl, pr, ql, qr) when round == layer, NULL for a lambda
 DRAW_FOLD_FN = ctypes.CFUNCTYPE(u64, voidp, size_t, u64p, voidp)   # root: 32 bytes, NULL at round 0
 
 # name -> (restype, argtypes); every symbol include/sumcheck_hip.h declares
@@ -181,6 +186,12 @@ SIGNATURES = {
     "sc_gp_layer": (ctypes.c_int, [voidp, voidp, size_t, ctypes.POINTER(voidp)]),
     "sc_gp_prove": (ctypes.c_int, [voidp, voidp, DRAW_GP_FN, voidp, u64, u64p, u64p, u64p, u64p, u64p]),
     "sc_table_affine": (ctypes.c_int, [voidp, voidp, u64, u64, ctypes.POINTER(voidp)]),
+    "sc_frac_create": (ctypes.c_int, [voidp, voidp, voidp, ctypes.POINTER(voidp)]),
+    "sc_frac_destroy": (ctypes.c_int, [voidp, voidp]),
+    "sc_frac_root": (ctypes.c_int, [voidp, u64p]),
+    "sc_frac_layer": (ctypes.c_int, [voidp, voidp, size_t, ctypes.c_int, ctypes.POINTER(voidp)]),
+    "sc_frac_prove": (ctypes.c_int, [voidp, voidp, DRAW_FRAC_FN, voidp, u64, u64p, u64p, u64p, u64p, u64p]),
+    "sc_lookup_count": (ctypes.c_int, [voidp, voidp, voidp, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(voidp), u64p]),
     "sc_circuit_create": (ctypes.c_int, [voidp, size_t, ctypes.POINTER(size_t), ctypes.POINTER(ctypes.POINTER(ctypes.c_int32)),
                                           ctypes.POINTER(ctypes.POINTER(ctypes.c_uint32)), ctypes.POINTER(ctypes.POINTER(ctypes.c_uint32)),
                                           ctypes.POINTER(voidp)]),

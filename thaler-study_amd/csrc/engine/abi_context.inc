@@ -192,6 +192,8 @@ const OptionSpec kOptions[] = {
     {"host_tail_log", &sc_ctx::host_tail_log, 0, kTailLogMax, 0},
     {"gp_host_log", &sc_ctx::gp_host_log, 0, sc::kGpHostLogMax, 0},
     {"gp_tree_lv", &sc_ctx::gp_tree_lv, 1, 3, 0},
+    {"fr_host_log", &sc_ctx::fr_host_log, 0, sc::kFrHostLogMax, 0},
+    {"fr_tree_lv", &sc_ctx::fr_tree_lv, 1, sc::kFrTreeLvMax, 0},
     {"tail_log", &sc_ctx::tail_log, 0, 40, 0},
     {"max_blocks", &sc_ctx::max_blocks, 1, INT64_MAX, 0},   // (1..partial_rows: sc_ctx_set_option)
     {"time_kernels", &sc_ctx::time_kernels, 0, 1, kOptBool},   // recorded pairs stay in the ring until it fills or the totals are read

@@ -269,3 +269,4 @@ __device__ __forceinline__ void transpose_to_pieces(ull2* __restrict__ lds, ull2
 #include "kernels/peer.hpp"
 #include "kernels/r1cs.hpp"
 #include "kernels/grand_product.hpp"
+#include "kernels/fraction.hpp"

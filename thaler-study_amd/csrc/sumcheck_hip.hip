@@ -159,6 +159,8 @@ struct sc_ctx {
   int matmul_path = 0;               // sc_matmul: 0 auto (the int8 matrix cores from 32 x 32), 1 matrix cores (from 16 x 16), 2 VALU
   int gp_host_log = 10;              // sc_gp_prove: layers of <= 2^this entries, and the last 2^this entries of every larger one, are proven on the host (measured: DESIGN.md section 9 item 16)
   int gp_tree_lv = sc::kGpTreeLv;    // sc_gp_create: tree layers per launch above the tail (1..3)
+  int fr_host_log = 9;               // sc_frac_prove: as gp_host_log, over the fraction trees (measured: DESIGN.md section 9 item 17)
+  int fr_tree_lv = sc::kFrTreeLv;    // sc_frac_create: tree layers per launch above the tail (1..3)
   int tail_log = 16;  // shard log-size at which a sharded prover gathers: a 512 KiB all-gather per table is
                       // cheaper than the ~25 us of collective latency of each further sharded pass
   // grid cap of the streaming kernels: three 256-thread blocks per CU (set in sc_ctx_create).
@@ -609,4 +611,5 @@ static int multi_prod2_fold_and_sums(sc_ctx* m, const sc_table* a, const sc_tabl
 #include "engine/abi_fold.inc"       // folded openings of a Reed-Solomon commitment
 #include "engine/abi_r1cs.inc"       // rank-1 constraint systems: sparse products and the cubic sumcheck
 #include "engine/abi_grand_product.inc"   // the grand product argument: product tree and layered cubic sumcheck
+#include "engine/abi_fraction.inc"        // LogUp lookups: fraction-sum trees, their layered cubic sumcheck, the multiplicities
 #include "engine/abi_multi.inc"
