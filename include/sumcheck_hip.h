@@ -128,6 +128,16 @@ const char* sc_last_error(const sc_ctx* ctx);
  *                      alternative is a grid pass streaming the whole table (n = 21..24); "wfold_always" = 1: wherever it can
  *                      run.  "wfold5_min_log" (default 24): a grid pass with FIVE challenges to fold over tables of >= 2^this
  *                      entries runs in the same kernel's (5, 3..5) form.  Same results; DESIGN.md sections 4, 5
+ *   "wfold_slot_period" (default -1; 0 = off; 1..2^24 in ticks of the device's 100 MHz wall clock, i.e. 10 ns) wfold_pass_kernel's
+ *                      writes of the folded tables aligned in time across the chip: every XCD reads the same clock, so slots
+ *                      [k period, k period + width) open on all of them at once, without communication and without any wave
+ *                      waiting.  "wfold_slot_width" = 0: only the bulk write-back requests move to the period's boundaries;
+ *                      > 0: a wave holds a tile's outputs in registers and stores them at the first sub-step boundary inside a
+ *                      slot, at the end of its next tile at the latest (>= period: always open).  "wfold_slot_stagger" = 1
+ *                      shifts the slots of the eight XCDs against each other by period / 8: the control of the measurement.
+ *                      -1: period 2400 and width 600 (a 6 us slot every 24 us) for the four-challenge fold of tables of
+ *                      >= 2^25 entries, where that was measured to pay (n = 28: 779 -> 734 us), none elsewhere; width and
+ *                      stagger apply to an explicit period only.  Same results bit for bit at every setting; DESIGN.md section 5
  *   "host_tail_log"    (default 12; 0..12) the host finishes the proof: a pass whose folded tables have <= 2^host_tail_log
  *                      entries (per device on a multi-device handle) writes them to pinned host memory instead of the
  *                      pool, and every later round is served by the host from them - fold the pending challenges

@@ -188,6 +188,9 @@ const OptionSpec kOptions[] = {
     {"wfold_min_log", &sc_ctx::wfold_min_log, 12, 40, 0},
     {"wfold5_min_log", &sc_ctx::wfold5_min_log, 12, 40, 0},
     {"wfold_always", &sc_ctx::wfold_always, 0, 1, kOptBool},
+    {"wfold_slot_period", &sc_ctx::wfold_slot_period, -1, 1 << 24, 0},   // ticks of 10 ns; 0: no slots; -1: by table size (launch_wfold_pass)
+    {"wfold_slot_width", &sc_ctx::wfold_slot_width, 0, 1 << 24, 0},
+    {"wfold_slot_stagger", &sc_ctx::wfold_slot_stagger, 0, 1, kOptBool},
     {"matmul_path", &sc_ctx::matmul_path, 0, 2, 0},   // 0 auto, 1 int8 matrix cores, 2 VALU
     {"host_tail_log", &sc_ctx::host_tail_log, 0, kTailLogMax, 0},
     {"gp_host_log", &sc_ctx::gp_host_log, 0, sc::kGpHostLogMax, 0},

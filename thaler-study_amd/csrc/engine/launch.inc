@@ -378,12 +378,28 @@ int launch_wfold_pass(sc_ctx* ctx, int kf, int ks, const u64* A, const u64* B, u
   const int grid = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(n_tiles, (size_t)wfold_resident_blocks(ctx)), (size_t)ctx->max_blocks));
   const sc::WgOut wo = next_wide_out(ctx, across_ranks, challenge_digest(r, kf, ks, log_in) ^ 0x77666f6cu, true, false);
   SC_TRY(timer_begin(ctx, SC_KIND_WFOLD_PASS, kf, ks, log_in, (u64)16 << log_in, (u64)16 << (log_in - kf)));
+  // the clock-aligned write slots (options "wfold_slot_*"): period 0 launches the kernel without them.  By default (-1) where they
+  // were measured to pay - the four-challenge fold of tables of >= 2^25 entries, a 6 us slot every 24 us (one tile per wave and
+  // period): 779 -> 734 us at 2^28, 112 -> 109 at 2^25, the staggered twin 796 / 115 (profiles/wfold_slots_sweep.txt); the (5, 3)
+  // form at 2^24, two tiles per wave, gains nothing (57.1 -> 56.9 us) and stays without
+  sc::WfSlots sl;
+  if (ctx->wfold_slot_period < 0) {
+    sl.period = (kf == 4 && log_in >= 25) ? 2400u : 0u;
+    sl.width = 600u;
+  } else {
+    sl.period = (unsigned)ctx->wfold_slot_period;
+    sl.width = (unsigned)ctx->wfold_slot_width;
+    sl.stagger = (unsigned)ctx->wfold_slot_stagger;
+  }
   SC_DISPATCH_FIELD(ctx, F, f, with_bool(log_in >= ctx->nt_load_log, [&](auto NT) {
-    auto go = [&](auto KF, auto KS) {
-      hipLaunchKernelGGL((sc::wfold_pass_kernel<F, KF, KS, NT>), dim3(grid), dim3(sc::kWfThreads), 0, ctx->stream, f, A, B, A2, B2, fw, r_top, n_tiles, wo);
-    };
-    if (kf == 4) go(IntC<4>{}, IntC<5>{});
-    else with_const<3, 4, 5>(ks, [&](auto KS) { go(IntC<5>{}, KS); });
+    with_bool(sl.period != 0, [&](auto SLOTS) {
+      auto go = [&](auto KF, auto KS) {
+        hipLaunchKernelGGL((sc::wfold_pass_kernel<F, KF, KS, NT, SLOTS>), dim3(grid), dim3(sc::kWfThreads), 0, ctx->stream, f, A, B, A2, B2, fw, r_top,
+                           n_tiles, wo, sl);
+      };
+      if (kf == 4) go(IntC<4>{}, IntC<5>{});
+      else with_const<3, 4, 5>(ks, [&](auto KS) { go(IntC<5>{}, KS); });
+    });
   }));
   return commit_wide_out(ctx, wo, pow3(ks));
 }

@@ -480,11 +480,30 @@ wgrid_pass_kernel(F f, const u64* __restrict__ A, const u64* __restrict__ B, u64
 // 101 + 26 + a trip to the host at n = 25; (5, ks) on 2^23..2^25-entry tables: what wgrid_pass_kernel - made for tables that sit
 // in the caches - streams at 4.5 TB/s.  Whole tiles only (tables of >= 2^12 entries); cells leave exactly as
 // wgrid_pass_kernel's (wgrid_finish).  r_top: the fifth challenge (KF = 5), in the tables' representation.
+//
+// SLOTS (options "wfold_slot_period" / "wfold_slot_width" / "wfold_slot_stagger"): the writes of the folded
+// tables aligned in TIME across the chip by the wall clock, which every XCD reads alike (tools/xcd_clock_probe.hip) - no
+// communication, and no wave ever waits: a slot is an opportunity taken at a sub-step boundary the wave reaches anyway.
+//  width = 0 (variant A): only the write-back requests of wave 0 of blocks 0..7 move - from the end of every tile to the first
+//    sub-step boundary behind every multiple of `period`.
+//  width > 0 (variant B): the stores move too.  At the end of a tile the wave takes its outputs out of the exchange area into
+//    registers (16 / 8 VGPRs for KF = 4 / 5) and stores them at the first of the next tile's four sub-step boundaries that lies in
+//    a slot [k period, k period + width); at the end of that tile at the latest (the deadline), and behind the loop what it still
+//    holds.  The write-back requests are issued at the end of every slot.
+//  stagger = 1 (the control): block b's slots are shifted by (b mod 8) period / 8 - same code, same number of requests, but
+//    the XCDs no longer coincide.
+// SLOTS = false is the kernel without any of it.
+#define SC_WFOLD_SLOTS 1
+struct WfSlots {
+  unsigned period = 0;    // ticks of wall_clock64 (100 MHz); > 0 in a SLOTS launch
+  unsigned width = 0;     // ticks; >= period: always open
+  unsigned stagger = 0;
+};
 constexpr int kWfThreads = 512;
-template <class F, int KF, int KS, bool NT>
+template <class F, int KF, int KS, bool NT, bool SLOTS = false>
 __global__ void __launch_bounds__(kWfThreads)
 wfold_pass_kernel(F f, const u64* __restrict__ A, const u64* __restrict__ B, u64* __restrict__ A2, u64* __restrict__ B2, FoldW fw,
-                  u64 r_top, size_t n_tiles, WgOut out) {
+                  u64 r_top, size_t n_tiles, WgOut out, WfSlots sl) {
   static_assert(KF == 4 || KF == 5, "four or five pending challenges");
   static_assert(KS >= 1 && KS <= 5, "one to five rounds");
   constexpr int OUT = 4, NPS = 8, NP = 32;          // a tile: 4 sub-steps of 8 KiB (1024 entries) per table
@@ -499,8 +518,28 @@ wfold_pass_kernel(F f, const u64* __restrict__ A, const u64* __restrict__ B, u64
   __shared__ u64 lds_all[kWaves * kRegionWords];
   __shared__ int cell_of[kWgEntries], suffix_of[kWgEntries];
   __shared__ unsigned lds_next;
+  // SLOTS: what a wave needs at a boundary sits in LDS, not in scalar registers that would be live across the whole tile loop (the
+  // generic field's constants and weights leave none to spare): {period, width, phase of this block} and, per wave, {the tile
+  // whose outputs it holds or kNoTile, the period of its last write-back request}
+  constexpr unsigned kNoTile = ~0u;
+  __shared__ unsigned lds_slots[4];
+  __shared__ unsigned lds_wave[kWaves][2];
   typedef __attribute__((address_space(3))) u64 lds_u64;
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+  auto lds_word = [](const unsigned* p) -> unsigned {   // one word of them, the same for the whole wave
+    return (unsigned)__builtin_amdgcn_readfirstlane((int)*(const volatile unsigned*)p);
+  };
+  if constexpr (SLOTS) {
+    if (tid == 0) {
+      lds_slots[0] = sl.period;
+      lds_slots[1] = sl.width;
+      lds_slots[2] = sl.stagger ? (blockIdx.x & 7u) * (sl.period >> 3) : 0u;
+    }
+    if (lane == 0) {
+      lds_wave[wave][0] = kNoTile;
+      lds_wave[wave][1] = ((unsigned)wall_clock64() + (sl.stagger ? (blockIdx.x & 7u) * (sl.period >> 3) : 0u) - sl.width) / sl.period;
+    }
+  }
   if (tid < kWgEntries) {   // (wgrid_body's tables)
     int c = 0, u = 0, p3 = 1;
     for (int m = 0; m < KS; ++m) {
@@ -610,6 +649,17 @@ wfold_pass_kernel(F f, const u64* __restrict__ A, const u64* __restrict__ B, u64
     }
     wave_lds_sync();
   };
+  // SLOTS: the outputs of tile `t` that the wave holds back
+  ull2 held[2 * NPO];
+  auto store_held = [&](unsigned t) {
+#pragma unroll
+    for (int k = 0; k < NPO; ++k) {
+      const size_t q = (size_t)t * kWave * NPO + (size_t)k * kWave + lane;
+      st16<false>(A2p + q, held[2 * k]);
+      st16<false>(B2p + q, held[2 * k + 1]);
+    }
+    lds_wave[wave][0] = kNoTile;
+  };
   ull2 pa[NPS], pb[NPS];
   size_t tile = next_tile();
   if (tile < n_tiles) {
@@ -621,6 +671,17 @@ wfold_pass_kernel(F f, const u64* __restrict__ A, const u64* __restrict__ B, u64
 #pragma unroll
     for (int i = 0; i < OUT; ++i) {
       const int o = (i + rot) & 3, no = (i + 1 + rot) & 3;
+      if constexpr (SLOTS) {   // a sub-step boundary: one look at the clock (its low word: the slots of all blocks jump together when it wraps)
+        const unsigned period = lds_word(&lds_slots[0]), width = lds_word(&lds_slots[1]);
+        const unsigned t = (unsigned)wall_clock64() + lds_word(&lds_slots[2]);
+        const unsigned ht = lds_word(&lds_wave[wave][0]);
+        if (ht != kNoTile && t % period < width) store_held(ht);
+        if (wave == 0 && blockIdx.x < 8) {   // the write-back request: behind every multiple of the period (width 0), at the end of every slot
+          const unsigned k = (t - width) / period;
+          if (k != lds_word(&lds_wave[0][1])) asm volatile("buffer_wbl2 sc1" ::: "memory");
+          lds_wave[0][1] = k;
+        }
+      }
       stash(pa);
       wave_lds_sync();
       if (i + 1 < OUT) load_sub(Ap, tile, no, pa);
@@ -639,20 +700,38 @@ wfold_pass_kernel(F f, const u64* __restrict__ A, const u64* __restrict__ B, u64
 #pragma unroll 1
       for (int g = 0; g < OUTS / kWgEntries; ++g) grid_group(o * (OUTS / kWgEntries) + g);
     }
-    // the folded tables: the exchange area holds the tile's outputs in index order - stored straight out of it
+    // the folded tables: the exchange area holds the tile's outputs in index order - stored straight out of it, or (SLOTS,
+    // width > 0) taken into registers for the next tile's boundaries, behind the previous tile's where no slot came for them
     {
       const ull2* xo = reinterpret_cast<const ull2*>(xchg);
       const size_t o0 = tile * kWave * NPO;
+      if (SLOTS && lds_word(&lds_slots[1]) != 0) {
+        const unsigned ht = lds_word(&lds_wave[wave][0]);
+        if (ht != kNoTile) store_held(ht);   // the deadline
 #pragma unroll
-      for (int k = 0; k < NPO; ++k) {
-        const size_t q = o0 + (size_t)k * kWave + lane;
-        st16<false>(A2p + q, xo[kWave * k + lane]);
-        st16<false>(B2p + q, xo[kWave * OUT / 2 + kWave * k + lane]);
+        for (int k = 0; k < NPO; ++k) {
+          held[2 * k] = xo[kWave * k + lane];
+          held[2 * k + 1] = xo[kWave * OUT / 2 + kWave * k + lane];
+        }
+        lds_wave[wave][0] = (unsigned)tile;
+      } else {
+#pragma unroll
+        for (int k = 0; k < NPO; ++k) {
+          const size_t q = o0 + (size_t)k * kWave + lane;
+          st16<false>(A2p + q, xo[kWave * k + lane]);
+          st16<false>(B2p + q, xo[kWave * OUT / 2 + kWave * k + lane]);
+        }
       }
     }
     wave_lds_sync();   // (the stores' LDS reads before the next tile's outputs)
-    if (wave == 0 && blockIdx.x < 8) asm volatile("buffer_wbl2 sc1" ::: "memory");   // (the bulk write-back hint of pass_kernel's pipelined forms)
+    if constexpr (!SLOTS) {
+      if (wave == 0 && blockIdx.x < 8) asm volatile("buffer_wbl2 sc1" ::: "memory");   // (the bulk write-back hint of pass_kernel's pipelined forms)
+    }
     tile = next;
+  }
+  if constexpr (SLOTS) {   // the loop's end: whatever the wave still holds
+    const unsigned ht = lds_word(&lds_wave[wave][0]);
+    if (ht != kNoTile) store_held(ht);
   }
   // the block's cells: accumulators -> residues, the waves added through LDS (the wave regions are free now)
   __syncthreads();

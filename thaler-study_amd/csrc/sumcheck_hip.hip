@@ -156,6 +156,11 @@ struct sc_ctx {
   int wfold_min_log = 21;            // ... and of >= 2^this entries (below, a five-round grid pass folds the four challenges)
   int wfold5_min_log = 24;           // a grid pass with FIVE challenges to fold over tables of >= 2^this entries runs in the same kernel's (5, ks) form
   int wfold_always = 0;              // 0: where the proof then needs fewer launches (the planner counts both ways); 1: wherever it can run
+  // wfold_pass_kernel's clock-aligned write slots (kernels/grid_pass.hpp, WfSlots), in ticks of the 100 MHz wall clock.
+  // period 0: the kernel without them, -1: where they were measured to pay (launch_wfold_pass); width 0: only the write-back requests
+  // are aligned, > 0: the stores leave inside the slots too; stagger 1: the slots of the eight XCDs shifted against each other (the
+  // control of the measurement)
+  int wfold_slot_period = -1, wfold_slot_width = 0, wfold_slot_stagger = 0;
   int matmul_path = 0;               // sc_matmul: 0 auto (the int8 matrix cores from 32 x 32), 1 matrix cores (from 16 x 16), 2 VALU
   int gp_host_log = 10;              // sc_gp_prove: layers of <= 2^this entries, and the last 2^this entries of every larger one, are proven on the host (measured: DESIGN.md section 9 item 16)
   int gp_tree_lv = sc::kGpTreeLv;    // sc_gp_create: tree layers per launch above the tail (1..3)

@@ -60,7 +60,7 @@ def describe(name):
         return "gram_finish", 0, int(m.group(1))
     if "wgrid_pass_kernel<" in name:
         return "grid_pass", -1, -1       # kf, ks from bench.py's schedule
-    m = re.search(r"wfold_pass_kernel<sc::\w+, (\d), (\d), \w+>", name)
+    m = re.search(r"wfold_pass_kernel<sc::\w+, (\d), (\d), \w+(?:, \w+)?>", name)   # (NT; SLOTS since the write slots)
     if m:
         return "wfold_pass", int(m.group(1)), int(m.group(2))
     m = re.search(r"pass_kernel<sc::\w+, (\d), (\d)(?:, \d+)?>", name)
