@@ -293,6 +293,13 @@ int sc_ctx_kernel_time(sc_ctx* ctx, double out[2], int reset);
 #define SC_KIND_LOOKUP_COUNT 32  /* sc_lookup_count: kf = 0 lookup_count_kernel (ks = 1: a private histogram per block in LDS, m <= 13; 0: adds to
                                  * global memory; log_in = n; reads 12 * 2^n bytes of w and idx and gathers 8 * 2^n of t, writes 4 * 2^m of
                                  * counters), kf = 1 lookup_mont_kernel (log_in = m; reads 4 * 2^m, writes 8 * 2^m) */
+#define SC_KIND_SPARK_INDEX 33   /* sc_spark_create, one dimension: kf = 0 spark_index_kernel (ks = 1: a private histogram per block in LDS, at most
+                                 * 2^13 counters; 0: adds to global memory; log_in = l; reads 4 * 2^l bytes of indices, writes 8 * 2^l of field
+                                 * words and 4 * 2^m of counters), kf = 1 lookup_mont_kernel (log_in = m; reads 4 * 2^m, writes 8 * 2^m) */
+#define SC_KIND_SPARK_GATHER 34  /* spark_gather_kernel: both dimensions of sc_spark_gather in one launch; log_in = l; reads 8 * 2^l bytes of
+                                 * indices and gathers 16 * 2^l, writes 16 * 2^l */
+#define SC_KIND_SPARK_TUPLE 35   /* spark_tuple_kernel: one table of sc_spark_denominators; kf = 1 where the key is the index itself; log_in = n
+                                 * for 2^n entries; reads 8 * 2^n bytes (12 * 2^n with a key stream), writes 8 * 2^n */
 typedef struct sc_launch_record {
   int32_t kind;           /* SC_KIND_* */
   int32_t kf, ks;         /* variables folded / rounds served (meaning per kind above) */
@@ -801,6 +808,47 @@ int sc_frac_prove(sc_ctx* ctx, const sc_frac* g, sc_draw_frac_fn draw, void* use
  * of the counts); every other i adds one to *mismatches and is not counted (SC_KIND_LOOKUP_COUNT).  SC_ERR_UNSUPPORTED:
  * p <= 2^max(n, m) (a count must be a field word). */
 int sc_lookup_count(sc_ctx* ctx, const sc_table* w, const sc_table* t, const uint32_t* idx_host, sc_table** mult, uint64_t* mismatches);
+
+/* ---- SPARK over LogUp: a committed sparse matrix and the proof of v = sum_k val_k U[row_k] W[col_k] (DESIGN.md section 9 item 18;
+ * kernels/spark.hpp states the protocol) ---------------------------------------------------------------------------------------
+ * M in F^(2^a x 2^b) is a list of nnz >= 1 triples, padded with (0, 0, 0) to N = 2^l entries, l = max(1, ceil(log2 nnz)); equal
+ * (row, col) pairs add.  The object holds five tables: row and col (the indices as field words) and val, of l variables, and the
+ * counts cr[i] = #{k < N : row_k = i} (a variables) and cc[j] = #{k < N : col_k = j} (b variables); the padding counts in cr[0]
+ * and cc[0].  Limits: 1 <= l, a, b <= 28; p > 3 and p > 2^max(l, a, b) (SC_ERR_UNSUPPORTED: indices and counts must be field words);
+ * one device and one rank (SC_ERR_UNSUPPORTED on a sharded context or a multi-device handle, before anything else is looked at).
+ * SC_ERR_ARG: a NULL argument, an empty list, a triple outside the matrix or with a value that is not a word below p, tables of
+ * the wrong length, a challenge that is not a word below p.  No security level, no zero knowledge and no Fiat-Shamir are claimed. */
+typedef struct sc_spark sc_spark;
+#define SC_SPARK_ROW 0
+#define SC_SPARK_COL 1
+#define SC_SPARK_VAL 2
+#define SC_SPARK_CR 3
+#define SC_SPARK_CC 4
+/* Validates every triple on the host, pads, uploads, and builds row, col, cr and cc on the device (SC_KIND_SPARK_INDEX launches);
+ * the host arrays may be freed on return.  A failure gives every block back. */
+int sc_spark_create(sc_ctx* ctx, size_t log_rows, size_t log_cols, const uint32_t* row, const uint32_t* col, const uint64_t* val, size_t nnz,
+                    sc_spark** out);
+int sc_spark_destroy(sc_ctx* ctx, sc_spark* sp);
+/* a copy of row, col, val, cr or cc (which = SC_SPARK_*) as a new table */
+int sc_spark_table(sc_ctx* ctx, const sc_spark* sp, int which, sc_table** out);
+/* er[k] = u[row_k] and ec[k] = w[col_k], k < N: two new tables from one launch (SC_KIND_SPARK_GATHER); u has 2^a entries, w 2^b */
+int sc_spark_gather(sc_ctx* ctx, const sc_spark* sp, const sc_table* u, const sc_table* w, sc_table** er, sc_table** ec);
+/* The denominators of one indexed lookup, dim = 0 (row) or 1 (col): den_w[k] = alpha - idx_k - beta e[k], k < N, and
+ * den_t[i] = alpha - i - beta t[i] over t's 2^a (2^b) entries: two new tables, one launch each (SC_KIND_SPARK_TUPLE) */
+int sc_spark_denominators(sc_ctx* ctx, const sc_spark* sp, int dim, const sc_table* t, const sc_table* e, uint64_t alpha, uint64_t beta,
+                          sc_table** den_w, sc_table** den_t);
+/* The cubic sumcheck over sum_x a(x) b(x) c(x), three tables of 2^n entries, 1 <= n <= 28, which are never written: n rounds of four
+ * values H(0..3), variable 0 first.  *c1 = H_0(0) + H_0(1); evals (4 n words, may be NULL); challenges (n words, may be NULL);
+ * finals = the three tables' extensions at the challenges.  draw == NULL: the synthetic challenger of sc_prove over seed_r.  One
+ * launch per round (gp_pass_kernel, SC_KIND_PRODUCT_PASS) down to the hand-over to the host (option "gp_host_log"); the transcript
+ * is the same at every value of the option. */
+int sc_product3_prove(sc_ctx* ctx, const sc_table* a, const sc_table* b, const sc_table* c, sc_draw4_fn draw, void* user, uint64_t seed_r,
+                      uint64_t* c1, uint64_t* evals, uint64_t* challenges, uint64_t finals[3]);
+/* eq(r, .) over n variables, 1 <= n <= 28, as a new table of 2^n words: out[i] = prod_j (bit_j(i) ? r[j] : 1 - r[j]) */
+int sc_table_eq(sc_ctx* ctx, const uint64_t* r, size_t n, sc_table** out);
+/* The row weights of the combined matrix of an R1CS instance (row k 2^s + i = row i of matrix k): a new table of 2^(s+2) words,
+ * (rho_A eq(rx, .), rho_B eq(rx, .), rho_C eq(rx, .), 0) - the vector sc_r1cs_bind_rows multiplies by, with a zero last quarter */
+int sc_r1cs_row_weights(sc_ctx* ctx, const sc_r1cs* r, const uint64_t* rx, const uint64_t rho[3], sc_table** out);
 
 /* ---- gkr_protocol::circuit::Circuit on the device, and the whole GKR prover over it ----------------------------------
  * A circuit lives on ONE context of one device and one rank: sharded contexts (world > 1) and multi-device handles get

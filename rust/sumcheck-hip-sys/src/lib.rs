@@ -123,6 +123,12 @@ pub struct sc_frac {
     _private: [u8; 0],
 }
 
+/// a sparse matrix with its index tables and counts on the device (`sc_spark_create`)
+#[repr(C)]
+pub struct sc_spark {
+    _private: [u8; 0],
+}
+
 pub type sc_allreduce_fn = Option<unsafe extern "C" fn(user: *mut c_void, buf: *mut u64, count: usize) -> c_int>;
 pub type sc_allgather_fn =
     Option<unsafe extern "C" fn(user: *mut c_void, send: *const u64, recv: *mut u64, count: usize) -> c_int>;
@@ -691,4 +697,60 @@ extern "C" {
         mult: *mut *mut sc_table,
         mismatches: *mut u64,
     ) -> c_int;
+    /// a sparse matrix of 2^log_rows x 2^log_cols from nnz >= 1 triples, padded to 2^l entries: its index tables and counts are
+    /// built on the device (SC_KIND_SPARK_INDEX, 33); the host arrays may be freed on return
+    pub fn sc_spark_create(
+        ctx: *mut sc_ctx,
+        log_rows: usize,
+        log_cols: usize,
+        row: *const u32,
+        col: *const u32,
+        val: *const u64,
+        nnz: usize,
+        out: *mut *mut sc_spark,
+    ) -> c_int;
+    pub fn sc_spark_destroy(ctx: *mut sc_ctx, sp: *mut sc_spark) -> c_int;
+    /// a copy of row (`which` = 0), col (1), val (2), cr (3) or cc (4) as a new table
+    pub fn sc_spark_table(ctx: *mut sc_ctx, sp: *const sc_spark, which: c_int, out: *mut *mut sc_table) -> c_int;
+    /// er[k] = u[row_k], ec[k] = w[col_k]: two new tables from one launch (SC_KIND_SPARK_GATHER, 34)
+    pub fn sc_spark_gather(
+        ctx: *mut sc_ctx,
+        sp: *const sc_spark,
+        u: *const sc_table,
+        w: *const sc_table,
+        er: *mut *mut sc_table,
+        ec: *mut *mut sc_table,
+    ) -> c_int;
+    /// den_w[k] = alpha - idx_k - beta e[k] and den_t[i] = alpha - i - beta t[i] of dimension `dim` (0: row, 1: col): two new
+    /// tables, one launch each (SC_KIND_SPARK_TUPLE, 35)
+    pub fn sc_spark_denominators(
+        ctx: *mut sc_ctx,
+        sp: *const sc_spark,
+        dim: c_int,
+        t: *const sc_table,
+        e: *const sc_table,
+        alpha: u64,
+        beta: u64,
+        den_w: *mut *mut sc_table,
+        den_t: *mut *mut sc_table,
+    ) -> c_int;
+    /// the cubic sumcheck over a(x) b(x) c(x): one launch per device round, SC_KIND_PRODUCT_PASS (29); evals 4 n words or null,
+    /// challenges n words or null, finals 3
+    pub fn sc_product3_prove(
+        ctx: *mut sc_ctx,
+        a: *const sc_table,
+        b: *const sc_table,
+        c: *const sc_table,
+        draw: sc_draw4_fn,
+        user: *mut c_void,
+        seed_r: u64,
+        c1: *mut u64,
+        evals: *mut u64,
+        challenges: *mut u64,
+        finals: *mut u64,
+    ) -> c_int;
+    /// eq(r, .) over n variables as a new table of 2^n words
+    pub fn sc_table_eq(ctx: *mut sc_ctx, r: *const u64, n: usize, out: *mut *mut sc_table) -> c_int;
+    /// (rho_A eq(rx, .), rho_B eq(rx, .), rho_C eq(rx, .), 0): a new table of 2^(s+2) words
+    pub fn sc_r1cs_row_weights(ctx: *mut sc_ctx, r: *const sc_r1cs, rx: *const u64, rho: *const u64, out: *mut *mut sc_table) -> c_int;
 }

@@ -42,6 +42,57 @@ int gp_build_tree(sc_ctx* ctx, sc_gp* g, int tree_lv) {
   });
 }
 
+// The device rounds of a cubic sumcheck over three tables of 2^k entries, k > te >= 1 (gp_pass_kernel, one launch per round,
+// SC_KIND_PRODUCT_PASS): rounds 0 .. k - te - 1 are completed - next(round, H(0..3), &c) draws, rs[round] receives c - and the
+// launch of round k - te leaves its four values in e and tables of 2^te entries at in[.], which the host takes.  in[.]: the tables
+// of round 0, never written; cur[.] owns every folded table (a block cur[q] holds on entry, the eq table of a layer, is given back
+// as that one was).  next() returning false ends the call with *stopped.
+template <class Next>
+int gp_device_rounds(sc_ctx* ctx, int k, int te, int resident, const u64* (&in)[3], PoolBuf (&cur)[3], u64* rs, u64 (&e)[4], const int* stopped,
+                     Next&& next) {
+  PoolBuf nxt[3];
+  u64 r_prev = 0;
+  for (int j = 0; j <= k - te; ++j) {
+    const bool fold = j > 0;
+    const int log_in = fold ? k - j + 1 : k;
+    const size_t n_units = (size_t)1 << (k - j - 1);
+    sc::GpTables tb;
+    for (int q = 0; q < 3; ++q) {
+      tb.in[q] = in[q];
+      tb.out[q] = nullptr;
+      if (fold) {
+        SC_TRY(nxt[q].alloc(ctx, (size_t)2 * n_units));
+        tb.out[q] = nxt[q].get();
+      }
+    }
+    const int grid = (int)std::max<size_t>(1, std::min<size_t>((n_units + sc::kBlock - 1) / sc::kBlock, (size_t)resident));
+    bool mb = false;
+    const sc::PassOut po = next_pass_out(ctx, false, 0, &mb);
+    SC_TRY(timer_begin(ctx, SC_KIND_PRODUCT_PASS, fold ? 1 : 0, 1, log_in, (u64)24 << log_in, fold ? (u64)24 << (log_in - 1) : 0));
+    SC_DISPATCH_FIELD(ctx, F, f, with_bool(fold, [&](auto FOLD) {
+      hipLaunchKernelGGL((sc::gp_pass_kernel<F, FOLD>), dim3(grid), dim3(sc::kBlock), 0, ctx->stream, f, tb, r_prev, n_units, po);
+    }));
+    SC_TRY(commit_pass_out(ctx, po, grid));
+    SC_TRY(timer_end(ctx));
+    if (fold)
+      for (int q = 0; q < 3; ++q) {
+        cur[q] = std::move(nxt[q]);   // (the tables of round j - 1 go back: the launch that reads them is queued)
+        in[q] = cur[q].get();
+      }
+    SC_TRY(collect_sums(ctx, 4, false, mb, e));
+    if (j == k - te) break;   // the host draws this round's challenge
+    if (!next((size_t)j, e, &r_prev)) return *stopped;
+    rs[(size_t)j] = r_prev;
+  }
+  return SC_OK;
+}
+
+// how many blocks of gp_pass_kernel the device holds at once
+int gp_pass_resident(sc_ctx* ctx) {
+  const void* fn = ctx->gold ? kernel_ptr(&sc::gp_pass_kernel<sc::GoldilocksMont, true>) : kernel_ptr(&sc::gp_pass_kernel<sc::MontGeneric, true>);
+  return std::min(resident_grid(ctx, fn, sc::kBlock, ctx->max_blocks), ctx->max_blocks);
+}
+
 }  // namespace
 
 extern "C" int sc_gp_create(sc_ctx* ctx, const sc_table* t, sc_gp** out) {
@@ -115,8 +166,7 @@ extern "C" int sc_gp_prove(sc_ctx* ctx, const sc_gp* g, sc_draw_gp_fn draw, void
     if (top == n) SC_HIP(ctx, hipMemcpyAsync(bottom.data() + tree_words, g->t->d, sizeof(u64) << n, hipMemcpyDeviceToHost, ctx->stream));
     SC_HIP(ctx, sync_stream(ctx));
   }
-  const void* fn = ctx->gold ? kernel_ptr(&sc::gp_pass_kernel<sc::GoldilocksMont, true>) : kernel_ptr(&sc::gp_pass_kernel<sc::MontGeneric, true>);
-  const int resident = std::min(resident_grid(ctx, fn, sc::kBlock, ctx->max_blocks), ctx->max_blocks);
+  const int resident = gp_pass_resident(ctx);
 
   // the challenger, in protocol order: one draw per round and one per rho
   u64 n_draws = 0;
@@ -152,43 +202,12 @@ extern "C" int sc_gp_prove(sc_ctx* ctx, const sc_gp* g, sc_draw_gp_fn draw, void
     } else {
       // the device runs the rounds 0 .. k - te; the launch of round k - te leaves tables of 2^te entries, which the host takes
       const int te = std::max(T, 1);
-      PoolBuf cur[3], nxt[3];
+      PoolBuf cur[3];
       SC_TRY(build_eq_table(ctx, z.data(), k, &cur[0]));
       const u64* lk = gp_layer_ptr(g, k + 1);
       const u64* in[3] = {cur[0].get(), lk, lk + len};
-      u64 r_prev = 0, e[4];
-      for (int j = 0; j <= k - te; ++j) {
-        const bool fold = j > 0;
-        const int log_in = fold ? k - j + 1 : k;
-        const size_t n_units = (size_t)1 << (k - j - 1);
-        sc::GpTables tb;
-        for (int q = 0; q < 3; ++q) {
-          tb.in[q] = in[q];
-          tb.out[q] = nullptr;
-          if (fold) {
-            SC_TRY(nxt[q].alloc(ctx, (size_t)2 * n_units));
-            tb.out[q] = nxt[q].get();
-          }
-        }
-        const int grid = (int)std::max<size_t>(1, std::min<size_t>((n_units + sc::kBlock - 1) / sc::kBlock, (size_t)resident));
-        bool mb = false;
-        const sc::PassOut po = next_pass_out(ctx, false, 0, &mb);
-        SC_TRY(timer_begin(ctx, SC_KIND_PRODUCT_PASS, fold ? 1 : 0, 1, log_in, (u64)24 << log_in, fold ? (u64)24 << (log_in - 1) : 0));
-        SC_DISPATCH_FIELD(ctx, F, f, with_bool(fold, [&](auto FOLD) {
-          hipLaunchKernelGGL((sc::gp_pass_kernel<F, FOLD>), dim3(grid), dim3(sc::kBlock), 0, ctx->stream, f, tb, r_prev, n_units, po);
-        }));
-        SC_TRY(commit_pass_out(ctx, po, grid));
-        SC_TRY(timer_end(ctx));
-        if (fold)
-          for (int q = 0; q < 3; ++q) {
-            cur[q] = std::move(nxt[q]);   // (the tables of round j - 1 go back: the launch that reads them is queued)
-            in[q] = cur[q].get();
-          }
-        SC_TRY(collect_sums(ctx, 4, false, mb, e));
-        if (j == k - te) break;   // the host draws this round's challenge
-        if (!next((size_t)j, e, &r_prev)) return rc;
-        rs[(size_t)j] = r_prev;
-      }
+      u64 e[4];
+      SC_TRY(gp_device_rounds(ctx, k, te, resident, in, cur, rs.data(), e, &rc, next));
       const size_t left = (size_t)1 << te;
       he.resize(left);
       hl.resize(left);

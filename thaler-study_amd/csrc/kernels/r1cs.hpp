@@ -23,7 +23,7 @@
 //    5. P builds T[y] = sum_k rho_k sum_i eq(r_x, i) M_k[i][y]: the three transposed products with the one vector eq(r_x, .).
 //    6. Sumcheck 2 is the existing product prover sc_prove(T, z), claim rho_A v_A + rho_B v_B + rho_C v_C, m rounds, ending at r_y.
 //    7. V computes T~(r_y) = sum_k rho_k sum_{(i,j,v) in M_k} eq(r_x, i) v eq(r_y, j) from the instance on the host:
-//       O(nnz + 2^s + 2^m).  The verifier reads the instance; no SPARK is built.
+//       O(nnz + 2^s + 2^m).  This verifier reads the instance; kernels/spark.hpp states the exchange that hands T~(r_y) to one that holds its roots.
 //    8. V computes x~(r_y[:m-1]) from the public inputs.
 //    9. V obtains w~(r_y[:m-1]) from one opening of the commitment (the plain Verifier, or a folded opening through open_folded).
 //   10. V checks T~(r_y) z~(r_y) against the last claim of sumcheck 2.

@@ -12,13 +12,16 @@ csrc/kernels/r1cs.hpp states the protocol; DESIGN.md section 9 item 15 describes
   4. V draws rho_A, rho_B, rho_C                   10. V checks T~(r_y) z~(r_y) against the last claim
   5. P builds T[y] = sum_k rho_k sum_i eq(r_x, i) M_k[i][y]
 
-Field elements are Montgomery words, as everywhere in this package.  The verifier reads the instance: no SPARK is built.  Nothing
-beyond the book's statement of each part is claimed: no security level, no zero knowledge, no Fiat-Shamir.
+Field elements are Montgomery words, as everywhere in this package.  Verifier reads the instance in step 7; SublinearVerifier
+holds the five roots of DeviceR1CS.commit_instance in its place and takes T~(r_y) from the SPARK exchange of spark.py (DESIGN.md
+section 9 item 18).  Nothing beyond the book's statement of each part is claimed: no security level, no zero knowledge, no
+Fiat-Shamir.
 
   R1CS              the instance on the host: is_satisfied, mul, bind_eval
-  DeviceR1CS        sc_r1cs_*: mul (A z, B z, C z) and bind_rows (T) on the device
+  DeviceR1CS        sc_r1cs_*: mul (A z, B z, C z), bind_rows (T) and row_weights on the device; commit_instance
   zerocheck_prove   sc_zerocheck_prove: the cubic sumcheck over any three tables
-  Prover, Verifier, prove_and_verify; synthetic_instance"""
+  Prover, Verifier, prove_and_verify; synthetic_instance
+  SublinearVerifier, prove_and_verify_sublinear"""
 import ctypes
 import random
 
@@ -166,6 +169,29 @@ class DeviceR1CS:
         h = voidp()
         self.ctx.check(self.ctx.lib.sc_r1cs_bind_rows(self.ctx.h, self.h, _u64p(r), _u64p(w), ctypes.byref(h)))
         return DenseMultilinearExtension(self.ctx, h)
+
+    def row_weights(self, rx, rho):
+        """sc_r1cs_row_weights: (rho_A eq(r_x, .), rho_B eq(r_x, .), rho_C eq(r_x, .), 0) as a device table of 2^(s+2) words - the
+        row weights of the combined matrix of commit_instance"""
+        r, w = _words(rx), _words(rho)
+        if r.size != self.s or w.size != 3:
+            raise ValueError("r_x has s = %d words and rho three" % self.s)
+        h = voidp()
+        self.ctx.check(self.ctx.lib.sc_r1cs_row_weights(self.ctx.h, self.h, _u64p(r), _u64p(w), ctypes.byref(h)))
+        return DenseMultilinearExtension(self.ctx, h)
+
+    def commit_instance(self, **commit_kwargs):
+        """the spark.SparseCommitment of the one combined matrix of 2^(s+2) x 2^m: row k 2^s + i holds entry (i, j) of matrix k (the
+        layout of bind_rows' transposed image).  commit_kwargs go to spark.default_commit (log_blowup, code)"""
+        from . import spark
+        if self.r1cs is None:
+            raise ValueError("commit_instance needs the host instance")
+        rows, cols, vals = [], [], []
+        for k, M in enumerate(self.r1cs.matrices):
+            rows += [(k << self.s) + i for i, _, _ in M]
+            cols += [j for _, j, _ in M]
+            vals += [v for _, _, v in M]
+        return spark.SparseCommitment(self.ctx, self.s + 2, self.m, rows, cols, vals, commit=spark.default_commit(**commit_kwargs))
 
     def close(self):
         if self.h and self.ctx.h:
@@ -394,3 +420,80 @@ def prove_and_verify(prover, verifier, rng):
     prover.sumcheck2(lambda j, e: verifier.round2(j, e, rng))
     w_value = open_committed(prover.pcs, verifier.pcs, verifier.point(), rng)
     return verifier.finish(w_value)
+
+
+# ---- the verifier that does not read the instance (spark.py) --------------------------------
+
+class SublinearVerifier(Verifier):
+    """Verifier's steps without the matrices: it holds s, m, the public inputs, the witness root with the verifier of its opening,
+    and instance_verifiers, the verifiers of the openings of the five tables of DeviceR1CS.commit_instance (built over its five
+    roots, keyed by spark.TABLES).  Step 7, T~(r_y), comes from the SPARK exchange over the combined matrix with
+    U = row_weights(r_x, rho) and W = eq(r_y, .), whose extensions are u_eval and w_eval below."""
+
+    def __init__(self, field, s, m, io, root, pcs_verifier, instance_verifiers):
+        F = self.field = field
+        if not 1 <= s <= MAX_LOG or not 2 <= m <= MAX_LOG:
+            raise ValueError("s must be in 1..%d and m in 2..%d" % (MAX_LOG, MAX_LOG))
+        if bytes(root) != pcs_verifier.root or pcs_verifier.num_vars != m - 1:
+            raise ValueError("the opening's verifier must be over the committed root and m - 1 = %d variables" % (m - 1))
+        if F.p <= 3:
+            raise ValueError("p = %d: the cubic through 0, 1, 2, 3 needs 2 and 3 invertible" % F.p)
+        self.r1cs, self.io, self.root, self.pcs = None, [int(x) for x in io], bytes(root), pcs_verifier
+        self.instance_pcs = dict(instance_verifiers)
+        self.s, self.m = s, m
+        self.inv2, self.inv6 = F.inv(F.from_int(2)), F.inv(F.from_int(6))
+        self.tau = self.claim = self.rho = None
+        self.rx, self.ry = [], []
+        self.phase = 0
+
+    def _eq_at(self, a, b):
+        F = self.field
+        out = F.one
+        for x, y in zip(a, b):
+            xy = F.mul(int(x), int(y))
+            out = F.mul(out, F.add(F.sub(F.sub(F.one, int(x)), int(y)), F.add(xy, xy)))
+        return out
+
+    def u_eval(self, z):
+        """U~(z) for U = (rho_A eq(r_x, .), rho_B eq(r_x, .), rho_C eq(r_x, .), 0): eq(r_x, z[:s]) (rho_A (1 - z_s)(1 - z_(s+1)) +
+        rho_B z_s (1 - z_(s+1)) + rho_C (1 - z_s) z_(s+1))"""
+        F = self.field
+        lo, hi = int(z[self.s]), int(z[self.s + 1])
+        nlo, nhi = F.sub(F.one, lo), F.sub(F.one, hi)
+        sel = F.add(F.add(F.mul(self.rho[0], F.mul(nlo, nhi)), F.mul(self.rho[1], F.mul(lo, nhi))), F.mul(self.rho[2], F.mul(nlo, hi)))
+        return F.mul(self._eq_at(self.rx, z[:self.s]), sel)
+
+    def w_eval(self, z):
+        """W~(z) for W = eq(r_y, .)"""
+        return self._eq_at(self.ry, z)
+
+    def finish(self, w_value, t_value):
+        """steps 8 and 10 with w~(r_y[:m-1]) = w_value from the opening and T~(r_y) = t_value from the SPARK exchange"""
+        F = self.field
+        pt = self.point()
+        ey = eq_weights(F, pt)
+        x_value = ey[0]                                               # the constant 1 at index 0
+        for k, v in enumerate(self.io):
+            x_value = F.add(x_value, F.mul(v, ey[k + 1]))
+        top = self.ry[self.m - 1]
+        z_value = F.add(F.mul(F.sub(F.one, top), x_value), F.mul(top, int(w_value)))
+        value = F.mul(int(t_value), z_value)
+        if value != self.claim:
+            raise FinalMismatch(2, self.claim, value)
+        return True
+
+
+def prove_and_verify_sublinear(prover, instance, verifier, rng):
+    """the whole exchange between a Prover, the spark.SparseCommitment of its instance (DeviceR1CS.commit_instance) and a
+    SublinearVerifier; True, or the verifier's error (spark's errors among them)"""
+    from . import spark
+    tau = verifier.draw_tau(rng)
+    finals = prover.sumcheck1(tau, lambda j, e: verifier.round1(j, e, rng))
+    verifier.receive_finals(*finals)
+    rho = verifier.draw_rho(rng)
+    prover.bind(rho)
+    prover.sumcheck2(lambda j, e: verifier.round2(j, e, rng))
+    U, W = prover.dev.row_weights(prover.rx, rho), spark.table_eq(prover.ctx, prover.ry)
+    t_value = spark.prove_eval(instance, verifier.instance_pcs, U, W, verifier.u_eval, verifier.w_eval, rng)
+    w_value = open_committed(prover.pcs, verifier.pcs, verifier.point(), rng)
+    return verifier.finish(w_value, t_value)
