@@ -300,6 +300,11 @@ int sc_ctx_kernel_time(sc_ctx* ctx, double out[2], int reset);
                                  * indices and gathers 16 * 2^l, writes 16 * 2^l */
 #define SC_KIND_SPARK_TUPLE 35   /* spark_tuple_kernel: one table of sc_spark_denominators; kf = 1 where the key is the index itself; log_in = n
                                  * for 2^n entries; reads 8 * 2^n bytes (12 * 2^n with a key stream), writes 8 * 2^n */
+#define SC_KIND_EQ_SUM 36        /* eq_sum_kernel: the one launch of sc_table_eq_sum; ks = the number of points, log_in = n; reads the ks * (n + 1)
+                                 * words of points and coefficients, writes 8 * 2^n */
+#define SC_KIND_SUMPROD_PASS 37  /* sumprod_pass_kernel: one round of sc_sumprod_prove; kf = 1 if it folded the previous challenge, ks = T, the
+                                 * pairs of tables; log_in = log2 of the tables it read: 2 T * 8 * 2^log_in bytes read, and
+                                 * 2 T * 8 * 2^(log_in - 1) written with kf = 1 */
 typedef struct sc_launch_record {
   int32_t kind;           /* SC_KIND_* */
   int32_t kf, ks;         /* variables folded / rounds served (meaning per kind above) */
@@ -849,6 +854,24 @@ int sc_table_eq(sc_ctx* ctx, const uint64_t* r, size_t n, sc_table** out);
 /* The row weights of the combined matrix of an R1CS instance (row k 2^s + i = row i of matrix k): a new table of 2^(s+2) words,
  * (rho_A eq(rx, .), rho_B eq(rx, .), rho_C eq(rx, .), 0) - the vector sc_r1cs_bind_rows multiplies by, with a zero last quarter */
 int sc_r1cs_row_weights(sc_ctx* ctx, const sc_r1cs* r, const uint64_t* rx, const uint64_t rho[3], sc_table** out);
+
+/* ---- batched openings: many evaluation claims about committed tables of one shape, one joint opening (DESIGN.md section 9 item 19;
+ * kernels/multiopen.hpp states the protocol) ------------------------------------------------------------------------------------
+ * One device and one rank (SC_ERR_UNSUPPORTED on a sharded context or a multi-device handle, before anything else is looked at).
+ * SC_ERR_ARG, before any launch: a NULL argument, a count out of range, tables of different or non-power-of-two length, a point or
+ * coefficient word that is not below p. */
+/* out[x] = sum_{k < count} coeffs[k] eq(points[k], x) as a new table of 2^n words; points: `count` rows of n Montgomery words;
+ * 1 <= count <= 16, 1 <= n <= 28.  One launch (eq_sum_kernel, SC_KIND_EQ_SUM): one multiply-add per entry and point. */
+int sc_table_eq_sum(sc_ctx* ctx, const uint64_t* points, const uint64_t* coeffs, size_t count, size_t n, sc_table** out);
+/* The sumcheck over sum_x sum_{t < count} a[t](x) b[t](x) with ONE sequence of challenges shared by all pairs, 1 <= count <= 8, all
+ * tables 2^n entries, 1 <= n <= 28, never written (a table may appear in several pairs): n rounds of three values H(0..2), variable 0
+ * first.  This is not sc_prove_batch, whose instances are independent proofs.  *c1 = H_0(0) + H_0(1); evals (3 n words, may be
+ * NULL); challenges (n words, may be NULL); finals_a[t], finals_b[t] = the tables' extensions at the challenges (count words each).
+ * draw == NULL: the synthetic challenger of sc_product3_prove over seed_r; a challenge that is not below p ends the call with
+ * SC_ERR_ARG.  One launch per round (sumprod_pass_kernel, SC_KIND_SUMPROD_PASS) down to the hand-over to the host (option
+ * "gp_host_log"); the transcript is the same at every value of the option. */
+int sc_sumprod_prove(sc_ctx* ctx, size_t count, const sc_table* const* a, const sc_table* const* b, sc_draw_fn draw, void* user, uint64_t seed_r,
+                     uint64_t* c1, uint64_t* evals, uint64_t* challenges, uint64_t* finals_a, uint64_t* finals_b);
 
 /* ---- gkr_protocol::circuit::Circuit on the device, and the whole GKR prover over it ----------------------------------
  * A circuit lives on ONE context of one device and one rank: sharded contexts (world > 1) and multi-device handles get

@@ -753,4 +753,30 @@ extern "C" {
     pub fn sc_table_eq(ctx: *mut sc_ctx, r: *const u64, n: usize, out: *mut *mut sc_table) -> c_int;
     /// (rho_A eq(rx, .), rho_B eq(rx, .), rho_C eq(rx, .), 0): a new table of 2^(s+2) words
     pub fn sc_r1cs_row_weights(ctx: *mut sc_ctx, r: *const sc_r1cs, rx: *const u64, rho: *const u64, out: *mut *mut sc_table) -> c_int;
+    /// out[x] = sum_k coeffs[k] eq(points[k], x) as a new table of 2^n words: `count` <= 16 rows of n words, one launch
+    /// (SC_KIND_EQ_SUM, 36)
+    pub fn sc_table_eq_sum(
+        ctx: *mut sc_ctx,
+        points: *const u64,
+        coeffs: *const u64,
+        count: usize,
+        n: usize,
+        out: *mut *mut sc_table,
+    ) -> c_int;
+    /// the sumcheck over sum_t a[t](x) b[t](x), `count` <= 8 pairs under shared challenges: one launch per device round,
+    /// SC_KIND_SUMPROD_PASS (37); evals 3 n words or null, challenges n words or null, finals_a and finals_b `count` words each
+    pub fn sc_sumprod_prove(
+        ctx: *mut sc_ctx,
+        count: usize,
+        a: *const *const sc_table,
+        b: *const *const sc_table,
+        draw: sc_draw_fn,
+        user: *mut c_void,
+        seed_r: u64,
+        c1: *mut u64,
+        evals: *mut u64,
+        challenges: *mut u64,
+        finals_a: *mut u64,
+        finals_b: *mut u64,
+    ) -> c_int;
 }

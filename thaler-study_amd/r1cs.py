@@ -497,3 +497,26 @@ def prove_and_verify_sublinear(prover, instance, verifier, rng):
     t_value = spark.prove_eval(instance, verifier.instance_pcs, U, W, verifier.u_eval, verifier.w_eval, rng)
     w_value = open_committed(prover.pcs, verifier.pcs, verifier.point(), rng)
     return verifier.finish(w_value, t_value)
+
+
+def prove_and_verify_sublinear_batched(prover, instance, verifier, rng, groups=None):
+    """prove_and_verify_sublinear with batched openings (multiopen.py): P sends w~(r_y[:m-1]) next to
+    the nine values of the SPARK exchange, and the witness claim joins that exchange's list of claims (spark.prove_eval_batched) -
+    one joint opening per commitment shape, the witness's commitment among them where its shape agrees.  The accepted value is
+    M~(r_x, r_y) exactly as in prove_and_verify_sublinear.  A FoldVerifier is refused with a ValueError: a joint folded opening is
+    out of scope.  groups: a list that receives multiopen.prove_claims' groups.  True, or the verifier's error"""
+    from . import multiopen, spark
+    if isinstance(verifier.pcs, ligero_pcs.FoldVerifier) or any(isinstance(v, ligero_pcs.FoldVerifier) for v in verifier.instance_pcs.values()):
+        raise ValueError("batched openings take the plain ligero_pcs.Verifier: a joint folded opening is out of scope")
+    tau = verifier.draw_tau(rng)
+    finals = prover.sumcheck1(tau, lambda j, e: verifier.round1(j, e, rng))
+    verifier.receive_finals(*finals)
+    rho = verifier.draw_rho(rng)
+    prover.bind(rho)
+    prover.sumcheck2(lambda j, e: verifier.round2(j, e, rng))
+    U, W = prover.dev.row_weights(prover.rx, rho), spark.table_eq(prover.ctx, prover.ry)
+    point = verifier.point()
+    w_value = prover.pcs.poly.evaluate(point)
+    extra = ({"w": prover.pcs}, {"w": verifier.pcs}, [multiopen.Claim("w", point, w_value)])
+    t_value = spark.prove_eval_batched(instance, verifier.instance_pcs, U, W, verifier.u_eval, verifier.w_eval, rng, extra=extra, groups=groups)
+    return verifier.finish(w_value, t_value)

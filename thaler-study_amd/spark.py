@@ -418,3 +418,42 @@ def prove_eval(commitment, pcs_verifiers, U, W, u_eval, w_eval, rng, verifier_of
     finally:
         P.close()
     return V.v
+
+
+def prove_eval_batched(commitment, pcs_verifiers, U, W, u_eval, w_eval, rng, verifier_of=None, commit=None, extra=None, groups=None):
+    """prove_eval with batched openings (multiopen.py): after the fraction sums P sends the nine values,
+    V runs finish on them as claimed values, and multiopen.prove_claims proves the nine claims - one joint opening per commitment
+    shape with several claims (the tables of l variables; more where a or b equals l and the shapes agree), the single opening for
+    the rest.  The verifiers are plain ligero_pcs.Verifier objects: a FoldVerifier is refused with a ValueError.
+    extra = (provers, verifiers, claims): further commitments and multiopen.Claim's that join the list (r1cs: the witness).
+    groups: a list that receives prove_claims' groups.  Returns v, the value the verifier accepted, or raises the verifier's error"""
+    from . import multiopen
+    ctx, F = commitment.ctx, commitment.ctx.field
+    if any(isinstance(v, ligero_pcs.FoldVerifier) for v in pcs_verifiers.values()):
+        raise ValueError("batched openings take the plain ligero_pcs.Verifier: a joint folded opening is out of scope")
+    if verifier_of is None:
+        like = pcs_verifiers["val"]
+        verifier_of = lambda p: opening_verifier(F, p, like.queries, False)   # noqa: E731
+    V = Verifier(F, commitment.a, commitment.b, commitment.ell, pcs_verifiers, u_eval, w_eval)
+    P = Prover(commitment, U, W, commit)
+    try:
+        P.gather_commit()                                                     # 1
+        V.receive_commitments(verifier_of(P.pcs["er"]), verifier_of(P.pcs["ec"]))
+        V.receive_finals(*P.sumcheck(V.receive_claim, lambda j, e: V.round(j, e, rng)))   # 1 (v), 2
+        alpha, beta = V.draw_lookup(rng)                                      # 3
+        for dim in DIMS:
+            V.receive_roots(dim, *P.lookup_roots(dim, alpha, beta))
+            for side in range(2):
+                P.lookup_prove(dim, side, V.frac[dim][side].challenger(rng))
+        tables = dict(commitment.tables, er=P.er, ec=P.ec)
+        claims = [multiopen.Claim(table, point, tables[table].evaluate(point)) for table, _, point in V.openings()]   # 4: P's nine values
+        V.finish({(table, at): c.value for (table, at), c in zip(OPENINGS, claims)})
+        provers, verifiers = dict(P.pcs), dict(V.pcs)
+        if extra is not None:
+            provers.update(extra[0])
+            verifiers.update(extra[1])
+            claims += [multiopen.Claim(*c) for c in extra[2]]
+        multiopen.prove_claims(ctx, provers, verifiers, claims, rng, groups)
+    finally:
+        P.close()
+    return V.v
