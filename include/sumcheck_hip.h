@@ -305,6 +305,11 @@ int sc_ctx_kernel_time(sc_ctx* ctx, double out[2], int reset);
 #define SC_KIND_SUMPROD_PASS 37  /* sumprod_pass_kernel: one round of sc_sumprod_prove; kf = 1 if it folded the previous challenge, ks = T, the
                                  * pairs of tables; log_in = log2 of the tables it read: 2 T * 8 * 2^log_in bytes read, and
                                  * 2 T * 8 * 2^(log_in - 1) written with kf = 1 */
+#define SC_KIND_SUMPROD_EXT_PASS 38 /* ext_sumprod_pass_kernel: one round j >= 1 of sc_sumprod_prove_ext (round 0 is a kind 37 record); kf = 1
+                                 * for base tables in (round 1), kf = 2 for extension tables in; ks = T; log_in = log2 of the entries per
+                                 * table it read: 2 T * 8 * 2^log_in bytes read with kf = 1, 2 T * 16 * 2^log_in with kf = 2, and
+                                 * 2 T * 16 * 2^(log_in - 1) written.  ks = 0: ext_fold_kernel, one launch of sc_table_evaluate_ext - the
+                                 * same fold of ONE table, nothing summed: the same bytes with 2 T replaced by 1 */
 typedef struct sc_launch_record {
   int32_t kind;           /* SC_KIND_* */
   int32_t kf, ks;         /* variables folded / rounds served (meaning per kind above) */
@@ -872,6 +877,29 @@ int sc_table_eq_sum(sc_ctx* ctx, const uint64_t* points, const uint64_t* coeffs,
  * "gp_host_log"); the transcript is the same at every value of the option. */
 int sc_sumprod_prove(sc_ctx* ctx, size_t count, const sc_table* const* a, const sc_table* const* b, sc_draw_fn draw, void* user, uint64_t seed_r,
                      uint64_t* c1, uint64_t* evals, uint64_t* challenges, uint64_t* finals_a, uint64_t* finals_b);
+
+/* ---- challenges from a quadratic extension field (kernels/ext_sumprod.hpp states the conventions) ----
+ * K = F_p[X] / (X^2 - w): w is a quadratic non-residue of F_p, a Montgomery word, checked on the host (w^((p-1)/2) = p - 1, else
+ * SC_ERR_ARG before any launch).  An element of K is two consecutive Montgomery words (c0, c1), meaning c0 + c1 X.  The tables are
+ * base-field tables; the challenges, the round values and the finals are elements of K.  One device and one rank (SC_ERR_UNSUPPORTED
+ * on a sharded context or a multi-device handle, before anything else is looked at). */
+/* a round's challenge: msg = H(0).c0, H(0).c1, H(1).c0, H(1).c1, H(2).c0, H(2).c1; out receives (c0, c1), both below p */
+typedef void (*sc_draw_ext_fn)(void* user, size_t round, const uint64_t msg[6], uint64_t out[2]);
+/* sc_sumprod_prove with challenges from K: the same arguments, limits and refusals (1 <= count <= 8, all tables 2^n entries,
+ * 1 <= n <= 28, never written, a table may appear in several pairs), and SC_ERR_ARG for a bad w or a challenge component that is
+ * not below p.  n rounds of six words, variable 0 first; c1 = (H_0(0) + H_0(1), 0); evals (6 n words, may be NULL); challenges
+ * (2 n words, may be NULL); finals_a, finals_b = the tables' extensions at the challenges (2 count words each).  draw == NULL: the
+ * synthetic challenger r_j = (to_mont(splitmix64(seed_r + 2 j + 1) mod p), to_mont(splitmix64(seed_r + 2 j + 2) mod p)).  Round 0
+ * is the launch of sc_sumprod_prove (SC_KIND_SUMPROD_PASS, kf = 0), every later device round one ext_sumprod_pass_kernel launch
+ * (SC_KIND_SUMPROD_EXT_PASS), down to the hand-over to the host (option "gp_host_log", as in sc_sumprod_prove); the transcript is
+ * the same at every value of the option. */
+int sc_sumprod_prove_ext(sc_ctx* ctx, uint64_t w, size_t count, const sc_table* const* a, const sc_table* const* b, sc_draw_ext_fn draw, void* user,
+                         uint64_t seed_r, uint64_t c1[2], uint64_t* evals, uint64_t* challenges, uint64_t* finals_a, uint64_t* finals_b);
+/* The multilinear extension of a base-field table of 2^n entries at a point of K^n (2 n words, coordinate 0 first = variable 0),
+ * 1 <= n <= 28, by the prover's own folds (ext_fold_kernel, SC_KIND_SUMPROD_EXT_PASS records with ks = 0) down to the host
+ * hand-over of option "gp_host_log"; no table of 2^n weights is built.  SC_ERR_ARG: a bad w, a component that is not below p, a
+ * table that has not 2^n entries. */
+int sc_table_evaluate_ext(sc_ctx* ctx, uint64_t w, const sc_table* t, const uint64_t* point, size_t n, uint64_t out[2]);
 
 /* ---- gkr_protocol::circuit::Circuit on the device, and the whole GKR prover over it ----------------------------------
  * A circuit lives on ONE context of one device and one rank: sharded contexts (world > 1) and multi-device handles get

@@ -133,6 +133,8 @@ pub type sc_allreduce_fn = Option<unsafe extern "C" fn(user: *mut c_void, buf: *
 pub type sc_allgather_fn =
     Option<unsafe extern "C" fn(user: *mut c_void, send: *const u64, recv: *mut u64, count: usize) -> c_int>;
 pub type sc_draw_fn = Option<unsafe extern "C" fn(user: *mut c_void, round: usize, evals: *const u64) -> u64>;
+/// sc_sumprod_prove_ext: msg = H(0), H(1), H(2) as (c0, c1) pairs, out = the challenge (c0, c1)
+pub type sc_draw_ext_fn = Option<unsafe extern "C" fn(user: *mut c_void, round: usize, msg: *const u64, out: *mut u64)>;
 /// `sc_ligero_fold_prove`: the verifier's alpha of a round; `root` = the round's layer root (32 bytes), null at round 0.
 pub type sc_draw_fold_fn = Option<unsafe extern "C" fn(user: *mut c_void, round: usize, evals: *const u64, root: *const u8) -> u64>;
 /// `sc_zerocheck_prove`: the verifier's challenge of a round; `evals` = the round's H(0), H(1), H(2), H(3).
@@ -779,4 +781,23 @@ extern "C" {
         finals_a: *mut u64,
         finals_b: *mut u64,
     ) -> c_int;
+    /// sc_sumprod_prove with challenges from K = F_p[X]/(X^2 - w), w a non-residue (Montgomery word): six words per round,
+    /// SC_KIND_SUMPROD_EXT_PASS (38) from round 1 on; c1 two words, evals 6 n or null, challenges 2 n or null, finals 2 `count` each
+    pub fn sc_sumprod_prove_ext(
+        ctx: *mut sc_ctx,
+        w: u64,
+        count: usize,
+        a: *const *const sc_table,
+        b: *const *const sc_table,
+        draw: sc_draw_ext_fn,
+        user: *mut c_void,
+        seed_r: u64,
+        c1: *mut u64,
+        evals: *mut u64,
+        challenges: *mut u64,
+        finals_a: *mut u64,
+        finals_b: *mut u64,
+    ) -> c_int;
+    /// the multilinear extension of a base table of 2^n entries at a point of K^n (2 n words); out: two words
+    pub fn sc_table_evaluate_ext(ctx: *mut sc_ctx, w: u64, t: *const sc_table, point: *const u64, n: usize, out: *mut u64) -> c_int;
 }

@@ -45,7 +45,12 @@ Staged folded openings: a schedule `arities` = (a_
 folds a_s variables between two committed layers - a layer's leaf then holds 2^a_s words and there are S - 1 trees instead of
 log_cols - 1 (sc_ligero_fold_begin_staged, one rs_fold_kernel launch per stage).  Prover.fold_begin, FoldVerifier and
 fold_opening_bytes take `arities`; fold_shape gives the (log_cols, schedule) of the smallest opening; rs_fold_many is the fold
-alone.  arities=None is the binary opening above, unchanged.  The number of queries an arity needs is not analysed."""
+alone.  arities=None is the binary opening above, unchanged.  The number of queries an arity needs is not analysed.
+
+Openings at a point of the quadratic extension K = F_p[X] / (X^2 - w) (ext_field.QuadExt):
+Prover.combine_ext and ExtVerifier open a base-field commitment at z in K^n.  The row weights eq(z[c:]) split into their c0 and c1
+words, u_z becomes the pair (u_z0, u_z1) - one sc_ligero_combine_rows call of three weight vectors - and the value is an element of
+K.  Both codes; gamma stays in the base field."""
 import ctypes
 import hashlib
 
@@ -288,6 +293,18 @@ class Prover:
         u_gamma, u_z = self.combine_rows([list(gamma), eq_weights(self.field, list(point)[self.log_cols:])])
         return u_gamma, u_z
 
+    def combine_ext(self, point, gamma, w=None):
+        """(u_gamma, u_z0, u_z1) for a point of K^n, K = ext_field.QuadExt(field, w) (elements are (c0, c1) pairs; w=None: the
+        smallest non-residue): the row weights eq(point[c:]) in K split into their c0 and c1 words, and since the table is
+        base-field, u_z = u_z0 + X u_z1 with u_zk = sum_i weight_k[i] row_i.  ONE sc_ligero_combine_rows call of three vectors"""
+        from .ext_field import QuadExt
+        if len(point) != self.num_vars:
+            raise ValueError("the point has %d coordinates, the polynomial %d variables" % (len(point), self.num_vars))
+        K = QuadExt(self.field, w)
+        w0, w1 = K.split(K.eq_weights([tuple(z) for z in point][self.log_cols:]))
+        u_gamma, u_z0, u_z1 = self.combine_rows([list(gamma), w0, w1])
+        return u_gamma, u_z0, u_z1
+
     def open_columns(self, indices):
         """[(index, values, ColumnPath)] for every index, in one call; values are the column's 2^log_rows Montgomery words"""
         idx = _words(indices)
@@ -509,6 +526,63 @@ class Verifier:
         value = 0
         for a, b in zip(self.u_z, eq_weights(F, list(point)[:self.log_cols])):
             value = F.add(value, F.mul(a, b))
+        return value
+
+
+# ---- the verifier of an opening at a point of the quadratic extension ------------------------------------------------
+
+class ExtVerifier(Verifier):
+    """The plain Verifier's flow for a point z of K^n, K = ext_field.QuadExt(field, w) (w=None: the smallest non-residue), over
+    a base-field commitment: draw_gamma, receive(u_gamma, u_z0, u_z1), draw_columns, verify(point, openings) - which returns the
+    value in K, a (c0, c1) pair.  The committed table is base-field, so f(z) = (sum eq.c0 f, sum eq.c1 f): the row weights
+    eq(z[c:]) split into two base vectors, and each opened column is checked against both (one EvalMismatch check per
+    component).  gamma stays in the base field."""
+
+    def __init__(self, field, num_vars, log_cols, log_blowup, root, queries, code="rs", w=None):
+        from .ext_field import QuadExt
+        super().__init__(field, num_vars, log_cols, log_blowup, root, queries, code=code)
+        self.ext = QuadExt(field, w)
+        self.u_z1 = self.enc_z1 = None
+
+    def receive(self, u_gamma, u_z0, u_z1):
+        if len(u_z1) != 1 << self.log_cols:
+            raise Error("the combined rows must have 2^log_cols = %d words" % (1 << self.log_cols))
+        super().receive(u_gamma, u_z0)
+        self.u_z1 = [int(x) for x in u_z1]
+        if self.code == "expander":
+            self.enc_z1 = expander_code.encode(self.field, self.u_z1)
+
+    def verify(self, point, openings):
+        """check every opening; returns the value of the committed polynomial at `point`, an element of K"""
+        F, K = self.field, self.ext
+        if self.columns is None:
+            raise Error("verify before draw_columns")
+        if len(point) != self.num_vars:
+            raise Error("the point has %d coordinates, the polynomial %d variables" % (len(point), self.num_vars))
+        if len(openings) != len(self.columns):
+            raise MerkleMismatch("%d openings for %d drawn columns" % (len(openings), len(self.columns)))
+        point = [tuple(int(x) for x in z) for z in point]
+        eq_rows0, eq_rows1 = K.split(K.eq_weights(point[self.log_cols:]))
+        for want, (index, values, path) in zip(self.columns, openings):
+            if index != want or path.index != want:
+                raise MerkleMismatch("the opening is of column %d, the drawn column is %d" % (index, want))
+            if len(values) != 1 << self.log_rows or len(path.siblings) != self.log_len:
+                raise MerkleMismatch("an opening of the wrong shape")
+            if not ColumnPath(path.index, path.siblings, F).verify_column(self.root, values):
+                raise MerkleMismatch("the opening of column %d does not lead to the committed root" % index)
+            for u, enc, weights, proximity in ((self.u_gamma, self.enc_gamma, self.gamma, True), (self.u_z, self.enc_z, eq_rows0, False),
+                                               (self.u_z1, self.enc_z1, eq_rows1, False)):
+                combined = 0
+                for wt, v in zip(weights, values):
+                    combined = F.add(combined, F.mul(wt, int(v)))
+                encoded = enc[index] if enc is not None else self._encode_at(u, index)
+                if encoded != combined:
+                    if proximity:
+                        raise ProximityMismatch(index, encoded, combined)
+                    raise EvalMismatch(combined, encoded)
+        value = K.zero
+        for a0, a1, e in zip(self.u_z, self.u_z1, K.eq_weights(point[:self.log_cols])):
+            value = K.add(value, K.mul((a0, a1), e))
         return value
 
 
