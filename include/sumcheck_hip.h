@@ -310,6 +310,18 @@ int sc_ctx_kernel_time(sc_ctx* ctx, double out[2], int reset);
                                  * table it read: 2 T * 8 * 2^log_in bytes read with kf = 1, 2 T * 16 * 2^log_in with kf = 2, and
                                  * 2 T * 16 * 2^(log_in - 1) written.  ks = 0: ext_fold_kernel, one launch of sc_table_evaluate_ext - the
                                  * same fold of ONE table, nothing summed: the same bytes with 2 T replaced by 1 */
+#define SC_KIND_EXT_PRODUCT_TREE 39 /* a launch of sc_gp_create_ext from layer m = log_in of the product tree over K: kf = LV = 1..3,
+                                 * ext_gp_tree_kernel<F, LV, LEAF_IN>; ks = 1 where it read the base table and formed the leaves (m = n),
+                                 * else 2 (both planes of layer m); it reads ks * 8 * 2^m bytes and writes both planes of the layers
+                                 * m-1 .. m-LV, 16 * (2^m - 2^(m-LV)); kf = 0, ext_gp_tree_tail_kernel, one block from a layer of <= 2^11
+                                 * entries down to V_0: 16 * (2^m - 1) written */
+#define SC_KIND_EXT_PRODUCT_PASS 40 /* ext_gp_pass_kernel: one round of a layer of sc_gp_prove_ext; kf = 1 if it folded the previous challenge;
+                                 * ks = 1 where L and R are the halves of the base table with the leaves formed in registers (layer
+                                 * n - 1), else 2 (planes from the tree or folded tables); log_in = log2 of the entries per table it
+                                 * read: 16 * 2^log_in bytes of E plus 2 * ks * 8 * 2^log_in of L and R read, and 48 * 2^(log_in - 1)
+                                 * written with kf = 1 */
+#define SC_KIND_EXT_EQ_TABLE 41  /* ext_eq_table_kernel: eq(z, .) of a layer of sc_gp_prove_ext, z in K^k; log_in = k; reads the 2 k words
+                                 * of the point, writes both planes, 16 * 2^k */
 typedef struct sc_launch_record {
   int32_t kind;           /* SC_KIND_* */
   int32_t kf, ks;         /* variables folded / rounds served (meaning per kind above) */
@@ -900,6 +912,35 @@ int sc_sumprod_prove_ext(sc_ctx* ctx, uint64_t w, size_t count, const sc_table* 
  * hand-over of option "gp_host_log"; no table of 2^n weights is built.  SC_ERR_ARG: a bad w, a component that is not below p, a
  * table that has not 2^n entries. */
 int sc_table_evaluate_ext(sc_ctx* ctx, uint64_t w, const sc_table* t, const uint64_t* point, size_t n, uint64_t out[2]);
+
+/* ---- the grand product argument over K (kernels/ext_grand_product.hpp states the protocol) ----
+ * The protocol of sc_gp_* with every element in K = F_p[X] / (X^2 - w): the leaves are V_n[i] = beta + alpha t[i] for a base-field
+ * table t of 2^n entries, 1 <= n <= 28, and alpha, beta in K, alpha != 0; they are never stored.  The tree, the round values, the
+ * challenges, the finals, the point and the claim are elements of K, two consecutive Montgomery words each.  One device and one
+ * rank (SC_ERR_UNSUPPORTED on a sharded context or a multi-device handle, before anything else is looked at); p <= 3 is
+ * SC_ERR_UNSUPPORTED; SC_ERR_ARG: a NULL argument, a tree of another context, a table of fewer than 2 or more than 2^28 entries, a
+ * bad w (as sc_sumprod_prove_ext), a component of alpha or beta that is not below p, alpha = (0, 0). */
+typedef struct sc_gp_ext sc_gp_ext;
+/* The product tree over K (SC_KIND_EXT_PRODUCT_TREE; options "gp_tree_lv" as in sc_gp_create): one pool block of 2 * 2^n words.
+ * `t` is borrowed until sc_gp_destroy_ext and never written. */
+int sc_gp_create_ext(sc_ctx* ctx, uint64_t w, const sc_table* t, const uint64_t alpha[2], const uint64_t beta[2], sc_gp_ext** out);
+int sc_gp_destroy_ext(sc_ctx* ctx, sc_gp_ext* g);
+/* P = V_0[0] in K */
+int sc_gp_product_ext(const sc_gp_ext* g, uint64_t out[2]);
+/* copies of the two planes of V_k, k < n, as base tables of 2^k words (the c0 words, the c1 words): new tables the caller frees */
+int sc_gp_layer_ext(sc_ctx* ctx, const sc_gp_ext* g, size_t k, sc_table** c0, sc_table** c1);
+/* round < layer: msg = the eight words H(0).c0, H(0).c1, .., H(3).c1 of that round, out receives its challenge; round == layer:
+ * msg = the four words of (l, r'), out receives rho; both components below p */
+typedef void (*sc_draw_gp_ext_fn)(void* user, size_t layer, size_t round, const uint64_t* msg, uint64_t out[2]);
+/* The n layers.  evals (may be NULL): 8 words per round, 8 k (k - 1) / 2 words before layer k; finals: 4 per layer; challenges (may
+ * be NULL): 2 k (k + 1) / 2 words before layer k, the layer's rounds, then rho; point: 2 n words, z_n; claim: 2 words, c_n, so that
+ * t~(z_n) = (c_n - beta) / alpha.  draw == NULL: the synthetic challenger, draw number d = 0, 1, .. in protocol order being
+ * (to_mont(splitmix64(seed_r + 2 d + 1) mod p), to_mont(splitmix64(seed_r + 2 d + 2) mod p)).  A challenge with a component that
+ * is not below p ends the call with SC_ERR_ARG.  One eq table (SC_KIND_EXT_EQ_TABLE) and one launch per round
+ * (SC_KIND_EXT_PRODUCT_PASS) for every layer above the hand-over to the host (option "gp_host_log", as in sc_gp_prove); the
+ * transcript is the same at every value of the option. */
+int sc_gp_prove_ext(sc_ctx* ctx, const sc_gp_ext* g, sc_draw_gp_ext_fn draw, void* user, uint64_t seed_r, uint64_t* evals, uint64_t* finals,
+                    uint64_t* challenges, uint64_t* point, uint64_t* claim);
 
 /* ---- gkr_protocol::circuit::Circuit on the device, and the whole GKR prover over it ----------------------------------
  * A circuit lives on ONE context of one device and one rank: sharded contexts (world > 1) and multi-device handles get

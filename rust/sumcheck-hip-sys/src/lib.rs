@@ -117,6 +117,12 @@ pub struct sc_gp {
     _private: [u8; 0],
 }
 
+/// a product tree over the quadratic extension on the device (`sc_gp_create_ext`)
+#[repr(C)]
+pub struct sc_gp_ext {
+    _private: [u8; 0],
+}
+
 /// a pair of fraction-sum trees on the device (`sc_frac_create`)
 #[repr(C)]
 pub struct sc_frac {
@@ -141,6 +147,9 @@ pub type sc_draw_fold_fn = Option<unsafe extern "C" fn(user: *mut c_void, round:
 pub type sc_draw4_fn = Option<unsafe extern "C" fn(user: *mut c_void, round: usize, evals: *const u64) -> u64>;
 /// `sc_gp_prove`: `round < layer`: `msg` = H(0..3) of that round, returns its challenge; `round == layer`: `msg` = (l, r'), returns rho
 pub type sc_draw_gp_fn = Option<unsafe extern "C" fn(user: *mut c_void, layer: usize, round: usize, msg: *const u64) -> u64>;
+/// `sc_gp_prove_ext`: `round < layer`: `msg` = the eight words H(0).c0 .. H(3).c1, `out` = the challenge (c0, c1); `round == layer`:
+/// `msg` = (l, r'), four words, `out` = rho
+pub type sc_draw_gp_ext_fn = Option<unsafe extern "C" fn(user: *mut c_void, layer: usize, round: usize, msg: *const u64, out: *mut u64)>;
 /// `sc_frac_prove`: `round < layer`: `msg` = H(0..3), returns its challenge; `round == layer`: `msg` = (pl, pr, ql, qr), returns rho;
 /// `round == layer + 1`: `msg` is null, returns lambda of the next layer
 pub type sc_draw_frac_fn = Option<unsafe extern "C" fn(user: *mut c_void, layer: usize, round: usize, msg: *const u64) -> u64>;
@@ -800,4 +809,26 @@ extern "C" {
     ) -> c_int;
     /// the multilinear extension of a base table of 2^n entries at a point of K^n (2 n words); out: two words
     pub fn sc_table_evaluate_ext(ctx: *mut sc_ctx, w: u64, t: *const sc_table, point: *const u64, n: usize, out: *mut u64) -> c_int;
+    /// the product tree over K of the leaves beta + alpha t[i], t a base table of 2^n entries, 1 <= n <= 28
+    /// (SC_KIND_EXT_PRODUCT_TREE, 39); alpha, beta: two words each, alpha != 0; `t` is borrowed until `sc_gp_destroy_ext`
+    pub fn sc_gp_create_ext(ctx: *mut sc_ctx, w: u64, t: *const sc_table, alpha: *const u64, beta: *const u64, out: *mut *mut sc_gp_ext) -> c_int;
+    pub fn sc_gp_destroy_ext(ctx: *mut sc_ctx, g: *mut sc_gp_ext) -> c_int;
+    /// V_0[0], two words
+    pub fn sc_gp_product_ext(g: *const sc_gp_ext, out: *mut u64) -> c_int;
+    /// copies of the two planes of V_k, k < n, as base tables of 2^k words
+    pub fn sc_gp_layer_ext(ctx: *mut sc_ctx, g: *const sc_gp_ext, k: usize, c0: *mut *mut sc_table, c1: *mut *mut sc_table) -> c_int;
+    /// the n layers with every challenge in K (SC_KIND_EXT_EQ_TABLE, 41, and SC_KIND_EXT_PRODUCT_PASS, 40): evals 8 words per round
+    /// or null, finals 4 n, challenges n (n + 1) words or null, point 2 n, claim 2
+    pub fn sc_gp_prove_ext(
+        ctx: *mut sc_ctx,
+        g: *const sc_gp_ext,
+        draw: sc_draw_gp_ext_fn,
+        user: *mut c_void,
+        seed_r: u64,
+        evals: *mut u64,
+        finals: *mut u64,
+        challenges: *mut u64,
+        point: *mut u64,
+        claim: *mut u64,
+    ) -> c_int;
 }

@@ -273,3 +273,4 @@ __device__ __forceinline__ void transpose_to_pieces(ull2* __restrict__ lds, ull2
 #include "kernels/spark.hpp"
 #include "kernels/multiopen.hpp"
 #include "kernels/ext_sumprod.hpp"
+#include "kernels/ext_grand_product.hpp"

@@ -620,4 +620,5 @@ static int multi_prod2_fold_and_sums(sc_ctx* m, const sc_table* a, const sc_tabl
 #include "engine/abi_spark.inc"           // SPARK over LogUp: the committed sparse matrix, its gather and tuples, the triple-product sumcheck
 #include "engine/abi_multiopen.inc"       // batched openings: the weighted sum of eq tables, the sumcheck over a sum of products
 #include "engine/abi_ext.inc"             // challenges from a quadratic extension: the sum-of-products sumcheck, table evaluation
+#include "engine/abi_ext_gp.inc"          // the grand product argument over the quadratic extension
 #include "engine/abi_multi.inc"
