@@ -398,6 +398,49 @@ PARENT_PEAK_WORDS = {
     "triangle var_len=6": 9224,
     "batch 3 x n=10": 12712,
 }
+# the round-per-launch sumchecks at n = 12 with gp_host_log = fr_host_log = 1 (eleven device rounds: the first fold and the steady
+# hand-over of folded tables), measured the same way on the parent commit 0356acd with nothing but these entries added to it
+PARENT_PEAK_WORDS.update({
+    "sc_gp_prove n=12": 13824,
+    "sc_frac_prove n=12": 26112,
+    "sc_zerocheck_prove n=12": 26624,
+    "sc_sumprod_prove T=2 n=12": 30720,
+    "sc_sumprod_prove_ext T=2 n=12": 43008,
+    "sc_gp_prove_ext n=12": 22528,
+    "sc_product3_prove n=12": 21504,
+})
+
+
+def with_host_logs_1(ctx, call):
+    """call() with the layered and the flat sumchecks handing over to the host at two entries"""
+    keep = {k: ctx.get_option(k) for k in ("gp_host_log", "fr_host_log")}
+    for k in keep:
+        ctx.set_option(k, 1)
+    try:
+        call()
+    finally:
+        for k, v in keep.items():
+            ctx.set_option(k, v)
+
+
+def round_per_launch_calls(pkg, ctx, n=12):
+    F = ctx.field
+    w = F.from_int(pkg.ext_field.nonresidue(F.p))
+    tau = [int(x) for x in challenges(oracle(GOLD), n)]
+
+    def tables(count):
+        return [pkg.DenseMultilinearExtension.generate(ctx, pyref.SEED_A + i, n) for i in range(count)]
+    calls = [
+        ("sc_gp_prove", lambda: pkg.grand_product.prove(pkg.grand_product.ProductTree(ctx, *tables(1)), seed_r=pyref.SEED_R)),
+        ("sc_frac_prove", lambda: pkg.logup.prove(pkg.logup.FractionTree(ctx, *tables(2)), seed_r=pyref.SEED_R)),
+        ("sc_zerocheck_prove", lambda: pkg.r1cs.zerocheck_prove(ctx, *tables(3), tau, seed_r=pyref.SEED_R)),
+        ("sc_sumprod_prove T=2", lambda: pkg.multiopen.sumprod_prove(ctx, tables(2), tables(2), seed_r=pyref.SEED_R)),
+        ("sc_sumprod_prove_ext T=2", lambda: pkg.ext_sumcheck.sumprod_prove_ext(ctx, w, tables(2), tables(2), seed_r=pyref.SEED_R)),
+        ("sc_gp_prove_ext", lambda: pkg.ext_grand_product.prove_ext(
+            pkg.ext_grand_product.ExtProductTree(ctx, w, *tables(1), (F.one, F.one), (3, 5)), seed_r=pyref.SEED_R)),
+        ("sc_product3_prove", lambda: pkg.spark.product3_prove(ctx, *tables(3), seed_r=pyref.SEED_R)),
+    ]
+    return [("%s n=%d" % (name, n), lambda call=call: with_host_logs_1(ctx, call)) for name, call in calls]
 
 
 def peak_calls(pkg, ctx):
@@ -408,7 +451,7 @@ def peak_calls(pkg, ctx):
         ("dense GKR k=5", lambda: gkr_dense_prove(pkg, ctx, 5)),
         ("triangle var_len=6", lambda: triangle_prove(pkg, ctx, 6)),
         ("batch 3 x n=10", lambda: batch_prove(pkg, ctx)),
-    ]
+    ] + round_per_launch_calls(pkg, ctx)
 
 
 def measure_peaks(pkg):

@@ -219,7 +219,7 @@ int prove_batch_impl(sc_ctx* ctx, size_t count, const sc_table* const* a, const 
       else prover_answer(&q, j, e);
       if (j == 0) c1[i] = hf.add(e[0], e[1]);
       if (evals) memcpy(evals + 3 * (i * (size_t)n + j), e, sizeof(e));
-      const u64 r = draw ? draw(user, i, j, e) : hf.mul(sc::splitmix64(seed_r[i] + j + 1) % ctx->fp.p, ctx->fp.r2_mod_p);
+      const u64 r = draw ? draw(user, i, j, e) : seeded_challenge(ctx, hf, seed_r[i], j);
       if (r >= ctx->fp.p) {
         rc = fail(ctx, SC_ERR_ARG, "sc_prove_batch: draw() returned an unreduced challenge (instance %zu, round %zu)", i, j);
         break;

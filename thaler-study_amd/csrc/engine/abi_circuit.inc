@@ -206,7 +206,7 @@ extern "C" int sc_gkr_prove_circuit(sc_ctx* ctx, const sc_circuit* c, const sc_t
   // the reference Verifier's draws, in its order; evals = the round's sums when the draw follows a round message
   size_t t = 0;
   auto next = [&](const u64* e, u64* r) -> int {
-    const u64 v = draw ? draw(user, t, e) : hf.mul(sc::splitmix64(seed_r + t + 1) % ctx->fp.p, ctx->fp.r2_mod_p);
+    const u64 v = draw ? draw(user, t, e) : seeded_challenge(ctx, hf, seed_r, t);
     if (v >= ctx->fp.p) return fail(ctx, SC_ERR_ARG, "draw() returned an unreduced challenge (draw %zu)", t);
     if (draws) draws[t] = v;
     ++t;

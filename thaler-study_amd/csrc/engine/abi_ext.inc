@@ -1,14 +1,13 @@
 // Part of sumcheck_hip.hip (included there, in order, after abi_multiopen.inc): the sum-of-products sumcheck with challenges from
 // the quadratic extension K = F_p[X] / (X^2 - w), and the evaluation of a base table at a point of K^n (kernels/ext_sumprod.hpp
-// states the conventions).  Round 0 is abi_multiopen.inc's launch; every later device round is ext_sumprod_pass_kernel.
+// states the conventions).  Round 0 is sumprod_pass_kernel, the base-field launch; every later device round is ext_sumprod_pass_kernel.
 
 namespace {
 
 // how many blocks of ext_sumprod_pass_kernel the device holds at once (the extension-in form of the widest T: the most registers)
 int ext_sumprod_resident(sc_ctx* ctx) {
-  const void* fn = ctx->gold ? kernel_ptr(&sc::ext_sumprod_pass_kernel<sc::GoldilocksMont, sc::kSumprodMaxPairs, false>)
-                             : kernel_ptr(&sc::ext_sumprod_pass_kernel<sc::MontGeneric, sc::kSumprodMaxPairs, false>);
-  return std::min(resident_grid(ctx, fn, sc::kBlock, ctx->max_blocks), ctx->max_blocks);
+  return resident_blocks(ctx, &sc::ext_sumprod_pass_kernel<sc::GoldilocksMont, sc::kSumprodMaxPairs, false>,
+                         &sc::ext_sumprod_pass_kernel<sc::MontGeneric, sc::kSumprodMaxPairs, false>);
 }
 
 // w must be a word below p and a quadratic non-residue: w^((p-1)/2) = -1
@@ -16,77 +15,6 @@ int check_nonresidue(sc_ctx* ctx, const HostField& hf, u64 w, const char* what) 
   if (w >= ctx->fp.p) return fail(ctx, SC_ERR_ARG, "%s: w is not a word below p", what);
   if (hf.pow(w, (ctx->fp.p - 1) / 2) != hf.neg(hf.one()))
     return fail(ctx, SC_ERR_ARG, "%s: w is not a quadratic non-residue of the field (w^((p-1)/2) is not p - 1)", what);
-  return SC_OK;
-}
-
-// The device rounds of the extension sumcheck, tables of 2^n entries, n > te >= 1: rounds 0 .. n - te - 1 are completed -
-// next(round, six words, c) draws, rs[2 round ..] receives c - and the launch of round n - te >= 1 leaves its six words in e and
-// tables of two planes of 2^te words at in[.], which the host takes.  in[.]: the 2T base tables of round 0, never written; cur[.]
-// owns every folded table.  next() returning false ends the call with *stopped.
-template <class Next>
-int ext_device_rounds(sc_ctx* ctx, u64 w, int T, int n, int te, const u64** in, PoolBuf* cur, u64* rs, u64 (&e)[6], const int* stopped, Next&& next) {
-  PoolBuf nxt[2 * sc::kSumprodMaxPairs];
-  const int resident0 = sumprod_pass_resident(ctx), resident = ext_sumprod_resident(ctx);
-  u64 r_prev[2] = {0, 0};
-  for (int j = 0; j <= n - te; ++j) {
-    const bool fold = j > 0, base_in = j == 1;
-    const int log_in = fold ? n - j + 1 : n;
-    const size_t n_units = (size_t)1 << (n - j - 1);
-    sc::SpTables tb;
-    memset(&tb, 0, sizeof(tb));
-    for (int q = 0; q < 2 * T; ++q) {
-      u64* o = nullptr;
-      if (fold) {
-        SC_TRY(nxt[q].alloc(ctx, (size_t)4 * n_units));   // two planes of 2 n_units words
-        o = nxt[q].get();
-      }
-      if (q < T) {
-        tb.a[q] = in[q];
-        tb.ao[q] = o;
-      } else {
-        tb.b[q - T] = in[q];
-        tb.bo[q - T] = o;
-      }
-    }
-    const int grid = (int)std::max<size_t>(1, std::min<size_t>((n_units + sc::kBlock - 1) / sc::kBlock, (size_t)(fold ? resident : resident0)));
-    bool mb = false;
-    const sc::PassOut po = next_pass_out(ctx, false, 0, &mb);
-    const u64 words = ((u64)2 * (u64)T) << log_in;   // entries of all input tables
-    if (!fold) {
-      SC_TRY(timer_begin(ctx, SC_KIND_SUMPROD_PASS, 0, T, log_in, 8 * words, 0));
-      SC_DISPATCH_FIELD(ctx, F, f, with_const<1, 2, 3, 4, 5, 6, 7, 8>(T, [&](auto TT) {
-        hipLaunchKernelGGL((sc::sumprod_pass_kernel<F, TT, false>), dim3(grid), dim3(sc::kBlock), 0, ctx->stream, f, tb, (u64)0, n_units, po);
-      }));
-    } else {
-      SC_TRY(timer_begin(ctx, SC_KIND_SUMPROD_EXT_PASS, base_in ? 1 : 2, T, log_in, (base_in ? 8 : 16) * words, 8 * words));
-      SC_DISPATCH_FIELD(ctx, F, f, with_bool(base_in, [&](auto BASE_IN) {
-        with_const<1, 2, 3, 4, 5, 6, 7, 8>(T, [&](auto TT) {
-          hipLaunchKernelGGL((sc::ext_sumprod_pass_kernel<F, TT, BASE_IN>), dim3(grid), dim3(sc::kBlock), 0, ctx->stream, f, tb, w, r_prev[0],
-                             r_prev[1], n_units, po);
-        });
-      }));
-    }
-    SC_TRY(commit_pass_out(ctx, po, grid));
-    SC_TRY(timer_end(ctx));
-    if (fold) {
-      for (int q = 0; q < 2 * T; ++q) {
-        cur[q] = std::move(nxt[q]);   // (the tables of round j - 1 go back: the launch that reads them is queued)
-        in[q] = cur[q].get();
-      }
-      SC_TRY(collect_sums(ctx, 6, false, mb, e));
-    } else {
-      u64 e3[3];
-      SC_TRY(collect_sums(ctx, 3, false, mb, e3));
-      for (int s = 0; s < 3; ++s) {
-        e[2 * s] = e3[s];
-        e[2 * s + 1] = 0;
-      }
-    }
-    if (j == n - te) break;   // the host draws this round's challenge
-    if (!next((size_t)j, e, r_prev)) return *stopped;
-    rs[2 * (size_t)j] = r_prev[0];
-    rs[2 * (size_t)j + 1] = r_prev[1];
-  }
   return SC_OK;
 }
 
@@ -129,7 +57,7 @@ extern "C" int sc_sumprod_prove_ext(sc_ctx* ctx, uint64_t w, size_t count, const
     if (draw) {
       draw(user, round, msg, r);
     } else {
-      for (int k = 0; k < 2; ++k) r[k] = hf.mul(sc::splitmix64(seed_r + 2 * (u64)round + 1 + (u64)k) % ctx->fp.p, ctx->fp.r2_mod_p);
+      for (int k = 0; k < 2; ++k) r[k] = seeded_challenge(ctx, hf, seed_r, 2 * (u64)round + (u64)k);
     }
     if (r[0] >= ctx->fp.p || r[1] >= ctx->fp.p) {
       rc = fail(ctx, SC_ERR_ARG, "sc_sumprod_prove_ext: draw() returned a challenge with an unreduced component");
@@ -154,7 +82,42 @@ extern "C" int sc_sumprod_prove_ext(sc_ctx* ctx, uint64_t w, size_t count, const
   for (int q = 0; q < 4 * T; ++q) pl[q] = host.data() + (size_t)q * left;
   u64 e[6];
   const bool on_device = n > te;
-  if (on_device) SC_TRY(ext_device_rounds(ctx, w, T, n, te, in, cur, rs.data(), e, &rc, next));
+  if (on_device) {
+    // Round 0 has nothing to fold and base tables: sumprod_pass_kernel, whose three sums are the c0 words of the round's message.
+    // It is never the hand-over (n > te), so next() sees every message of that form and widens it first.  The launch of round 1
+    // folds base tables into planes, every later one planes into planes; folded tables are two planes of 2 n_units words.
+    const int resident0 = sumprod_pass_resident(ctx), resident = ext_sumprod_resident(ctx);
+    auto widened = [&](size_t round, u64* msg, u64* out) {
+      if (round == 0)
+        for (int s = 2; s >= 0; --s) {
+          msg[2 * s] = msg[s];
+          msg[2 * s + 1] = 0;
+        }
+      return next(round, msg, out);
+    };
+    SC_TRY((device_rounds<2 * sc::kSumprodMaxPairs, 2, 4>(ctx, 2 * T, n, te, in, cur, rs.data(), e, &rc, [&](const DeviceRound& d, Launched* l) {
+      const sc::SpTables tb = sumprod_tables(d, T);
+      const u64 words = ((u64)2 * (u64)T) << d.log_in;   // entries of all input tables
+      if (d.round == 0) {
+        *l = {d.grid(resident0), 3};
+        SC_TRY(timer_begin(ctx, SC_KIND_SUMPROD_PASS, 0, T, d.log_in, 8 * words, 0));
+        SC_DISPATCH_FIELD(ctx, F, f, with_const<1, 2, 3, 4, 5, 6, 7, 8>(T, [&](auto TT) {
+          hipLaunchKernelGGL((sc::sumprod_pass_kernel<F, TT, false>), dim3(l->grid), dim3(sc::kBlock), 0, ctx->stream, f, tb, (u64)0, d.n_units, d.po);
+        }));
+        return SC_OK;
+      }
+      const bool base_in = d.round == 1;
+      *l = {d.grid(resident), 6};
+      SC_TRY(timer_begin(ctx, SC_KIND_SUMPROD_EXT_PASS, base_in ? 1 : 2, T, d.log_in, (base_in ? 8 : 16) * words, 8 * words));
+      SC_DISPATCH_FIELD(ctx, F, f, with_bool(base_in, [&](auto BASE_IN) {
+        with_const<1, 2, 3, 4, 5, 6, 7, 8>(T, [&](auto TT) {
+          hipLaunchKernelGGL((sc::ext_sumprod_pass_kernel<F, TT, BASE_IN>), dim3(l->grid), dim3(sc::kBlock), 0, ctx->stream, f, tb, w, d.r_prev[0],
+                             d.r_prev[1], d.n_units, d.po);
+        });
+      }));
+      return SC_OK;
+    }, widened)));
+  }
   // a folded table is its two planes, adjacent; a base table fills the c0 plane and leaves the zeros of the c1 plane
   for (int q = 0; q < 2 * T; ++q)
     SC_HIP(ctx, hipMemcpyAsync(pl[2 * q], in[q], (on_device ? 2 : 1) * left * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));

@@ -18,41 +18,33 @@ int check_gp_ext(sc_ctx* ctx, const sc_gp_ext* g, const char* what) {
   return SC_OK;
 }
 
-// the launches of the tree: from layer n (the leaves formed in registers), up to gp_tree_lv layers per launch down to layer
-// kExtGpTailLog, then the tail kernel
+// the launches of the tree (tree_schedule): ext_gp_tree_kernel from layer m over lv layers, ext_gp_tree_tail_kernel below layer
+// kExtGpTailLog; the launch from layer n forms the leaves in registers
 int ext_gp_build_tree(sc_ctx* ctx, sc_gp_ext* g, int tree_lv) {
-  int m = g->n;
   u64* const tree = g->tree.get();
   const size_t heap = (size_t)1 << g->n;
   const sc::ExtGpLeaf lf = g->lf;
-  auto source = [&](int layer, bool* leaf_in) {
-    *leaf_in = layer == g->n;
-    return *leaf_in ? (const u64*)g->t->d : (const u64*)tree + ((size_t)1 << layer);
-  };
-  while (m > sc::kExtGpTailLog) {
-    const int lv = std::min(tree_lv, m - sc::kExtGpTailLog);
-    bool leaf_in = false;
-    const u64* src = source(m, &leaf_in);
+  return tree_schedule(g->n, sc::kExtGpTailLog, tree_lv, [&](int m, int lv) {
+    const bool leaf_in = m == g->n;
+    const u64* src = leaf_in ? (const u64*)g->t->d : (const u64*)tree + ((size_t)1 << m);
+    const u64 read = (u64)(leaf_in ? 8 : 16) << m;
+    if (lv == 0)
+      return launch_recorded(ctx, {SC_KIND_EXT_PRODUCT_TREE, 0, leaf_in ? 1 : 2, m, read, ((u64)16 << m) - 16}, "ext_gp_tree_tail_kernel", [&] {
+        SC_DISPATCH_FIELD(ctx, F, f, with_bool(leaf_in, [&](auto LEAF_IN) {
+          hipLaunchKernelGGL((sc::ext_gp_tree_tail_kernel<F, LEAF_IN>), dim3(1), dim3(sc::kBlock), 0, ctx->stream, f, lf, src, heap, tree, heap, m);
+        }));
+      });
     const int log_low = m - lv;
     const size_t n_units = (size_t)1 << (log_low - 1);
     const int grid = grid_for(ctx, n_units);
-    SC_TRY(launch_recorded(ctx, {SC_KIND_EXT_PRODUCT_TREE, lv, leaf_in ? 1 : 2, m, (u64)(leaf_in ? 8 : 16) << m, ((u64)16 << m) - ((u64)16 << log_low)},
-                           "ext_gp_tree_kernel", [&] {
+    return launch_recorded(ctx, {SC_KIND_EXT_PRODUCT_TREE, lv, leaf_in ? 1 : 2, m, read, ((u64)16 << m) - ((u64)16 << log_low)}, "ext_gp_tree_kernel", [&] {
       SC_DISPATCH_FIELD(ctx, F, f, with_bool(leaf_in, [&](auto LEAF_IN) {
         with_const<1, 2, 3>(lv, [&](auto LV) {
           hipLaunchKernelGGL((sc::ext_gp_tree_kernel<F, LV, LEAF_IN>), dim3(grid), dim3(sc::kBlock), 0, ctx->stream, f, lf, src, heap, tree, heap, log_low,
                              n_units);
         });
       }));
-    }));
-    m = log_low;
-  }
-  bool leaf_in = false;
-  const u64* src = source(m, &leaf_in);
-  return launch_recorded(ctx, {SC_KIND_EXT_PRODUCT_TREE, 0, leaf_in ? 1 : 2, m, (u64)(leaf_in ? 8 : 16) << m, ((u64)16 << m) - 16}, "ext_gp_tree_tail_kernel", [&] {
-    SC_DISPATCH_FIELD(ctx, F, f, with_bool(leaf_in, [&](auto LEAF_IN) {
-      hipLaunchKernelGGL((sc::ext_gp_tree_tail_kernel<F, LEAF_IN>), dim3(1), dim3(sc::kBlock), 0, ctx->stream, f, lf, src, heap, tree, heap, m);
-    }));
+    });
   });
 }
 
@@ -71,82 +63,12 @@ int build_ext_eq_table(sc_ctx* ctx, u64 w, const u64* z, int k, PoolBuf* out) {
   return SC_OK;
 }
 
-// The tables of a device layer as its next launch reads them: planes at in[q], in[q] + stride[q] - or, while `leaf`, in[1] and
-// in[2] are the halves of t as base words
-struct ExtGpCursor {
-  const u64* in[3];
-  size_t stride[3];
-  bool leaf;
-};
-
-// The device rounds of a cubic sumcheck over three extension tables of 2^k entries, k > te >= 1 (ext_gp_pass_kernel, one launch per
-// round, SC_KIND_EXT_PRODUCT_PASS): rounds 0 .. k - te - 1 are completed - next(round, eight words, c) draws, rs[2 round ..] receives
-// c - and the launch of round k - te leaves its eight words in e and tables of 2^te entries at cu, which the host takes.  The tables
-// of round 0 are never written; cur[.] owns every folded table (the block cur[0] holds on entry, the eq table, is given back as
-// that one was).  next() returning false ends the call with *stopped.
-template <class Next>
-int ext_gp_device_rounds(sc_ctx* ctx, const sc::ExtGpLeaf& lf, int k, int te, int resident, ExtGpCursor& cu, PoolBuf (&cur)[3], u64* rs, u64 (&e)[8],
-                         const int* stopped, Next&& next) {
-  PoolBuf nxt[3];
-  u64 r_prev[2] = {0, 0};
-  for (int j = 0; j <= k - te; ++j) {
-    const bool fold = j > 0, leaf = cu.leaf;
-    const int log_in = fold ? k - j + 1 : k;
-    const size_t n_units = (size_t)1 << (k - j - 1);
-    sc::ExtGpTables tb;
-    for (int q = 0; q < 3; ++q) {
-      tb.in[q] = cu.in[q];
-      tb.stride[q] = cu.stride[q];
-      tb.out[q] = nullptr;
-      if (fold) {
-        SC_TRY(nxt[q].alloc(ctx, (size_t)4 * n_units));   // two planes of 2 n_units words
-        tb.out[q] = nxt[q].get();
-      }
-    }
-    const int grid = (int)std::max<size_t>(1, std::min<size_t>((n_units + sc::kBlock - 1) / sc::kBlock, (size_t)resident));
-    bool mb = false;
-    const sc::PassOut po = next_pass_out(ctx, false, 0, &mb);
-    SC_TRY(timer_begin(ctx, SC_KIND_EXT_PRODUCT_PASS, fold ? 1 : 0, leaf ? 1 : 2, log_in, ((u64)16 << log_in) + ((u64)(leaf ? 16 : 32) << log_in),
-                       fold ? (u64)48 << (log_in - 1) : 0));
-    SC_DISPATCH_FIELD(ctx, F, f, with_bool(fold, [&](auto FOLD) {
-      with_bool(leaf, [&](auto LEAF_IN) {
-        hipLaunchKernelGGL((sc::ext_gp_pass_kernel<F, FOLD, LEAF_IN>), dim3(grid), dim3(sc::kBlock), 0, ctx->stream, f, tb, lf, r_prev[0], r_prev[1], n_units,
-                           po);
-      });
-    }));
-    SC_TRY(commit_pass_out(ctx, po, grid));
-    SC_TRY(timer_end(ctx));
-    if (fold) {
-      for (int q = 0; q < 3; ++q) {
-        cur[q] = std::move(nxt[q]);   // (the tables of round j - 1 go back: the launch that reads them is queued)
-        cu.in[q] = cur[q].get();
-        cu.stride[q] = (size_t)2 * n_units;
-      }
-      cu.leaf = false;
-    }
-    SC_TRY(collect_sums(ctx, 8, false, mb, e));
-    if (j == k - te) break;   // the host draws this round's challenge
-    if (!next((size_t)j, e, r_prev)) return *stopped;
-    rs[2 * (size_t)j] = r_prev[0];
-    rs[2 * (size_t)j + 1] = r_prev[1];
-  }
-  return SC_OK;
-}
-
-// how many blocks of ext_gp_pass_kernel the device holds at once (the planes-in fold: the most registers)
-int ext_gp_pass_resident(sc_ctx* ctx) {
-  const void* fn = ctx->gold ? kernel_ptr(&sc::ext_gp_pass_kernel<sc::GoldilocksMont, true, false>)
-                             : kernel_ptr(&sc::ext_gp_pass_kernel<sc::MontGeneric, true, false>);
-  return std::min(resident_grid(ctx, fn, sc::kBlock, ctx->max_blocks), ctx->max_blocks);
-}
-
 }  // namespace
 
 extern "C" int sc_gp_create_ext(sc_ctx* ctx, uint64_t w, const sc_table* t, const uint64_t alpha[2], const uint64_t beta[2], sc_gp_ext** out) {
   if (!ctx) return SC_ERR_ARG;
   SC_TRY(one_device_only(ctx, "sc_gp_create_ext"));
-  if (ctx->fp.p <= 3) return fail(ctx, SC_ERR_UNSUPPORTED, "sc_gp_create_ext: p = %llu: a cubic through 0, 1, 2, 3 needs 2 and 3 invertible",
-                                  (unsigned long long)ctx->fp.p);
+  SC_TRY(require_cubic_field(ctx, "sc_gp_create_ext"));
   if (!t || !alpha || !beta || !out) return fail(ctx, SC_ERR_ARG, "sc_gp_create_ext: a NULL argument");
   SC_TRY(check_table(ctx, t, "sc_gp_create_ext"));
   if (t->len < 2 || t->len > ((size_t)1 << sc::kGpMaxLog))
@@ -215,8 +137,7 @@ extern "C" int sc_gp_prove_ext(sc_ctx* ctx, const sc_gp_ext* g, sc_draw_gp_ext_f
                                uint64_t* challenges, uint64_t* point, uint64_t* claim) {
   if (!ctx) return SC_ERR_ARG;
   SC_TRY(one_device_only(ctx, "sc_gp_prove_ext"));
-  if (ctx->fp.p <= 3) return fail(ctx, SC_ERR_UNSUPPORTED, "sc_gp_prove_ext: p = %llu: a cubic through 0, 1, 2, 3 needs 2 and 3 invertible",
-                                  (unsigned long long)ctx->fp.p);
+  SC_TRY(require_cubic_field(ctx, "sc_gp_prove_ext"));
   if (!finals || !point || !claim) return fail(ctx, SC_ERR_ARG, "sc_gp_prove_ext: a NULL argument");
   SC_TRY(check_gp_ext(ctx, g, "sc_gp_prove_ext"));
   SC_TRY(set_device(ctx));
@@ -248,7 +169,8 @@ extern "C" int sc_gp_prove_ext(sc_ctx* ctx, const sc_gp_ext* g, sc_draw_gp_ext_f
       bottom[1][heap + i] = o[1];
     }
   }
-  const int resident = ext_gp_pass_resident(ctx);
+  // (the resident blocks of the planes-in fold: the most registers)
+  const int resident = resident_blocks(ctx, &sc::ext_gp_pass_kernel<sc::GoldilocksMont, true, false>, &sc::ext_gp_pass_kernel<sc::MontGeneric, true, false>);
 
   // the challenger, in protocol order: one draw per round and one per rho, two words each
   u64 n_draws = 0;
@@ -258,7 +180,7 @@ extern "C" int sc_gp_prove_ext(sc_ctx* ctx, const sc_gp_ext* g, sc_draw_gp_ext_f
     if (draw) {
       draw(user, layer, round, msg, c);
     } else {
-      for (int s = 0; s < 2; ++s) c[s] = hf.mul(sc::splitmix64(seed_r + 2 * n_draws + 1 + (u64)s) % ctx->fp.p, ctx->fp.r2_mod_p);
+      for (int s = 0; s < 2; ++s) c[s] = seeded_challenge(ctx, hf, seed_r, 2 * n_draws + (u64)s);
     }
     n_draws += 1;
     if (c[0] >= ctx->fp.p || c[1] >= ctx->fp.p) {
@@ -296,29 +218,49 @@ extern "C" int sc_gp_prove_ext(sc_ctx* ctx, const sc_gp_ext* g, sc_draw_gp_ext_f
       const int te = std::max(T, 1);
       PoolBuf cur[3];
       SC_TRY(build_ext_eq_table(ctx, w, z.data(), k, &cur[0]));
-      ExtGpCursor cu;
-      cu.leaf = k == n - 1;
-      cu.in[0] = cur[0].get();
-      cu.stride[0] = len;
-      cu.in[1] = cu.leaf ? (const u64*)g->t->d : (const u64*)g->tree.get() + 2 * len;
-      cu.in[2] = cu.in[1] + len;
-      cu.stride[1] = cu.stride[2] = heap;
+      // The layer's own tables: E in two planes of 2^k words, the halves of layer k + 1 as planes a heap apart - or, under the
+      // leaves (k = n - 1), the halves of t as base words.  The launches of rounds 0 and 1 read them (round 1 is the first fold);
+      // from round 2 on a launch reads folded tables, two adjacent planes of 2^log_in words.
+      const bool leaf_layer = k == n - 1;
+      const u64* lk = leaf_layer ? (const u64*)g->t->d : (const u64*)g->tree.get() + 2 * len;
+      const u64* in[3] = {cur[0].get(), lk, lk + len};
       u64 e[8];
-      SC_TRY(ext_gp_device_rounds(ctx, lf, k, te, resident, cu, cur, rs.data(), e, &rc, next));
+      SC_TRY((device_rounds<3, 2, 4>(ctx, 3, k, te, in, cur, rs.data(), e, &rc, [&](const DeviceRound& d, Launched* l) {
+        const bool fold = d.round > 0, own = d.round <= 1, leaf = own && leaf_layer;
+        sc::ExtGpTables tb;
+        for (int q = 0; q < 3; ++q) {
+          tb.in[q] = d.in[q];
+          tb.stride[q] = own ? (q == 0 ? len : heap) : (size_t)1 << d.log_in;
+          tb.out[q] = d.out[q];
+        }
+        *l = {d.grid(resident), 8};
+        SC_TRY(timer_begin(ctx, SC_KIND_EXT_PRODUCT_PASS, fold ? 1 : 0, leaf ? 1 : 2, d.log_in, ((u64)16 << d.log_in) + ((u64)(leaf ? 16 : 32) << d.log_in),
+                           fold ? (u64)48 << (d.log_in - 1) : 0));
+        SC_DISPATCH_FIELD(ctx, F, f, with_bool(fold, [&](auto FOLD) {
+          with_bool(leaf, [&](auto LEAF_IN) {
+            hipLaunchKernelGGL((sc::ext_gp_pass_kernel<F, FOLD, LEAF_IN>), dim3(l->grid), dim3(sc::kBlock), 0, ctx->stream, f, tb, lf, d.r_prev[0], d.r_prev[1],
+                               d.n_units, d.po);
+          });
+        }));
+        return SC_OK;
+      }, next)));
+      // what the host takes: folded tables (planes 2^te words apart) - or, where the one launch folded nothing (k = te), the
+      // layer's own, whose leaves are formed below
       const size_t left = (size_t)1 << te;
+      const bool folded = k > te, leaves_in = leaf_layer && !folded;
       host.assign(6 * left, 0);
       for (int q = 0; q < 6; ++q) pl[q] = host.data() + (size_t)q * left;
-      if (cu.leaf) leaves.resize(2 * left);
+      if (leaves_in) leaves.resize(2 * left);
       for (int q = 0; q < 3; ++q) {
-        if (cu.leaf && q > 0) {   // (no launch folded: the halves of t, whose leaves are formed below)
-          SC_HIP(ctx, hipMemcpyAsync(leaves.data() + (size_t)(q - 1) * left, cu.in[q], left * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+        if (leaves_in && q > 0) {
+          SC_HIP(ctx, hipMemcpyAsync(leaves.data() + (size_t)(q - 1) * left, in[q], left * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
           continue;
         }
-        for (int c = 0; c < 2; ++c)
-          SC_HIP(ctx, hipMemcpyAsync(pl[2 * q + c], cu.in[q] + (size_t)c * cu.stride[q], left * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+        const size_t stride = folded ? left : q == 0 ? len : heap;
+        for (int c = 0; c < 2; ++c) SC_HIP(ctx, hipMemcpyAsync(pl[2 * q + c], in[q] + (size_t)c * stride, left * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
       }
       SC_HIP(ctx, sync_stream(ctx));
-      if (cu.leaf)
+      if (leaves_in)
         for (int q = 1; q < 3; ++q)
           for (size_t i = 0; i < left; ++i) {
             u64 o[2];

@@ -24,36 +24,31 @@ const u64* fr_layer_ptr(const sc_frac* g, int which, int k) {
   return t ? t->d : nullptr;
 }
 
-// the launches of the trees: from layer n, up to tree_lv layers per launch down to layer kFrTailLog, then the tail kernel
+// the launches of the trees (tree_schedule): fr_tree_kernel from layer m over lv layers, fr_tree_tail_kernel below layer kFrTailLog
 int fr_build_trees(sc_ctx* ctx, sc_frac* g, int tree_lv) {
-  int m = g->n;
   u64* const pt = g->tree[0].get();
   u64* const qt = g->tree[1].get();
-  while (m > sc::kFrTailLog) {
-    const int lv = std::min(tree_lv, m - sc::kFrTailLog);
+  return tree_schedule(g->n, sc::kFrTailLog, tree_lv, [&](int m, int lv) {
     const u64* ps = fr_layer_ptr(g, 0, m);
     const u64* qs = fr_layer_ptr(g, 1, m);
     const bool ones = !ps;
+    const u64 read = (u64)(ones ? 8 : 16) << m;
+    if (lv == 0)
+      return launch_recorded(ctx, {SC_KIND_FRACTION_TREE, 0, ones ? 1 : 2, m, read, ((u64)16 << m) - 16}, "fr_tree_tail_kernel", [&] {
+        SC_DISPATCH_FIELD(ctx, F, f, with_bool(ones, [&](auto ONES) {
+          hipLaunchKernelGGL((sc::fr_tree_tail_kernel<F, ONES>), dim3(1), dim3(sc::kBlock), 0, ctx->stream, f, ps, qs, pt, qt, m);
+        }));
+      });
     const int log_low = m - lv;
     const size_t n_units = (size_t)1 << (log_low - 1);
     const int grid = grid_for(ctx, n_units);
-    const u64 read = (u64)(ones ? 8 : 16) << m, written = ((u64)16 << m) - ((u64)16 << log_low);
-    SC_TRY(launch_recorded(ctx, {SC_KIND_FRACTION_TREE, lv, ones ? 1 : 2, m, read, written}, "fr_tree_kernel", [&] {
+    return launch_recorded(ctx, {SC_KIND_FRACTION_TREE, lv, ones ? 1 : 2, m, read, ((u64)16 << m) - ((u64)16 << log_low)}, "fr_tree_kernel", [&] {
       SC_DISPATCH_FIELD(ctx, F, f, with_const<1, 2, 3>(lv, [&](auto LV) {
         with_bool(ones, [&](auto ONES) {
           hipLaunchKernelGGL((sc::fr_tree_kernel<F, LV, ONES>), dim3(grid), dim3(sc::kBlock), 0, ctx->stream, f, ps, qs, pt, qt, log_low, n_units);
         });
       }));
-    }));
-    m = log_low;
-  }
-  const u64* ps = fr_layer_ptr(g, 0, m);
-  const u64* qs = fr_layer_ptr(g, 1, m);
-  const bool ones = !ps;
-  return launch_recorded(ctx, {SC_KIND_FRACTION_TREE, 0, ones ? 1 : 2, m, (u64)(ones ? 8 : 16) << m, ((u64)16 << m) - 16}, "fr_tree_tail_kernel", [&] {
-    SC_DISPATCH_FIELD(ctx, F, f, with_bool(ones, [&](auto ONES) {
-      hipLaunchKernelGGL((sc::fr_tree_tail_kernel<F, ONES>), dim3(1), dim3(sc::kBlock), 0, ctx->stream, f, ps, qs, pt, qt, m);
-    }));
+    });
   });
 }
 
@@ -62,8 +57,7 @@ int fr_build_trees(sc_ctx* ctx, sc_frac* g, int tree_lv) {
 extern "C" int sc_frac_create(sc_ctx* ctx, const sc_table* p, const sc_table* q, sc_frac** out) {
   if (!ctx) return SC_ERR_ARG;
   SC_TRY(one_device_only(ctx, "sc_frac_create"));
-  if (ctx->fp.p <= 3) return fail(ctx, SC_ERR_UNSUPPORTED, "sc_frac_create: p = %llu: a cubic through 0, 1, 2, 3 needs 2 and 3 invertible",
-                                  (unsigned long long)ctx->fp.p);
+  SC_TRY(require_cubic_field(ctx, "sc_frac_create"));
   if (!q || !out) return fail(ctx, SC_ERR_ARG, "sc_frac_create: a NULL argument");
   SC_TRY(check_table(ctx, q, "sc_frac_create"));
   if (p) SC_TRY(check_table(ctx, p, "sc_frac_create"));
@@ -119,8 +113,7 @@ extern "C" int sc_frac_prove(sc_ctx* ctx, const sc_frac* g, sc_draw_frac_fn draw
                              uint64_t* challenges, uint64_t* point, uint64_t claims[2]) {
   if (!ctx) return SC_ERR_ARG;
   SC_TRY(one_device_only(ctx, "sc_frac_prove"));
-  if (ctx->fp.p <= 3) return fail(ctx, SC_ERR_UNSUPPORTED, "sc_frac_prove: p = %llu: a cubic through 0, 1, 2, 3 needs 2 and 3 invertible",
-                                  (unsigned long long)ctx->fp.p);
+  SC_TRY(require_cubic_field(ctx, "sc_frac_prove"));
   if (!finals || !point || !claims) return fail(ctx, SC_ERR_ARG, "sc_frac_prove: a NULL argument");
   SC_TRY(check_frac(ctx, g, "sc_frac_prove"));
   SC_TRY(set_device(ctx));
@@ -143,14 +136,13 @@ extern "C" int sc_frac_prove(sc_ctx* ctx, const sc_frac* g, sc_draw_frac_fn draw
     }
   }
   SC_HIP(ctx, sync_stream(ctx));
-  const void* fn = ctx->gold ? kernel_ptr(&sc::fr_pass_kernel<sc::GoldilocksMont, true, false>) : kernel_ptr(&sc::fr_pass_kernel<sc::MontGeneric, true, false>);
-  const int resident = std::min(resident_grid(ctx, fn, sc::kBlock, ctx->max_blocks), ctx->max_blocks);
+  const int resident = resident_blocks(ctx, &sc::fr_pass_kernel<sc::GoldilocksMont, true, false>, &sc::fr_pass_kernel<sc::MontGeneric, true, false>);
 
   // the challenger, in protocol order: per layer its lambda (k >= 1), one draw per round, and rho
   u64 n_draws = 0;
   int rc = SC_OK;
   auto challenge = [&](size_t layer, size_t round, const u64* msg, u64* out) {
-    const u64 c = draw ? draw(user, layer, round, msg) : hf.mul(sc::splitmix64(seed_r + n_draws + 1) % ctx->fp.p, ctx->fp.r2_mod_p);
+    const u64 c = draw ? draw(user, layer, round, msg) : seeded_challenge(ctx, hf, seed_r, n_draws);
     if (c >= ctx->fp.p) {
       rc = fail(ctx, SC_ERR_ARG, "sc_frac_prove: draw() returned an unreduced challenge");
       return false;
@@ -189,46 +181,29 @@ extern "C" int sc_frac_prove(sc_ctx* ctx, const sc_frac* g, sc_draw_frac_fn draw
     } else {
       // the device runs the rounds 0 .. k - te; the launch of round k - te leaves tables of 2^te entries, which the host takes
       const int te = std::max(T, 1);
-      PoolBuf cur[5], nxt[5];
+      PoolBuf cur[5];
       SC_TRY(build_eq_table(ctx, z.data(), k, &cur[0]));
       const u64* pk = fr_layer_ptr(g, 0, k + 1);
       const u64* qk = fr_layer_ptr(g, 1, k + 1);
       const u64* in[5] = {cur[0].get(), qk, qk + len, nt == 5 ? pk : nullptr, nt == 5 ? pk + len : nullptr};
-      u64 r_prev = 0, e[4];
-      for (int j = 0; j <= k - te; ++j) {
-        const bool fold = j > 0;
-        const int log_in = fold ? k - j + 1 : k;
-        const size_t n_units = (size_t)1 << (k - j - 1);
+      u64 e[4];
+      SC_TRY((device_rounds<5, 1, 2>(ctx, nt, k, te, in, cur, rs.data(), e, &rc, [&](const DeviceRound& d, Launched* l) {
+        const bool fold = d.round > 0;
         sc::FrTables ft;
         for (int q = 0; q < 5; ++q) {
-          ft.in[q] = q < nt ? in[q] : nullptr;
-          ft.out[q] = nullptr;
-          if (fold && q < nt) {
-            SC_TRY(nxt[q].alloc(ctx, (size_t)2 * n_units));
-            ft.out[q] = nxt[q].get();
-          }
+          ft.in[q] = q < nt ? d.in[q] : nullptr;
+          ft.out[q] = d.out[q];
         }
-        const int grid = (int)std::max<size_t>(1, std::min<size_t>((n_units + sc::kBlock - 1) / sc::kBlock, (size_t)resident));
-        bool mb = false;
-        const sc::PassOut po = next_pass_out(ctx, false, 0, &mb);
-        SC_TRY(timer_begin(ctx, SC_KIND_FRACTION_PASS, fold ? 1 : 0, nt, log_in, (u64)(8 * nt) << log_in, fold ? (u64)(8 * nt) << (log_in - 1) : 0));
+        *l = {d.grid(resident), 4};
+        SC_TRY(timer_begin(ctx, SC_KIND_FRACTION_PASS, fold ? 1 : 0, nt, d.log_in, (u64)(8 * nt) << d.log_in, fold ? (u64)(8 * nt) << (d.log_in - 1) : 0));
         SC_DISPATCH_FIELD(ctx, F, f, with_bool(fold, [&](auto FOLD) {
           with_bool(nt == 3, [&](auto ONES) {
-            hipLaunchKernelGGL((sc::fr_pass_kernel<F, FOLD, ONES>), dim3(grid), dim3(sc::kBlock), 0, ctx->stream, f, ft, r_prev, lambda, n_units, po);
+            hipLaunchKernelGGL((sc::fr_pass_kernel<F, FOLD, ONES>), dim3(l->grid), dim3(sc::kBlock), 0, ctx->stream, f, ft, d.r_prev[0], lambda, d.n_units,
+                               d.po);
           });
         }));
-        SC_TRY(commit_pass_out(ctx, po, grid));
-        SC_TRY(timer_end(ctx));
-        if (fold)
-          for (int q = 0; q < nt; ++q) {
-            cur[q] = std::move(nxt[q]);   // (the tables of round j - 1 go back: the launch that reads them is queued)
-            in[q] = cur[q].get();
-          }
-        SC_TRY(collect_sums(ctx, 4, false, mb, e));
-        if (j == k - te) break;   // the host draws this round's challenge
-        if (!next((size_t)j, e, &r_prev)) return rc;
-        rs[(size_t)j] = r_prev;
-      }
+        return SC_OK;
+      }, next)));
       const size_t left = (size_t)1 << te;
       for (int q = 0; q < nt; ++q) {
         host[q].resize(left);

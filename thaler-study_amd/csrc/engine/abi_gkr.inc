@@ -601,7 +601,7 @@ static int run_rounds(sc_ctx* ctx, P* pr, size_t num_vars, RoundFn round, sc_dra
     u64 e[3];
     SC_TRY(round(pr, r_j, j, e));
     if (evals) memcpy(evals + 3 * j, e, sizeof(e));
-    r_j = draw ? draw(user, j, e) : hf.mul(sc::splitmix64(seed_r + j + 1) % ctx->fp.p, ctx->fp.r2_mod_p);
+    r_j = draw ? draw(user, j, e) : seeded_challenge(ctx, hf, seed_r, j);
     if (r_j >= ctx->fp.p) return fail(ctx, SC_ERR_ARG, "draw() returned an unreduced challenge");
     if (challenges) challenges[j] = r_j;
   }

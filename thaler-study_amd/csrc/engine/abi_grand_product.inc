@@ -19,78 +19,50 @@ int check_gp(sc_ctx* ctx, const sc_gp* g, const char* what) {
 // layer k of the tree, 0 <= k <= n
 const u64* gp_layer_ptr(const sc_gp* g, int k) { return k == g->n ? g->t->d : g->tree.get() + ((size_t)1 << k); }
 
-// the launches of the tree: from layer n, up to kGpTreeLv layers per launch down to layer kGpTailLog, then the tail kernel
+// the launches of the tree (tree_schedule): gp_tree_kernel from layer m over lv layers, gp_tree_tail_kernel below layer kGpTailLog
 int gp_build_tree(sc_ctx* ctx, sc_gp* g, int tree_lv) {
-  int m = g->n;
   u64* const tree = g->tree.get();
-  while (m > sc::kGpTailLog) {
-    const int lv = std::min(tree_lv, m - sc::kGpTailLog);
+  return tree_schedule(g->n, sc::kGpTailLog, tree_lv, [&](int m, int lv) {
     const u64* src = gp_layer_ptr(g, m);
+    if (lv == 0)
+      return launch_recorded(ctx, {SC_KIND_PRODUCT_TREE, 0, 0, m, (u64)8 << m, ((u64)8 << m) - 8}, "gp_tree_tail_kernel", [&] {
+        SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::gp_tree_tail_kernel<F>), dim3(1), dim3(sc::kBlock), 0, ctx->stream, f, src, tree, m));
+      });
     const int log_low = m - lv;
     const size_t n_units = (size_t)1 << (log_low - 1);
     const int grid = grid_for(ctx, n_units);
-    SC_TRY(launch_recorded(ctx, {SC_KIND_PRODUCT_TREE, lv, 0, m, (u64)8 << m, ((u64)8 << m) - ((u64)8 << log_low)}, "gp_tree_kernel", [&] {
+    return launch_recorded(ctx, {SC_KIND_PRODUCT_TREE, lv, 0, m, (u64)8 << m, ((u64)8 << m) - ((u64)8 << log_low)}, "gp_tree_kernel", [&] {
       SC_DISPATCH_FIELD(ctx, F, f, with_const<1, 2, 3>(lv, [&](auto LV) {
         hipLaunchKernelGGL((sc::gp_tree_kernel<F, LV>), dim3(grid), dim3(sc::kBlock), 0, ctx->stream, f, src, tree, log_low, n_units);
       }));
-    }));
-    m = log_low;
-  }
-  const u64* src = gp_layer_ptr(g, m);
-  return launch_recorded(ctx, {SC_KIND_PRODUCT_TREE, 0, 0, m, (u64)8 << m, ((u64)8 << m) - 8}, "gp_tree_tail_kernel", [&] {
-    SC_DISPATCH_FIELD(ctx, F, f, hipLaunchKernelGGL((sc::gp_tree_tail_kernel<F>), dim3(1), dim3(sc::kBlock), 0, ctx->stream, f, src, tree, m));
+    });
   });
 }
 
-// The device rounds of a cubic sumcheck over three tables of 2^k entries, k > te >= 1 (gp_pass_kernel, one launch per round,
-// SC_KIND_PRODUCT_PASS): rounds 0 .. k - te - 1 are completed - next(round, H(0..3), &c) draws, rs[round] receives c - and the
-// launch of round k - te leaves its four values in e and tables of 2^te entries at in[.], which the host takes.  in[.]: the tables
-// of round 0, never written; cur[.] owns every folded table (a block cur[q] holds on entry, the eq table of a layer, is given back
-// as that one was).  next() returning false ends the call with *stopped.
+// The device rounds of a cubic sumcheck over three tables of 2^k entries (device_rounds with gp_pass_kernel, SC_KIND_PRODUCT_PASS,
+// four values per round); in, cur, rs, e, stopped and next as there
 template <class Next>
 int gp_device_rounds(sc_ctx* ctx, int k, int te, int resident, const u64* (&in)[3], PoolBuf (&cur)[3], u64* rs, u64 (&e)[4], const int* stopped,
                      Next&& next) {
-  PoolBuf nxt[3];
-  u64 r_prev = 0;
-  for (int j = 0; j <= k - te; ++j) {
-    const bool fold = j > 0;
-    const int log_in = fold ? k - j + 1 : k;
-    const size_t n_units = (size_t)1 << (k - j - 1);
+  return device_rounds<3, 1, 2>(ctx, 3, k, te, in, cur, rs, e, stopped, [&](const DeviceRound& d, Launched* l) {
+    const bool fold = d.round > 0;
     sc::GpTables tb;
     for (int q = 0; q < 3; ++q) {
-      tb.in[q] = in[q];
-      tb.out[q] = nullptr;
-      if (fold) {
-        SC_TRY(nxt[q].alloc(ctx, (size_t)2 * n_units));
-        tb.out[q] = nxt[q].get();
-      }
+      tb.in[q] = d.in[q];
+      tb.out[q] = d.out[q];
     }
-    const int grid = (int)std::max<size_t>(1, std::min<size_t>((n_units + sc::kBlock - 1) / sc::kBlock, (size_t)resident));
-    bool mb = false;
-    const sc::PassOut po = next_pass_out(ctx, false, 0, &mb);
-    SC_TRY(timer_begin(ctx, SC_KIND_PRODUCT_PASS, fold ? 1 : 0, 1, log_in, (u64)24 << log_in, fold ? (u64)24 << (log_in - 1) : 0));
+    *l = {d.grid(resident), 4};
+    SC_TRY(timer_begin(ctx, SC_KIND_PRODUCT_PASS, fold ? 1 : 0, 1, d.log_in, (u64)24 << d.log_in, fold ? (u64)24 << (d.log_in - 1) : 0));
     SC_DISPATCH_FIELD(ctx, F, f, with_bool(fold, [&](auto FOLD) {
-      hipLaunchKernelGGL((sc::gp_pass_kernel<F, FOLD>), dim3(grid), dim3(sc::kBlock), 0, ctx->stream, f, tb, r_prev, n_units, po);
+      hipLaunchKernelGGL((sc::gp_pass_kernel<F, FOLD>), dim3(l->grid), dim3(sc::kBlock), 0, ctx->stream, f, tb, d.r_prev[0], d.n_units, d.po);
     }));
-    SC_TRY(commit_pass_out(ctx, po, grid));
-    SC_TRY(timer_end(ctx));
-    if (fold)
-      for (int q = 0; q < 3; ++q) {
-        cur[q] = std::move(nxt[q]);   // (the tables of round j - 1 go back: the launch that reads them is queued)
-        in[q] = cur[q].get();
-      }
-    SC_TRY(collect_sums(ctx, 4, false, mb, e));
-    if (j == k - te) break;   // the host draws this round's challenge
-    if (!next((size_t)j, e, &r_prev)) return *stopped;
-    rs[(size_t)j] = r_prev;
-  }
-  return SC_OK;
+    return SC_OK;
+  }, next);
 }
 
 // how many blocks of gp_pass_kernel the device holds at once
 int gp_pass_resident(sc_ctx* ctx) {
-  const void* fn = ctx->gold ? kernel_ptr(&sc::gp_pass_kernel<sc::GoldilocksMont, true>) : kernel_ptr(&sc::gp_pass_kernel<sc::MontGeneric, true>);
-  return std::min(resident_grid(ctx, fn, sc::kBlock, ctx->max_blocks), ctx->max_blocks);
+  return resident_blocks(ctx, &sc::gp_pass_kernel<sc::GoldilocksMont, true>, &sc::gp_pass_kernel<sc::MontGeneric, true>);
 }
 
 }  // namespace
@@ -98,8 +70,7 @@ int gp_pass_resident(sc_ctx* ctx) {
 extern "C" int sc_gp_create(sc_ctx* ctx, const sc_table* t, sc_gp** out) {
   if (!ctx) return SC_ERR_ARG;
   SC_TRY(one_device_only(ctx, "sc_gp_create"));
-  if (ctx->fp.p <= 3) return fail(ctx, SC_ERR_UNSUPPORTED, "sc_gp_create: p = %llu: a cubic through 0, 1, 2, 3 needs 2 and 3 invertible",
-                                  (unsigned long long)ctx->fp.p);
+  SC_TRY(require_cubic_field(ctx, "sc_gp_create"));
   if (!t || !out) return fail(ctx, SC_ERR_ARG, "sc_gp_create: a NULL argument");
   SC_TRY(check_table(ctx, t, "sc_gp_create"));
   if (t->len < 2 || t->len > ((size_t)1 << sc::kGpMaxLog))
@@ -148,8 +119,7 @@ extern "C" int sc_gp_prove(sc_ctx* ctx, const sc_gp* g, sc_draw_gp_fn draw, void
                            uint64_t* challenges, uint64_t* point, uint64_t* claim) {
   if (!ctx) return SC_ERR_ARG;
   SC_TRY(one_device_only(ctx, "sc_gp_prove"));
-  if (ctx->fp.p <= 3) return fail(ctx, SC_ERR_UNSUPPORTED, "sc_gp_prove: p = %llu: a cubic through 0, 1, 2, 3 needs 2 and 3 invertible",
-                                  (unsigned long long)ctx->fp.p);
+  SC_TRY(require_cubic_field(ctx, "sc_gp_prove"));
   if (!finals || !point || !claim) return fail(ctx, SC_ERR_ARG, "sc_gp_prove: a NULL argument");
   SC_TRY(check_gp(ctx, g, "sc_gp_prove"));
   SC_TRY(set_device(ctx));
@@ -172,7 +142,7 @@ extern "C" int sc_gp_prove(sc_ctx* ctx, const sc_gp* g, sc_draw_gp_fn draw, void
   u64 n_draws = 0;
   int rc = SC_OK;
   auto challenge = [&](size_t layer, size_t round, const u64* msg, u64* out) {
-    const u64 c = draw ? draw(user, layer, round, msg) : hf.mul(sc::splitmix64(seed_r + n_draws + 1) % ctx->fp.p, ctx->fp.r2_mod_p);
+    const u64 c = draw ? draw(user, layer, round, msg) : seeded_challenge(ctx, hf, seed_r, n_draws);
     n_draws += 1;
     if (c >= ctx->fp.p) {
       rc = fail(ctx, SC_ERR_ARG, "sc_gp_prove: draw() returned an unreduced challenge");

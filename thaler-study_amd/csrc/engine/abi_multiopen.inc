@@ -5,64 +5,21 @@ namespace {
 
 // how many blocks of sumprod_pass_kernel the device holds at once (the occupancy does not depend on T: the loop over t is not unrolled)
 int sumprod_pass_resident(sc_ctx* ctx) {
-  const void* fn = ctx->gold ? kernel_ptr(&sc::sumprod_pass_kernel<sc::GoldilocksMont, sc::kSumprodMaxPairs, true>)
-                             : kernel_ptr(&sc::sumprod_pass_kernel<sc::MontGeneric, sc::kSumprodMaxPairs, true>);
-  return std::min(resident_grid(ctx, fn, sc::kBlock, ctx->max_blocks), ctx->max_blocks);
+  return resident_blocks(ctx, &sc::sumprod_pass_kernel<sc::GoldilocksMont, sc::kSumprodMaxPairs, true>,
+                         &sc::sumprod_pass_kernel<sc::MontGeneric, sc::kSumprodMaxPairs, true>);
 }
 
-// The device rounds of the sumcheck over sum_t a_t b_t, tables of 2^n entries, n > te >= 1 (sumprod_pass_kernel, one launch per
-// round, SC_KIND_SUMPROD_PASS): rounds 0 .. n - te - 1 are completed - next(round, H(0..2), &c) draws, rs[round] receives c - and
-// the launch of round n - te leaves its three values in e and tables of 2^te entries at in[.], which the host takes.  in[.]: the 2T
-// tables of round 0 (a_0 .. a_(T-1), b_0 .. b_(T-1)), never written; cur[.] owns every folded table.  next() returning false ends
-// the call with *stopped.
-template <class Next>
-int sumprod_device_rounds(sc_ctx* ctx, int T, int n, int te, const u64** in, PoolBuf* cur, u64* rs, u64 (&e)[3], const int* stopped, Next&& next) {
-  PoolBuf nxt[2 * sc::kSumprodMaxPairs];
-  const int resident = sumprod_pass_resident(ctx);
-  u64 r_prev = 0;
-  for (int j = 0; j <= n - te; ++j) {
-    const bool fold = j > 0;
-    const int log_in = fold ? n - j + 1 : n;
-    const size_t n_units = (size_t)1 << (n - j - 1);
-    sc::SpTables tb;
-    memset(&tb, 0, sizeof(tb));
-    for (int q = 0; q < 2 * T; ++q) {
-      u64* o = nullptr;
-      if (fold) {
-        SC_TRY(nxt[q].alloc(ctx, (size_t)2 * n_units));
-        o = nxt[q].get();
-      }
-      if (q < T) {
-        tb.a[q] = in[q];
-        tb.ao[q] = o;
-      } else {
-        tb.b[q - T] = in[q];
-        tb.bo[q - T] = o;
-      }
-    }
-    const int grid = (int)std::max<size_t>(1, std::min<size_t>((n_units + sc::kBlock - 1) / sc::kBlock, (size_t)resident));
-    bool mb = false;
-    const sc::PassOut po = next_pass_out(ctx, false, 0, &mb);
-    const u64 bytes = ((u64)16 * (u64)T) << log_in;
-    SC_TRY(timer_begin(ctx, SC_KIND_SUMPROD_PASS, fold ? 1 : 0, T, log_in, bytes, fold ? bytes / 2 : 0));
-    SC_DISPATCH_FIELD(ctx, F, f, with_bool(fold, [&](auto FOLD) {
-      with_const<1, 2, 3, 4, 5, 6, 7, 8>(T, [&](auto TT) {
-        hipLaunchKernelGGL((sc::sumprod_pass_kernel<F, TT, FOLD>), dim3(grid), dim3(sc::kBlock), 0, ctx->stream, f, tb, r_prev, n_units, po);
-      });
-    }));
-    SC_TRY(commit_pass_out(ctx, po, grid));
-    SC_TRY(timer_end(ctx));
-    if (fold)
-      for (int q = 0; q < 2 * T; ++q) {
-        cur[q] = std::move(nxt[q]);   // (the tables of round j - 1 go back: the launch that reads them is queued)
-        in[q] = cur[q].get();
-      }
-    SC_TRY(collect_sums(ctx, 3, false, mb, e));
-    if (j == n - te) break;   // the host draws this round's challenge
-    if (!next((size_t)j, e, &r_prev)) return *stopped;
-    rs[(size_t)j] = r_prev;
+// the 2T tables of a device round (a_0 .. a_(T-1), b_0 .. b_(T-1)) as the sum-of-products kernels take them
+sc::SpTables sumprod_tables(const DeviceRound& d, int T) {
+  sc::SpTables tb;
+  memset(&tb, 0, sizeof(tb));
+  for (int t = 0; t < T; ++t) {
+    tb.a[t] = d.in[t];
+    tb.ao[t] = d.out[t];
+    tb.b[t] = d.in[T + t];
+    tb.bo[t] = d.out[T + t];
   }
-  return SC_OK;
+  return tb;
 }
 
 }  // namespace
@@ -123,7 +80,7 @@ extern "C" int sc_sumprod_prove(sc_ctx* ctx, size_t count, const sc_table* const
   auto next = [&](size_t round, const u64* msg, u64* out) {
     if (round == 0) *c1 = hf.add(msg[0], msg[1]);
     if (evals) memcpy(evals + 3 * round, msg, 3 * sizeof(u64));
-    const u64 r = draw ? draw(user, round, msg) : hf.mul(sc::splitmix64(seed_r + (u64)round + 1) % ctx->fp.p, ctx->fp.r2_mod_p);
+    const u64 r = draw ? draw(user, round, msg) : seeded_challenge(ctx, hf, seed_r, round);
     if (r >= ctx->fp.p) {
       rc = fail(ctx, SC_ERR_ARG, "sc_sumprod_prove: draw() returned an unreduced challenge");
       return false;
@@ -147,7 +104,23 @@ extern "C" int sc_sumprod_prove(sc_ctx* ctx, size_t count, const sc_table* const
     hb[t] = host.data() + (size_t)(T + t) * left;
   }
   u64 e[3];
-  if (n > te) SC_TRY(sumprod_device_rounds(ctx, T, n, te, in, cur, rs.data(), e, &rc, next));
+  if (n > te) {
+    // one launch of sumprod_pass_kernel per round (SC_KIND_SUMPROD_PASS), three values each
+    const int resident = sumprod_pass_resident(ctx);
+    SC_TRY((device_rounds<2 * sc::kSumprodMaxPairs, 1, 2>(ctx, 2 * T, n, te, in, cur, rs.data(), e, &rc, [&](const DeviceRound& d, Launched* l) {
+      const bool fold = d.round > 0;
+      const sc::SpTables tb = sumprod_tables(d, T);
+      const u64 bytes = ((u64)16 * (u64)T) << d.log_in;
+      *l = {d.grid(resident), 3};
+      SC_TRY(timer_begin(ctx, SC_KIND_SUMPROD_PASS, fold ? 1 : 0, T, d.log_in, bytes, fold ? bytes / 2 : 0));
+      SC_DISPATCH_FIELD(ctx, F, f, with_bool(fold, [&](auto FOLD) {
+        with_const<1, 2, 3, 4, 5, 6, 7, 8>(T, [&](auto TT) {
+          hipLaunchKernelGGL((sc::sumprod_pass_kernel<F, TT, FOLD>), dim3(l->grid), dim3(sc::kBlock), 0, ctx->stream, f, tb, d.r_prev[0], d.n_units, d.po);
+        });
+      }));
+      return SC_OK;
+    }, next)));
+  }
   for (int q = 0; q < 2 * T; ++q)
     SC_HIP(ctx, hipMemcpyAsync(host.data() + (size_t)q * left, in[q], left * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
   SC_HIP(ctx, sync_stream(ctx));

@@ -915,8 +915,7 @@ extern "C" int sc_prove(sc_ctx* ctx, const sc_table* a, const sc_table* b, sc_dr
     rc = sc_prover_round(pr, r_j, j, e);
     if (rc != SC_OK) break;
     if (evals) memcpy(evals + 3 * j, e, sizeof(e));
-    r_j = draw ? draw(user, j, e)
-               : hf.mul(sc::splitmix64(seed_r + j + 1) % ctx->fp.p, ctx->fp.r2_mod_p);
+    r_j = draw ? draw(user, j, e) : seeded_challenge(ctx, hf, seed_r, j);
     if (r_j >= ctx->fp.p) {
       rc = fail(ctx, SC_ERR_ARG, "sc_prove: draw() returned an unreduced challenge");
       break;

@@ -174,8 +174,7 @@ extern "C" int sc_zerocheck_prove(sc_ctx* ctx, const sc_table* a, const sc_table
   if (!ctx) return SC_ERR_ARG;
   if (!tau || !c1 || !finals) return fail(ctx, SC_ERR_ARG, "sc_zerocheck_prove: a NULL argument");
   SC_TRY(one_device_only(ctx, "sc_zerocheck_prove"));
-  if (ctx->fp.p <= 3) return fail(ctx, SC_ERR_UNSUPPORTED, "sc_zerocheck_prove: p = %llu: a cubic through 0, 1, 2, 3 needs 2 and 3 invertible",
-                                  (unsigned long long)ctx->fp.p);
+  SC_TRY(require_cubic_field(ctx, "sc_zerocheck_prove"));
   SC_TRY(check_table(ctx, a, "sc_zerocheck_prove"));
   SC_TRY(check_table(ctx, b, "sc_zerocheck_prove"));
   SC_TRY(check_table(ctx, c, "sc_zerocheck_prove"));
@@ -185,54 +184,48 @@ extern "C" int sc_zerocheck_prove(sc_ctx* ctx, const sc_table* a, const sc_table
   for (int i = 0; i < s; ++i)
     if (tau[i] >= ctx->fp.p) return fail(ctx, SC_ERR_ARG, "sc_zerocheck_prove: tau[%d] is not a word below p", i);
   SC_TRY(set_device(ctx));
-  HostField hf(ctx->fp);
-  PoolBuf cur[4], nxt[4];
+  const HostField hf(ctx->fp);
+  int rc = SC_OK;
+  auto next = [&](size_t round, const u64* msg, u64* out) {
+    if (round == 0) *c1 = hf.add(msg[0], msg[1]);
+    if (evals) memcpy(evals + 4 * round, msg, 4 * sizeof(u64));
+    const u64 r = draw ? draw(user, round, msg) : seeded_challenge(ctx, hf, seed_r, round);
+    if (r >= ctx->fp.p) {
+      rc = fail(ctx, SC_ERR_ARG, "sc_zerocheck_prove: draw() returned an unreduced challenge");
+      return false;
+    }
+    *out = r;
+    return true;
+  };
+  PoolBuf cur[4];
   SC_TRY(build_eq_table(ctx, tau, s, &cur[0]));
   const u64* in[4] = {cur[0].get(), a->d, b->d, c->d};
-  const void* fn = ctx->gold ? kernel_ptr(&sc::zc_pass_kernel<sc::GoldilocksMont, true>) : kernel_ptr(&sc::zc_pass_kernel<sc::MontGeneric, true>);
-  const int resident = std::min(resident_grid(ctx, fn, sc::kBlock, ctx->max_blocks), ctx->max_blocks);
-  u64 r_prev = 0;
-  for (int j = 0; j < s; ++j) {
-    // round j: tables of 2^(s-j) entries - read folded from those of round j - 1 (twice as long) for j > 0
-    const bool fold = j > 0;
-    const int log_in = fold ? s - j + 1 : s;
-    const size_t n_units = (size_t)1 << (s - j - 1);
+  const int resident = resident_blocks(ctx, &sc::zc_pass_kernel<sc::GoldilocksMont, true>, &sc::zc_pass_kernel<sc::MontGeneric, true>);
+  // every round on the device: the launch of round s - 1 leaves its message and tables of two entries
+  u64 own[64];   // (s < 64: a table has 2^s words)
+  u64* const rs = challenges ? challenges : own;
+  u64 e[4];
+  SC_TRY((device_rounds<4, 1, 2>(ctx, 4, s, 1, in, cur, rs, e, &rc, [&](const DeviceRound& d, Launched* l) {
+    const bool fold = d.round > 0;
     sc::ZcTables tb;
     for (int k = 0; k < 4; ++k) {
-      tb.in[k] = in[k];
-      tb.out[k] = nullptr;
-      if (fold) {
-        SC_TRY(nxt[k].alloc(ctx, (size_t)2 * n_units));
-        tb.out[k] = nxt[k].get();
-      }
+      tb.in[k] = d.in[k];
+      tb.out[k] = d.out[k];
     }
-    const int grid = (int)std::max<size_t>(1, std::min<size_t>((n_units + sc::kBlock - 1) / sc::kBlock, (size_t)resident));
-    bool mb = false;
-    const sc::PassOut po = next_pass_out(ctx, false, 0, &mb);
-    SC_TRY(timer_begin(ctx, SC_KIND_ZEROCHECK, fold ? 1 : 0, 1, log_in, (u64)32 << log_in, fold ? (u64)32 << (log_in - 1) : 0));
+    *l = {d.grid(resident), 4};
+    SC_TRY(timer_begin(ctx, SC_KIND_ZEROCHECK, fold ? 1 : 0, 1, d.log_in, (u64)32 << d.log_in, fold ? (u64)32 << (d.log_in - 1) : 0));
     SC_DISPATCH_FIELD(ctx, F, f, with_bool(fold, [&](auto FOLD) {
-      hipLaunchKernelGGL((sc::zc_pass_kernel<F, FOLD>), dim3(grid), dim3(sc::kBlock), 0, ctx->stream, f, tb, r_prev, n_units, po);
+      hipLaunchKernelGGL((sc::zc_pass_kernel<F, FOLD>), dim3(l->grid), dim3(sc::kBlock), 0, ctx->stream, f, tb, d.r_prev[0], d.n_units, d.po);
     }));
-    SC_TRY(commit_pass_out(ctx, po, grid));
-    SC_TRY(timer_end(ctx));
-    if (fold)
-      for (int k = 0; k < 4; ++k) {
-        cur[k] = std::move(nxt[k]);   // (the tables of round j - 1 go back: the launch that reads them is queued)
-        in[k] = cur[k].get();
-      }
-    u64 e[4];
-    SC_TRY(collect_sums(ctx, 4, false, mb, e));
-    if (j == 0) *c1 = hf.add(e[0], e[1]);
-    if (evals) memcpy(evals + 4 * (size_t)j, e, sizeof(e));
-    const u64 r_j = draw ? draw(user, (size_t)j, e) : hf.mul(sc::splitmix64(seed_r + (u64)j + 1) % ctx->fp.p, ctx->fp.r2_mod_p);
-    if (r_j >= ctx->fp.p) return fail(ctx, SC_ERR_ARG, "sc_zerocheck_prove: draw() returned an unreduced challenge");
-    if (challenges) challenges[j] = r_j;
-    r_prev = r_j;
-  }
+    return SC_OK;
+  }, next)));
+  u64 r_last = 0;
+  if (!next((size_t)s - 1, e, &r_last)) return rc;
+  rs[(size_t)s - 1] = r_last;
   // the two entries left of A, B, C, folded by the last challenge on the host
   u64 last[3][2];
   for (int k = 0; k < 3; ++k) SC_HIP(ctx, hipMemcpyAsync(last[k], in[k + 1], 2 * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
   SC_HIP(ctx, sync_stream(ctx));
-  for (int k = 0; k < 3; ++k) finals[k] = hf.add(last[k][0], hf.mul(r_prev, hf.sub(last[k][1], last[k][0])));
+  for (int k = 0; k < 3; ++k) finals[k] = hf.add(last[k][0], hf.mul(r_last, hf.sub(last[k][1], last[k][0])));
   return SC_OK;
 }

@@ -70,6 +70,7 @@ extern "C" int sc_spark_create(sc_ctx* ctx, size_t log_rows, size_t log_cols, co
   if (nnz < 1 || nnz > ((size_t)1 << sc::kSparkMaxLog))
     return fail(ctx, SC_ERR_ARG, "sc_spark_create: %zu entries (at least one, at most 2^%d)", nnz, sc::kSparkMaxLog);
   const int a = (int)log_rows, b = (int)log_cols, l = sc::spark_log_len(nnz), top = std::max(l, std::max(a, b));
+  // (not require_cubic_field: one refusal, with one text, for both bounds on p)
   if (ctx->fp.p <= 3 || ctx->fp.p <= ((u64)1 << top))
     return fail(ctx, SC_ERR_UNSUPPORTED, "sc_spark_create: p = %llu: indices and counts of up to 2^%d must be field words, and a cubic through 0, 1, 2, 3 "
                 "needs 2 and 3 invertible", (unsigned long long)ctx->fp.p, top);
@@ -182,8 +183,7 @@ extern "C" int sc_product3_prove(sc_ctx* ctx, const sc_table* a, const sc_table*
                                  uint64_t* c1, uint64_t* evals, uint64_t* challenges, uint64_t finals[3]) {
   if (!ctx) return SC_ERR_ARG;
   SC_TRY(one_device_only(ctx, "sc_product3_prove"));
-  if (ctx->fp.p <= 3) return fail(ctx, SC_ERR_UNSUPPORTED, "sc_product3_prove: p = %llu: a cubic through 0, 1, 2, 3 needs 2 and 3 invertible",
-                                  (unsigned long long)ctx->fp.p);
+  SC_TRY(require_cubic_field(ctx, "sc_product3_prove"));
   if (!c1 || !finals) return fail(ctx, SC_ERR_ARG, "sc_product3_prove: a NULL argument");
   SC_TRY(check_table(ctx, a, "sc_product3_prove"));
   SC_TRY(check_table(ctx, b, "sc_product3_prove"));
@@ -200,7 +200,7 @@ extern "C" int sc_product3_prove(sc_ctx* ctx, const sc_table* a, const sc_table*
   auto next = [&](size_t round, const u64* msg, u64* out) {
     if (round == 0) *c1 = hf.add(msg[0], msg[1]);
     if (evals) memcpy(evals + 4 * round, msg, 4 * sizeof(u64));
-    const u64 r = draw ? draw(user, round, msg) : hf.mul(sc::splitmix64(seed_r + (u64)round + 1) % ctx->fp.p, ctx->fp.r2_mod_p);
+    const u64 r = draw ? draw(user, round, msg) : seeded_challenge(ctx, hf, seed_r, round);
     if (r >= ctx->fp.p) {
       rc = fail(ctx, SC_ERR_ARG, "sc_product3_prove: draw() returned an unreduced challenge");
       return false;

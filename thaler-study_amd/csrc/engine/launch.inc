@@ -72,6 +72,12 @@ u64 eval2_from_inf(const HostField& hf, u64 e0, u64 e1, u64 einf) {
   return hf.sub(hf.add(t, t), e0);
 }
 
+// the synthetic challenger of a call with draw == NULL: word `index` of the sequence under seed_r, a Montgomery word (a challenge
+// of two words takes the indices 2 i and 2 i + 1)
+u64 seeded_challenge(const sc_ctx* ctx, const HostField& hf, u64 seed_r, u64 index) {
+  return hf.mul(sc::splitmix64(seed_r + index + 1) % ctx->fp.p, ctx->fp.r2_mod_p);
+}
+
 // add the durations of the recorded launches to the totals (waits for the last of them)
 void drain_kernel_timers(sc_ctx* ctx) {
   if (ctx->kt_used == 0) return;

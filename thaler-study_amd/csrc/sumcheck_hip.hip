@@ -614,6 +614,7 @@ static int multi_prod2_fold_and_sums(sc_ctx* m, const sc_table* a, const sc_tabl
 #include "engine/abi_expander.inc"   // the expander row code
 #include "engine/abi_row_code.inc"   // the table of both, and the entry points that encode and commit through it
 #include "engine/abi_fold.inc"       // folded openings of a Reed-Solomon commitment
+#include "engine/rounds.inc"         // what the round-per-launch sumchecks below share: the driver of their device rounds, the tree schedule
 #include "engine/abi_r1cs.inc"       // rank-1 constraint systems: sparse products and the cubic sumcheck
 #include "engine/abi_grand_product.inc"   // the grand product argument: product tree and layered cubic sumcheck
 #include "engine/abi_fraction.inc"        // LogUp lookups: fraction-sum trees, their layered cubic sumcheck, the multiplicities
