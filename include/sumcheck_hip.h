@@ -159,7 +159,8 @@ const char* sc_last_error(const sc_ctx* ctx);
  *                      of <= 2^fr_host_log entries are proven on the host from one copy of the bottom of both trees, and in every
  *                      larger layer the launch that writes tables of 2^fr_host_log entries is the last one.  Same transcript at
  *                      every value.  "fr_tree_lv" (default 3; 1..3): tree layers per launch of sc_frac_create above its one-block
- *                      tail.  DESIGN.md section 9 item 17
+ *                      tail.  DESIGN.md section 9 item 17.  sc_frac_prove_ext and sc_frac_create_ext (item 22) follow both options
+ *                      over their four heaps; the one-block tail of their trees takes layers of <= 2^10 entries
  *   "grid_pass"        the passes whose FOLDED tables have <= 2^"grid_log" (default 20) entries serve up to
  *                      "grid_max_vars" (default 5) rounds each and fold up to five pending challenges at once
  *                      (wgrid_pass_kernel); "grid_blocks" caps the launch (0 = what fits on the chip at once).
@@ -322,6 +323,19 @@ int sc_ctx_kernel_time(sc_ctx* ctx, double out[2], int reset);
                                  * written with kf = 1 */
 #define SC_KIND_EXT_EQ_TABLE 41  /* ext_eq_table_kernel: eq(z, .) of a layer of sc_gp_prove_ext, z in K^k; log_in = k; reads the 2 k words
                                  * of the point, writes both planes, 16 * 2^k */
+#define SC_KIND_EXT_FRACTION_TREE 42 /* a launch of sc_frac_create_ext from layer m = log_in of the fraction trees over K: kf = LV = 1..3,
+                                 * ext_fr_tree_kernel<F, LV, LEAF_IN, ONES>; ks = the planes or base tables it read: 1 (m = n, all-ones
+                                 * numerator: t), 2 (m = n: t and p), else 4 (the four planes of layer m); it reads ks * 8 * 2^m bytes and
+                                 * writes the four planes of the layers m-1 .. m-LV, 32 * (2^m - 2^(m-LV)); kf = 0,
+                                 * ext_fr_tree_tail_kernel, one block from a layer of <= 2^10 entries down to the root: 32 * (2^m - 1)
+                                 * written */
+#define SC_KIND_EXT_FRACTION_PASS 43 /* ext_fr_pass_kernel: one round of a layer of sc_frac_prove_ext; kf = 1 if it folded the previous
+                                 * challenge; ks = the words per entry of L and R it read: 2 (layer n - 1, all-ones numerator: the
+                                 * halves of t as base words), 4 (layer n - 1: the halves of t and p; or QL, QR in planes under an
+                                 * all-ones numerator), 8 (QL, QR, PL, PR in planes); log_in = log2 of the entries per table it read:
+                                 * 16 * 2^log_in bytes of E plus ks * 8 * 2^log_in read, and with kf = 1 both planes of every folded
+                                 * table written: 80 * 2^(log_in - 1) with five tables, 48 * 2^(log_in - 1) with three.  The eq table
+                                 * of a layer is a SC_KIND_EXT_EQ_TABLE record */
 typedef struct sc_launch_record {
   int32_t kind;           /* SC_KIND_* */
   int32_t kf, ks;         /* variables folded / rounds served (meaning per kind above) */
@@ -941,6 +955,41 @@ typedef void (*sc_draw_gp_ext_fn)(void* user, size_t layer, size_t round, const 
  * transcript is the same at every value of the option. */
 int sc_gp_prove_ext(sc_ctx* ctx, const sc_gp_ext* g, sc_draw_gp_ext_fn draw, void* user, uint64_t seed_r, uint64_t* evals, uint64_t* finals,
                     uint64_t* challenges, uint64_t* point, uint64_t* claim);
+
+/* ---- LogUp's fraction sums over K (kernels/ext_fraction.hpp states the protocol) ----
+ * The protocol of sc_frac_* with every element in K = F_p[X] / (X^2 - w).  The leaves are never stored: the denominators are
+ * q_i = beta + alpha t[i] for a base-field table t of 2^n entries, 1 <= n <= 28, and alpha, beta in K, alpha != 0; the numerators
+ * are a base-field table p embedded as (p_i, 0), or all ones (p == NULL: the top layer reads three tables, not five; its finals
+ * pl = pr = (1, 0); a_n must be (1, 0)).  The trees, the root, the round values, the challenges, the finals, the point and the
+ * claims are elements of K, two consecutive Montgomery words each.  One device and one rank (SC_ERR_UNSUPPORTED on a sharded
+ * context or a multi-device handle, before anything else is looked at); p <= 3 is SC_ERR_UNSUPPORTED; SC_ERR_ARG: a NULL argument,
+ * a tree of another context, tables of different lengths, of fewer than 2 or more than 2^28 entries, a layer k >= n, a bad w (as
+ * sc_sumprod_prove_ext), a component of alpha or beta that is not below p, alpha = (0, 0). */
+typedef struct sc_frac_ext sc_frac_ext;
+/* The trees over K (SC_KIND_EXT_FRACTION_TREE; option "fr_tree_lv" as in sc_frac_create): one pool block of 4 * 2^n words, the heaps
+ * p.c0, p.c1, q.c0, q.c1.  `p` (may be NULL) and `t` are borrowed until sc_frac_destroy_ext and never written. */
+int sc_frac_create_ext(sc_ctx* ctx, uint64_t w, const sc_table* p, const sc_table* t, const uint64_t alpha[2], const uint64_t beta[2],
+                       sc_frac_ext** out);
+int sc_frac_destroy_ext(sc_ctx* ctx, sc_frac_ext* g);
+/* out = (P.c0, P.c1, Q.c0, Q.c1) */
+int sc_frac_root_ext(const sc_frac_ext* g, uint64_t out[4]);
+/* copies of the two planes of layer k, k < n, of p (which = 0) or q (which = 1) as base tables of 2^k words (the c0 words, the c1
+ * words): new tables the caller frees */
+int sc_frac_layer_ext(sc_ctx* ctx, const sc_frac_ext* g, size_t k, int which, sc_table** c0, sc_table** c1);
+/* round < layer: msg = the eight words H(0).c0, H(0).c1, .., H(3).c1 of that round, out receives its challenge; round == layer:
+ * msg = the eight words of (pl, pr, ql, qr), out receives rho_layer; round == layer + 1: msg = NULL, out receives lambda of
+ * layer + 1 (not called after the last layer).  Both components below p. */
+typedef void (*sc_draw_frac_ext_fn)(void* user, size_t layer, size_t round, const uint64_t* msg, uint64_t out[2]);
+/* The n layers.  evals (may be NULL): 8 words per round, 8 k (k - 1) / 2 words before layer k; finals: 8 per layer, (pl, pr, ql, qr);
+ * challenges (2 (n (n-1) / 2 + 2 n - 1) words, may be NULL): two words each as they were drawn, in sc_frac_prove's order - rho_0,
+ * then per layer k >= 1 lambda_k, its rounds' challenges and rho_k; point: 2 n words, z_n; claims: four words, (a_n, b_n), so that
+ * p~(z_n) = a_n and t~(z_n) = (b_n - beta) / alpha.  draw == NULL: the synthetic challenger, draw number d = 0, 1, .. in that order
+ * being (to_mont(splitmix64(seed_r + 2 d + 1) mod p), to_mont(splitmix64(seed_r + 2 d + 2) mod p)).  A challenge with a component
+ * that is not below p ends the call with SC_ERR_ARG.  One eq table (SC_KIND_EXT_EQ_TABLE) and one launch per round
+ * (SC_KIND_EXT_FRACTION_PASS) for every layer above the hand-over to the host (option "fr_host_log", as in sc_frac_prove); the
+ * transcript is the same at every value of "fr_host_log", "fr_tree_lv" and "max_blocks". */
+int sc_frac_prove_ext(sc_ctx* ctx, const sc_frac_ext* g, sc_draw_frac_ext_fn draw, void* user, uint64_t seed_r, uint64_t* evals, uint64_t* finals,
+                      uint64_t* challenges, uint64_t* point, uint64_t claims[4]);
 
 /* ---- gkr_protocol::circuit::Circuit on the device, and the whole GKR prover over it ----------------------------------
  * A circuit lives on ONE context of one device and one rank: sharded contexts (world > 1) and multi-device handles get

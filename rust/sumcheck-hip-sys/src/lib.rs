@@ -123,6 +123,12 @@ pub struct sc_gp_ext {
     _private: [u8; 0],
 }
 
+/// the fraction-sum trees over the quadratic extension on the device (`sc_frac_create_ext`)
+#[repr(C)]
+pub struct sc_frac_ext {
+    _private: [u8; 0],
+}
+
 /// a pair of fraction-sum trees on the device (`sc_frac_create`)
 #[repr(C)]
 pub struct sc_frac {
@@ -153,6 +159,9 @@ pub type sc_draw_gp_ext_fn = Option<unsafe extern "C" fn(user: *mut c_void, laye
 /// `sc_frac_prove`: `round < layer`: `msg` = H(0..3), returns its challenge; `round == layer`: `msg` = (pl, pr, ql, qr), returns rho;
 /// `round == layer + 1`: `msg` is null, returns lambda of the next layer
 pub type sc_draw_frac_fn = Option<unsafe extern "C" fn(user: *mut c_void, layer: usize, round: usize, msg: *const u64) -> u64>;
+/// `sc_frac_prove_ext`: `round < layer`: `msg` = the eight words H(0).c0 .. H(3).c1, `out` = the challenge (c0, c1); `round == layer`:
+/// `msg` = (pl, pr, ql, qr), eight words, `out` = rho; `round == layer + 1`: `msg` is null, `out` = lambda of the next layer
+pub type sc_draw_frac_ext_fn = Option<unsafe extern "C" fn(user: *mut c_void, layer: usize, round: usize, msg: *const u64, out: *mut u64)>;
 /// `sc_prove_batch`: called round by round, within a round in instance order.
 pub type sc_draw_batch_fn = Option<unsafe extern "C" fn(user: *mut c_void, instance: usize, round: usize, evals: *const u64) -> u64>;
 
@@ -830,5 +839,36 @@ extern "C" {
         challenges: *mut u64,
         point: *mut u64,
         claim: *mut u64,
+    ) -> c_int;
+    /// the fraction-sum trees over K of the leaves (p[i], beta + alpha t[i]), p and t base tables of 2^n entries, 1 <= n <= 28
+    /// (SC_KIND_EXT_FRACTION_TREE, 42); `p` null: all ones; alpha, beta: two words each, alpha != 0; both tables are borrowed until
+    /// `sc_frac_destroy_ext`
+    pub fn sc_frac_create_ext(
+        ctx: *mut sc_ctx,
+        w: u64,
+        p: *const sc_table,
+        t: *const sc_table,
+        alpha: *const u64,
+        beta: *const u64,
+        out: *mut *mut sc_frac_ext,
+    ) -> c_int;
+    pub fn sc_frac_destroy_ext(ctx: *mut sc_ctx, g: *mut sc_frac_ext) -> c_int;
+    /// (P, Q), four words
+    pub fn sc_frac_root_ext(g: *const sc_frac_ext, out: *mut u64) -> c_int;
+    /// copies of the two planes of layer k, k < n, of p (`which` = 0) or q (1) as base tables of 2^k words
+    pub fn sc_frac_layer_ext(ctx: *mut sc_ctx, g: *const sc_frac_ext, k: usize, which: c_int, c0: *mut *mut sc_table, c1: *mut *mut sc_table) -> c_int;
+    /// the n layers with every challenge in K (SC_KIND_EXT_EQ_TABLE, 41, and SC_KIND_EXT_FRACTION_PASS, 43): evals 8 words per round
+    /// or null, finals 8 n, challenges 2 (n (n - 1) / 2 + 2 n - 1) words or null, point 2 n, claims 4
+    pub fn sc_frac_prove_ext(
+        ctx: *mut sc_ctx,
+        g: *const sc_frac_ext,
+        draw: sc_draw_frac_ext_fn,
+        user: *mut c_void,
+        seed_r: u64,
+        evals: *mut u64,
+        finals: *mut u64,
+        challenges: *mut u64,
+        point: *mut u64,
+        claims: *mut u64,
     ) -> c_int;
 }

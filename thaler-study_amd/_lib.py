@@ -53,7 +53,7 @@ KIND_NAMES = {0: "pass", 2: "evaluate", 3: "fold", 4: "fix_low", 5: "fold_be", 6
               17: "grid_extend", 18: "merkle", 19: "rs_encode", 20: "ligero", 21: "xc_encode", 22: "rs_long", 23: "xc_long", 24: "rs_fold", 25: "rs_fold_many",
               26: "spmv", 27: "zerocheck", 28: "product_tree", 29: "product_pass", 30: "fraction_tree", 31: "fraction_pass", 32: "lookup_count",
               33: "spark_index", 34: "spark_gather", 35: "spark_tuple", 36: "eq_sum", 37: "sumprod_pass", 38: "sumprod_ext_pass",
-              39: "ext_product_tree", 40: "ext_product_pass", 41: "ext_eq_table"}
+              39: "ext_product_tree", 40: "ext_product_pass", 41: "ext_eq_table", 42: "ext_fraction_tree", 43: "ext_fraction_pass"}
 # SC_KIND_SPARK_INDEX records: kf -> the kernel that ran
 SPARK_INDEX_KERNELS = {0: "spark_index_kernel", 1: "lookup_mont_kernel"}
 # SC_KIND_FRACTION_TREE records: kf -> the kernel that ran (kf = LV layers per launch; 0: the one-block tail)
@@ -81,6 +81,7 @@ DRAW4_FN = ctypes.CFUNCTYPE(u64, voidp, size_t, u64p)           # sc_zerocheck_p
 DRAW_GP_FN = ctypes.CFUNCTYPE(u64, voidp, size_t, size_t, u64p)    # sc_gp_prove: msg = H(0..3) of a round, or (l, r') when round == layer
 DRAW_GP_EXT_FN = ctypes.CFUNCTYPE(None, voidp, size_t, size_t, u64p, u64p)   # sc_gp_prove_ext: msg = eight words of a round, or (l, r'), four, when round == layer
 DRAW_FRAC_FN = ctypes.CFUNCTYPE(u64, voidp, size_t, size_t, u64p)  # sc_frac_prove: msg = H(0..3), (pl, pr, ql, qr) when round == layer, NULL for a lambda
+DRAW_FRAC_EXT_FN = ctypes.CFUNCTYPE(None, voidp, size_t, size_t, u64p, u64p)   # sc_frac_prove_ext: msg = eight words (a round, or the finals when round == layer), NULL for a lambda
 DRAW_FOLD_FN = ctypes.CFUNCTYPE(u64, voidp, size_t, u64p, voidp)   # root: 32 bytes, NULL at round 0
 
 # name -> (restype, argtypes); every symbol include/sumcheck_hip.h declares
@@ -216,6 +217,11 @@ SIGNATURES = {
     "sc_gp_product_ext": (ctypes.c_int, [voidp, u64p]),
     "sc_gp_layer_ext": (ctypes.c_int, [voidp, voidp, size_t, ctypes.POINTER(voidp), ctypes.POINTER(voidp)]),
     "sc_gp_prove_ext": (ctypes.c_int, [voidp, voidp, DRAW_GP_EXT_FN, voidp, u64, u64p, u64p, u64p, u64p, u64p]),
+    "sc_frac_create_ext": (ctypes.c_int, [voidp, u64, voidp, voidp, u64p, u64p, ctypes.POINTER(voidp)]),
+    "sc_frac_destroy_ext": (ctypes.c_int, [voidp, voidp]),
+    "sc_frac_root_ext": (ctypes.c_int, [voidp, u64p]),
+    "sc_frac_layer_ext": (ctypes.c_int, [voidp, voidp, size_t, ctypes.c_int, ctypes.POINTER(voidp), ctypes.POINTER(voidp)]),
+    "sc_frac_prove_ext": (ctypes.c_int, [voidp, voidp, DRAW_FRAC_EXT_FN, voidp, u64, u64p, u64p, u64p, u64p, u64p]),
     "sc_r1cs_row_weights": (ctypes.c_int, [voidp, voidp, u64p, u64p, ctypes.POINTER(voidp)]),
     "sc_circuit_create": (ctypes.c_int, [voidp, size_t, ctypes.POINTER(size_t), ctypes.POINTER(ctypes.POINTER(ctypes.c_int32)),
                                           ctypes.POINTER(ctypes.POINTER(ctypes.c_uint32)), ctypes.POINTER(ctypes.POINTER(ctypes.c_uint32)),

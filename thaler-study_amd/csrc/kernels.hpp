@@ -274,3 +274,4 @@ __device__ __forceinline__ void transpose_to_pieces(ull2* __restrict__ lds, ull2
 #include "kernels/multiopen.hpp"
 #include "kernels/ext_sumprod.hpp"
 #include "kernels/ext_grand_product.hpp"
+#include "kernels/ext_fraction.hpp"

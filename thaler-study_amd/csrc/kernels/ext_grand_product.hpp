@@ -128,6 +128,14 @@ SC_HD void ext_gp_tree_item(const F& f, u64 w, const u64 (&in)[1 << LV][2], u64 
   }
 }
 
+// e(t) m into the accumulators of t: acc[t / 2][3 (t % 2)] += e0 m0, [.. + 1] += e1 m1, [.. + 2] += (e0 + e1)(m0 + m1)
+template <class F>
+SC_HD void ext_gp_mac_cells(const F& f, typename F::Acc (&acc)[2][6], int t, const u64 (&et)[2], const u64 (&m)[2]) {
+  f.acc_mac(acc[t >> 1][3 * (t & 1)], et[0], m[0]);
+  f.acc_mac(acc[t >> 1][3 * (t & 1) + 1], et[1], m[1]);
+  f.acc_mac(acc[t >> 1][3 * (t & 1) + 2], f.add(et[0], et[1]), f.add(m[0], m[1]));
+}
+
 // One item of the cubic pass: the pairs (e, l, r)[0..1] of one index i ([entry][component]) -> the partial products of
 // e_i(t) (l_i(t) r_i(t)), t = 0 .. 3: with m = l(t) r(t), acc[t / 2][3 (t % 2)] += e0 m0, [.. + 1] += e1 m1,
 // [.. + 2] += (e0 + e1)(m0 + m1)
@@ -161,9 +169,7 @@ SC_HD void ext_gp_accumulate(const F& f, u64 w, typename F::Acc (&acc)[2][6], co
     }
     u64 m[2];
     ext_mul(f, w, lt, rt, m);
-    f.acc_mac(acc[t >> 1][3 * (t & 1)], et[0], m[0]);
-    f.acc_mac(acc[t >> 1][3 * (t & 1) + 1], et[1], m[1]);
-    f.acc_mac(acc[t >> 1][3 * (t & 1) + 2], f.add(et[0], et[1]), f.add(m[0], m[1]));
+    ext_gp_mac_cells(f, acc, t, et, m);
   }
 }
 

@@ -622,4 +622,5 @@ static int multi_prod2_fold_and_sums(sc_ctx* m, const sc_table* a, const sc_tabl
 #include "engine/abi_multiopen.inc"       // batched openings: the weighted sum of eq tables, the sumcheck over a sum of products
 #include "engine/abi_ext.inc"             // challenges from a quadratic extension: the sum-of-products sumcheck, table evaluation
 #include "engine/abi_ext_gp.inc"          // the grand product argument over the quadratic extension
+#include "engine/abi_ext_fraction.inc"    // LogUp's fraction sums over the quadratic extension
 #include "engine/abi_multi.inc"
